@@ -8,9 +8,12 @@ against its neighbour's.  Inputs live in HBM before the timed region.  With N > 
 processes its own batch (weak scaling) and every step issues one RCCL gather of the fixed-capacity
 keypoint/descriptor records to rank 0 on its own stream (monoorbslam3_amd/dist.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` for the
-dominant kernel (HIP-event timing on the launch stream) and `cpu_baseline` (the C oracle
-timed on the host cores, rank 0, N=1 only).
+Prints ONE JSON line on rank 0 (the benchmark contract).  A plain run sets up, warms up,
+times the --steps steps and prints the headline keys only (`value`, `ms_per_step`, ...).  With
+--full the line also carries `roofline` for the dominant kernel (HIP-event timing on the launch
+stream), `cpu_baseline` (the C oracle timed on the host cores, rank 0, N=1 only) and the other
+extra keys, each measured after the timed steps.  --dump-outputs DIR writes the last timed
+step's outputs as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -309,6 +312,50 @@ def bench_config5(device_index):
             "timed_by": "kernels: HIP events inside orbba_linearize on the call's stream (median of 5); calls: host clock, host arrays in and out"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_FRAMES = 64
+
+
+def dump_outputs(out_dir, n, kp, desc, cap, match=None, rec=None):
+    """`--dump-outputs DIR`: what the timed path handed its caller in its last step, as DIR/<name>.npy in float32 / float64.
+    n: (B,) key-point counts; kp / desc: (B, cap, 28) / (B, cap, 32) u8 records; match: the (index, best, second) (B, cap)
+    buffers of the best-2 search; rec: the frame-record buffers of --records.  Counts cover every frame, the per-key-point
+    arrays a fixed, seeded sample of frames (at most DUMP_MAX_FRAMES, DUMP_MAX_BYTES in all) with the rows past a frame's
+    count zeroed: the same arguments give the same inputs, so two builds can be compared array for array."""
+    from monoorbslam3_amd.extractor import KP_DTYPE
+    B, nk = int(n.shape[0]), len(KP_DTYPE.names)
+    per_frame = cap * (nk + 32 + (3 if match is not None else 0) + (nk + 2 * 2 if rec is not None else 0)) * 4
+    n_sample = max(1, min(B, DUMP_MAX_FRAMES, (DUMP_MAX_BYTES - 3 * 8 * B) // per_frame))
+    frames = np.sort(np.random.RandomState(0).choice(B, size=n_sample, replace=False))
+    sel = torch.from_numpy(frames).to(n.device)
+    counts = n.cpu().numpy().astype(np.int64)
+
+    def rows(x, dtype, cnt=counts):
+        """the sampled frames of a (B, cap, ...) device buffer as `dtype`, rows past the frame's count `cnt` zeroed"""
+        a = x.index_select(0, sel).cpu().numpy()
+        if x.shape[-1] == 28 and x.dtype == torch.uint8:   # key-point records: one column per KP_DTYPE field, in its order
+            k = np.frombuffer(a.tobytes(), KP_DTYPE).reshape(n_sample, cap)
+            a = np.stack([k[f] for f in KP_DTYPE.names], axis=-1)
+        a = a.astype(dtype)
+        a[np.arange(cap)[None, :] >= np.minimum(cnt[frames], cap)[:, None]] = 0
+        return a
+
+    arrays = {"sample_frames": frames.astype(np.float64), "n_keypoints": counts.astype(np.float64),
+              "keypoints": rows(kp, np.float32), "descriptors": rows(desc, np.float32)}
+    if match is not None:
+        idx, bd, sd = match   # distances are u16 in i16 buffers
+        arrays.update(match_index=rows(idx, np.float32), match_best_distance=rows(bd.to(torch.int32) & 0xFFFF, np.float32),
+                      match_second_distance=rows(sd.to(torch.int32) & 0xFFFF, np.float32))
+    if rec is not None:
+        words = rec["n_words"].cpu().numpy().astype(np.int64)
+        arrays.update(records_keypoints_undistorted=rows(rec["kp_un"], np.float32), records_n_words=words.astype(np.float64),
+                      records_bow_ids=rows(rec["bow_ids"], np.float64, words), records_bow_values=rows(rec["bow_vals"], np.float64, words))
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -323,6 +370,13 @@ def main():
                     help="BASELINE.json configuration: 2 = KITTI 1242x375 / 2000 features, a resident batch per GPU (the "
                          "metric's configuration, default); 4 = 1920x1080 stream, ONE frame per GPU per step (8 concurrent "
                          "frames sharded 1/GPU at --gpus 8), gathered to rank 0")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: the PCIe-inclusive rate, "
+                         "per-stage timing and rooflines, the check of the timed match, the density sweep, configs 3 and 5 and the "
+                         "CPU baseline (each can be left out with its --no-* option).  Off: the line holds the headline keys only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (key points, descriptors, best-2 matches; rank 0's) "
+                         "as DIR/<name>.npy in float32 / float64, per-key-point arrays for a fixed, seeded sample of the frames")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive measurement")
     ap.add_argument("--no-match", action="store_true", help="time extraction only")
@@ -601,6 +655,51 @@ def main():
                         "world": dist.get_world_size(), "world_c_abi": xc.world_reported() if xc is not None else None,
                         "backend": args.backend, "gather": args.gather}
     fps = world * B * args.steps / dt
+    last = (step_no[0] - 1) % NBUF   # the output set of the last timed step (its match ran in sync's flush)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_n[last], d_kp[last], d_desc[last], cap,
+                     None if args.no_match else (d_bidx[last], d_bd[last], d_sd[last]),
+                     {k: v[last] for k, v in rec.items() if isinstance(v, list)} if rec else None)
+    head = {
+        "metric": baseline_metric(),
+        "value": round(fps, 2),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "clock_warmup_steps": args.clock_warmup_steps,
+        "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "scaling_diag": scaling_diag,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {"workload": ("KITTI 1242x375, 2000 feat, 8-level pyramid scale 1.2, FAST 20/7; extract + "
+                                "2000x2000 Hamming best-2 per frame" + (" + frame records (undistort, grid, bag of words)" if args.records else "")
+                                if (W, H, NF) == (1242, 375, 2000) else
+                                "Batched synthetic 1920x1080 stream, 2000 feat, %d concurrent frame(s) sharded %d/GPU, RCCL gather "
+                                "over xGMI; extract + Hamming best-2 against the previous frame" % (world * B, B)
+                                if (W, H, NF) == (1920, 1080, 2000) else "%dx%d, %d feat" % (W, H, NF)),
+                   "baseline_config": args.config,
+                   "frames_per_gpu_per_step": B, "width": W, "height": H, "n_features": NF,
+                   "match": not args.no_match, "records": bool(args.records),
+                   "match_placement": None if args.no_match else args.match_placement, "best2_resident": args.best2_resident,
+                   "parallelism": ("frames sharded %d per GPU per step over %d GPU(s), one gather of the fixed-capacity records "
+                                   "to rank 0 per step" % (B, world)) if world > 1 else
+                                  "%d resident frame(s) on one GPU, no collective" % B},
+        "full": bool(args.full),
+    }
+    if not args.full:
+        # a plain run: the headline and nothing else (every other measurement and check below is --full's)
+        if rank == 0:
+            print(json.dumps(dict(head, keypoints_per_frame=round(float(d_n[last].float().mean().item()), 1),
+                                  records={"words_per_frame": round(float(rec["n_words"][last].float().mean().item()), 1)} if rec else None)),
+                  flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- PCIe-inclusive rate (SURVEY 8d "report both"; never `value`): the same steps, but every batch arrives from
     # pinned host memory (H2D of level 0) and its records -- counts, 28-byte key points, 32-byte descriptors at their fixed
@@ -910,34 +1009,7 @@ def main():
                             "fast_frac_of_hbm_peak": round(P * B / (accd["fast"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)})
             del fr
 
-    out = {
-        "metric": baseline_metric(),
-        "value": round(fps, 2),
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "clock_warmup_steps": args.clock_warmup_steps,
-        "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "scaling_diag": scaling_diag,
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {"workload": ("KITTI 1242x375, 2000 feat, 8-level pyramid scale 1.2, FAST 20/7; extract + "
-                                "2000x2000 Hamming best-2 per frame" + (" + frame records (undistort, grid, bag of words)" if args.records else "")
-                                if (W, H, NF) == (1242, 375, 2000) else
-                                "Batched synthetic 1920x1080 stream, 2000 feat, %d concurrent frame(s) sharded %d/GPU, RCCL gather "
-                                "over xGMI; extract + Hamming best-2 against the previous frame" % (world * B, B)
-                                if (W, H, NF) == (1920, 1080, 2000) else "%dx%d, %d feat" % (W, H, NF)),
-                   "baseline_config": args.config,
-                   "frames_per_gpu_per_step": B, "width": W, "height": H, "n_features": NF,
-                   "match": not args.no_match, "records": bool(args.records),
-                   "match_placement": None if args.no_match else args.match_placement, "best2_resident": args.best2_resident,
-                   "parallelism": ("frames sharded %d per GPU per step over %d GPU(s), one gather of the fixed-capacity records "
-                                   "to rank 0 per step" % (B, world)) if world > 1 else
-                                  "%d resident frame(s) on one GPU, no collective" % B},
+    out = dict(head, **{
         "keypoints_per_frame": round(kp_mean, 1),
         "records": ({"words_per_frame": round(float(rec["n_words"][0].float().mean().item()), 1),
                      "fv_nodes_per_frame": round(float(rec["n_fv"][0].float().mean().item()), 1),
@@ -966,7 +1038,7 @@ def main():
                                      "algorithmic_bytes_per_frame": 2 * P},
         "valu_issue": {"rates_gwinst_s": {"cheap_class": VALU_RATE_CHEAP_GWINST, "slow_class": VALU_RATE_SLOW_GWINST},
                        "stages": valu, "source": valu_source},
-    }
+    })
     if e2e is not None:
         out["value_end_to_end"] = e2e
     if world == 1 and not args.no_extra_configs:

@@ -1,8 +1,9 @@
 #!/bin/bash
 # Per-launch kernel durations (median / min per kernel and grid size) from a rocprofv3 kernel trace of a short bench run;
 # shows e.g. the seven resize levels separately.  Run on the GPU box from the repository root.
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -o r -- python3 $GRAFT_REPO_ROOT/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-match --batch 256 > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -o r -- python3 "$ROOT/bench.py" --full --steps 6 --warmup 2 --no-cpu-baseline --no-match --batch 256 > /dev/null 2>&1
 python3 - <<'PY'
 import csv, glob, collections
 f = glob.glob('/tmp/tr/**/*kernel_trace.csv', recursive=True)[0]
