@@ -44,6 +44,8 @@ void orbm_destroy(orbm_t *h);
                                    * registers and 37 KB of LDS per workgroup) -- for a caller that runs it beside other kernels */
 #define ORBM_VAR_INIT_LANES 3 /* orbm_search_for_initialization_device: lanes that share one query's window list in the resolve kernel:
                               * 0 chosen from the mean list length (default), or 1, 4, 16, 64 (the parity twins) */
+#define ORBM_VAR_INIT_MAX_SWEEPS 4 /* orbm_search_for_initialization_device: sweeps of the fixed point before it gives up (d_result[1]
+                                    * = 2): 0 = ORBM_INIT_MAX_SWEEPS (default), or 1 .. ORBM_INIT_MAX_SWEEPS */
 int orbm_set_variant(orbm_t *h, int which, int value);
 
 /* DBoW2::FeatureVector (thirdParty/DBoW2/DBoW2/FeatureVector.h) flattened to CSR:
@@ -236,7 +238,8 @@ int orbm_search_by_projection_points_device(orbm_t *h, float nn_ratio, const uin
  * Limits: n2 + 5 n1 <= 38400 (the claims live in LDS), list_cap entries per query on average (pool of n1 * list_cap).
  * d_result (int32 x 8): [0] matches, [1] = 1 when the lists overflowed the pool (d_matches12 all -1, d_pre untouched: repeat with
  * a larger list_cap or use the host entry point), [1] = 2 when the fixed point had not settled after ORBM_INIT_MAX_SWEEPS sweeps
- * (same guarantee: nothing written; use the host entry point), [2] sweeps of the fixed point, [3] list entries.
+ * (ORBM_VAR_INIT_MAX_SWEEPS lowers the cap; same guarantee: nothing written; use the host entry point), [2] sweeps of the fixed
+ * point (the cap when [1] = 2), [3] list entries.
  * Cost: ONE workgroup resolves the search; a sweep walks every level-0 feature's window list (1, 4 or 16 lanes share a list,
  * chosen from the mean list length: ORBM_VAR_INIT_LANES) and, per entry, the chain of queries that claim that candidate.  Measured
  * device time of the whole call (profiles/r06_match_latency.txt): 0.11 ms on two extracted views (22 entries per list, 3 sweeps; the

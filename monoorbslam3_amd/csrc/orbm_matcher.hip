@@ -1454,6 +1454,7 @@ struct orbm_ctx {
     int best2_variant = 0;      // ORBM_VAR_BEST2: 0 = fp4, 1 = i8, 2 = valu
     int init_lanes = 0;         // ORBM_VAR_INIT_LANES: lanes per query of k_init_resolve: 0 = by list length (default), 1, 4, 16, 64
     int best2_resident = 0;     // ORBM_VAR_BEST2_RESIDENT: k_best2_fp4 as a grid of this many workgroups per CU (0 = one per block of queries)
+    int init_max_sweeps = 0;    // ORBM_VAR_INIT_MAX_SWEEPS: k_init_resolve gives up after this many sweeps (0 = ORBM_INIT_MAX_SWEEPS)
     int n_cus = 256;            // the device's CU count (set at create)
     size_t window_last_total = 0; // candidates the previous window search returned (sizes the first copy-out)
 };
@@ -1495,6 +1496,7 @@ extern "C" int orbm_set_variant(orbm_t *c, int which, int value)
     if (which == ORBM_VAR_WINDOW && (value == 0 || value == 1)) { c->window_on_device = !value; return ORBX_OK; }
     if (which == ORBM_VAR_BEST2_RESIDENT && value >= 0 && value <= 2) { c->best2_resident = value; return ORBX_OK; }
     if (which == ORBM_VAR_INIT_LANES && (value == 0 || value == 1 || value == 4 || value == 16 || value == 64)) { c->init_lanes = value; return ORBX_OK; }
+    if (which == ORBM_VAR_INIT_MAX_SWEEPS && value >= 0 && value <= ORBM_INIT_MAX_SWEEPS) { c->init_max_sweeps = value; return ORBX_OK; }
     return orbx_set_error(ORBX_E_ARG, "unknown matcher variant switch or value out of range");
 }
 
@@ -2561,7 +2563,8 @@ extern "C" int orbm_search_for_initialization_device(orbm_t *c, float nn_ratio, 
                        d_counts, d_pool, d_total, d_offs);
     M_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_init_resolve), 150 * 1024));
     hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(PR_T), lds, s, d_counts, d_offs, d_pool, (int)std::min(pool_cap, (size_t)INT_MAX), d_total,
-                       n1, n2, (const orbx_kp *)d_kps1, (const orbx_kp *)d_kps2, nn_ratio, check_orientation, ORBM_INIT_MAX_SWEEPS, c->init_lanes, d_matches12,
+                       n1, n2, (const orbx_kp *)d_kps1, (const orbx_kp *)d_kps2, nn_ratio, check_orientation,
+                       c->init_max_sweeps > 0 ? c->init_max_sweeps : ORBM_INIT_MAX_SWEEPS, c->init_lanes, d_matches12,
                        d_pre, d_result);
     M_TRY(hipGetLastError());
     return ORBX_OK;

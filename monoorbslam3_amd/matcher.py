@@ -14,6 +14,8 @@ from . import _lib
 from .extractor import KP_DTYPE
 
 TH_LOW, TH_HIGH, HISTO_LENGTH = 50, 100, 30
+# kernel-choice switches of include/orbm.h (ORBM_VAR_*): name -> index
+VARIANTS = {"best2": 0, "window": 1, "best2_resident": 2, "init_lanes": 3, "init_max_sweeps": 4}
 
 
 class _Fv(C.Structure):
@@ -105,8 +107,9 @@ class MatcherHandle:
 
     def set_variant(self, name, value):
         """orbm_set_variant: "best2" = "fp4" | "i8" | "valu" (dense best / second-best kernel), "window" = "device" | "host",
-        "best2_resident" = 0 | 1 | 2 (k_best2_fp4 as that many workgroups per CU walking the query blocks)."""
-        which = {"best2": 0, "window": 1, "best2_resident": 2, "init_lanes": 3}[name]
+        "best2_resident" = 0 | 1 | 2 (k_best2_fp4 as that many workgroups per CU walking the query blocks), "init_lanes" = 0 | 1 |
+        4 | 16 | 64, "init_max_sweeps" = 0 (the default cap, ORBM_INIT_MAX_SWEEPS) | 1 .. 64 (SearchForInitializationDevice)."""
+        which = VARIANTS[name]
         val = {"fp4": 0, "i8": 1, "valu": 2, "device": 0, "host": 1}.get(value, value)
         _lib.check(self._L.orbm_set_variant(self._h, which, int(val)))
 
@@ -298,7 +301,10 @@ class ORBMatcher:
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
         orbf_frame_post_device leaves it), desc2, cell_start, cell_items, pre (float32 [n1, 2], in / out), matches12 (int32 [n1], out),
-        result (int32 x 8, out))."""
+        result (int32 x 8, out)).  result[0] is the match count and result[2] the sweeps of the fixed point.  result[1] = 1: the window
+        lists overflowed the pool of n1 * list_cap entries; result[1] = 2: the fixed point had not settled within the sweep cap
+        (set_variant("init_max_sweeps"), default 64).  In both cases nothing was written -- matches12 is all -1, pre is untouched,
+        result[0] is 0 -- and the caller runs the host entry point, SearchForInitialization, instead."""
         p = lambda k: d[k].data_ptr()  # noqa: E731
         _lib.check(self._L.orbm_search_for_initialization_device(
             self._hd._h, self.nn_ratio, int(self.be_check_orientation), p("kps1"), p("desc1"), n1, p("kps2"), p("desc2"),

@@ -49,6 +49,22 @@ def test_kp_record_layout_matches_cv_keypoint():
         [0, 4, 8, 12, 16, 20, 24]
 
 
+def _defines(header, prefix):
+    txt = open(os.path.join(ROOT, "include", header)).read()
+    return {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define\s+%s([A-Z0-9_]+)\s+(-?\d+)" % prefix, txt)}
+
+
+def test_variant_ids_of_the_python_wrappers_match_the_headers():
+    """extractor.VARIANTS / matcher.VARIANTS name every ORBX_VAR_* / ORBM_VAR_* switch with its id, and nothing else"""
+    from monoorbslam3_amd import extractor, matcher
+    orbx = _defines("orbx.h", "ORBX_VAR_")
+    assert {k: v[0] for k, v in extractor.VARIANTS.items()} == orbx
+    assert sorted(orbx.values()) == list(range(_defines("orbx.h", "ORBX_N_")["variants"]))
+    orbm = _defines("orbm.h", "ORBM_VAR_")
+    assert matcher.VARIANTS == orbm and "init_max_sweeps" in orbm
+    assert sorted(orbm.values()) == list(range(len(orbm)))
+
+
 def test_fails_loudly_without_a_gpu(built):
     import torch
     if torch.cuda.is_available():

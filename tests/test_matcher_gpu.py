@@ -197,6 +197,20 @@ def test_search_for_initialization_on_extracted_frames(oracle_mod):
         assert n_got > 50
 
 
+def _crowd(n, seed):
+    """crowded scene for SearchForInitialization: n level-0 features (a few at level 1) inside a 260 x 200 px area of a 752 x 480
+    frame, descriptors from 40 clusters with a few flipped bits -- many features want the same candidate"""
+    from monoorbslam3_amd.extractor import KP_DTYPE
+    centres = np.random.RandomState(2026).randint(0, 256, (40, 32)).astype(np.uint8)
+    r = np.random.RandomState(seed)
+    k = np.zeros(n, KP_DTYPE)
+    k["x"] = r.uniform(200, 460, n).astype(np.float32); k["y"] = r.uniform(100, 300, n).astype(np.float32)
+    k["size"] = 1.0; k["angle"] = (r.normal(40, 25, n) % 360).astype(np.float32); k["octave"] = (r.uniform(size=n) > 0.85).astype(np.int32)
+    k["class_id"] = -1
+    d = centres[r.randint(0, 40, n)] ^ np.packbits(r.uniform(size=(n, 256)) < 0.03, axis=1, bitorder="little")
+    return k, d.astype(np.uint8)
+
+
 @pytest.mark.parametrize("ori", [True, False])
 def test_search_for_initialization_on_the_device(oracle_mod, ori):
     """orbm_search_for_initialization_device (ORBMatcher.cpp:33-116 with the window lists, the stealing rule of :63 / :75-81, the
@@ -205,7 +219,7 @@ def test_search_for_initialization_on_the_device(oracle_mod, ori):
     crowded synthetic scene (near-duplicate descriptors in a small area: many features want the same candidate, several are robbed,
     the fixed point needs more than two sweeps)."""
     import torch
-    from monoorbslam3_amd.extractor import ORBExtractor, KP_DTYPE
+    from monoorbslam3_amd.extractor import ORBExtractor
     from monoorbslam3_amd.frame import FramePost
     from monoorbslam3_amd.matcher import ORBMatcher
     dev = torch.device("cuda", 0)
@@ -215,18 +229,7 @@ def test_search_for_initialization_on_the_device(oracle_mod, ori):
     f2 = np.ascontiguousarray(canvas[9:9 + h, 22:22 + w])
     ex = ORBExtractor(2000, 1.2, 8, 20, 7)
     cases = [("views",) + ex(f1) + ex(f2)]
-    # crowded: 900 level-0 features of either frame inside a 260 x 200 px area, descriptors from 40 clusters with a few flipped bits
-    rng = np.random.RandomState(2026)
-    centres = rng.randint(0, 256, (40, 32)).astype(np.uint8)
-    def crowd(n, seed):
-        r = np.random.RandomState(seed)
-        k = np.zeros(n, KP_DTYPE)
-        k["x"] = r.uniform(200, 460, n).astype(np.float32); k["y"] = r.uniform(100, 300, n).astype(np.float32)
-        k["size"] = 1.0; k["angle"] = (r.normal(40, 25, n) % 360).astype(np.float32); k["octave"] = (r.uniform(size=n) > 0.85).astype(np.int32)
-        k["class_id"] = -1
-        d = centres[r.randint(0, 40, n)] ^ np.packbits(r.uniform(size=(n, 256)) < 0.03, axis=1, bitorder="little")
-        return k, d.astype(np.uint8)
-    cases.append(("crowded",) + crowd(900, 1) + crowd(850, 2))
+    cases.append(("crowded",) + _crowd(900, 1) + _crowd(850, 2))
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
     kp = lambda k: torch.from_numpy(np.frombuffer(np.ascontiguousarray(k).tobytes(), np.uint8).copy()).to(dev)  # noqa: E731
     post = FramePost(w, h, 460.0, 460.0, w / 2.0, h / 2.0)
@@ -268,6 +271,59 @@ def test_search_for_initialization_on_the_device(oracle_mod, ori):
     d["matches12"].fill_(7)
     m.SearchForInitializationDevice(d, n1, 0, post.cols, post.rows)
     assert (d["matches12"].cpu().numpy() == -1).all() and int(d["result"][0]) == 0
+
+
+def test_search_for_initialization_on_the_device_sweep_cap(oracle_mod):
+    """The give-up path of k_init_resolve (ORBM_VAR_INIT_MAX_SWEEPS): on the crowded scene the fixed point takes s > 2 sweeps, the
+    last of which changes nothing.  A cap of s still returns the oracle's answer (the off-by-one edge); a cap of s - 1 or 1 stops
+    with result[1] = 2, result[0] = 0, result[2] = the cap, matches12 all -1 and pre untouched; back at the default the answer is
+    the oracle's again.  Values outside 0 .. 64 are refused."""
+    import torch
+    from monoorbslam3_amd._lib import OrbxError
+    from monoorbslam3_amd.frame import FramePost
+    from monoorbslam3_amd.matcher import MatcherHandle, ORBMatcher
+    dev = torch.device("cuda", 0)
+    w, h = 752, 480
+    (k1, d1), (k2, d2) = _crowd(900, 1), _crowd(850, 2)
+    n1, n2 = len(k1), len(k2)
+    pre = np.stack([k1["x"], k1["y"]], axis=1).astype(np.float32)
+    n_ref, m_ref, pre_ref = oracle_mod.search_for_initialization(0.9, True, k1, d1, k2, d2, w, h, pre, 100)
+    assert n_ref > 50 and not np.array_equal(pre_ref, pre)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    kp = lambda k: torch.from_numpy(np.frombuffer(np.ascontiguousarray(k).tobytes(), np.uint8).copy()).to(dev)  # noqa: E731
+    post = FramePost(w, h, 460.0, 460.0, w / 2.0, h / 2.0)
+    _, k2u, start, items = post(k2)
+    d = dict(kps1=kp(k1), desc1=up(d1), kps2=kp(k2u), desc2=up(d2), cell_start=up(start.astype(np.int32)),
+             cell_items=up(np.concatenate([items, np.zeros(1, items.dtype)]).astype(np.int32)), pre=up(pre),
+             matches12=torch.full((n1,), 7, dtype=torch.int32, device=dev), result=torch.zeros(8, dtype=torch.int32, device=dev))
+    hd = MatcherHandle(device=0)
+    m = ORBMatcher(0.9, True, handle=hd)
+
+    def run(cap):
+        hd.set_variant("init_max_sweeps", cap)
+        d["pre"].copy_(up(pre)); d["matches12"].fill_(7); d["result"].fill_(-9)
+        m.SearchForInitializationDevice(d, n1, n2, post.cols, post.rows, window=100, list_cap=1024)
+        return d["result"].cpu().numpy(), d["matches12"].cpu().numpy(), d["pre"].cpu().numpy()
+
+    res, m12, p = run(0)
+    s = int(res[2])
+    assert s > 2, res                       # the fixed point had chains to follow
+    assert res[1] == 0 and res[0] == n_ref and np.array_equal(m12, m_ref) and np.array_equal(p, pre_ref), res
+    entries = int(res[3])
+    res, m12, p = run(s)                    # the last sweep changes nothing: a cap of s is enough
+    assert res[1] == 0 and res[0] == n_ref and res[2] == s, (s, res)
+    assert np.array_equal(m12, m_ref) and np.array_equal(p, pre_ref), s
+    for cap in (s - 1, 1):
+        res, m12, p = run(cap)
+        assert res[1] == 2 and res[0] == 0 and res[2] == cap and res[3] == entries, (cap, s, res)
+        assert (m12 == -1).all(), (cap, np.unique(m12)[:8])
+        assert p.tobytes() == pre.tobytes(), cap
+    res, m12, p = run(0)                    # back to the default cap
+    assert res[1] == 0 and res[0] == n_ref and res[2] == s, res
+    assert np.array_equal(m12, m_ref) and np.array_equal(p, pre_ref)
+    for bad in (-1, 65):
+        with pytest.raises(OrbxError):
+            hd.set_variant("init_max_sweeps", bad)
 
 
 def _two_views(w=752, h=480, nf=2000):
