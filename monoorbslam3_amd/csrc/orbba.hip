@@ -14,21 +14,14 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/orbba.h"
 #include "../../include/orbx.h"
+#include "orb_host.h"
 
-int orbx_set_error(int code, const std::string &msg);
 hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes); // orbx_api.hip: dynamic LDS above 64 KB, per kernel and per device
-#define B_TRY(expr)                                                                                    \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return orbx_set_error(ORBX_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // kernel-choice switches of the BA entry points (include/orbba.h: orbba_set_variant); the entry points take no handle, so the
 // switches are per process and read per call
@@ -237,67 +230,25 @@ struct BaWork {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    uint8_t *d = nullptr, *h = nullptr;
-    size_t d_bytes = 0, h_bytes = 0;
-    hipError_t need(size_t dev_bytes, size_t host_bytes)
+    DevBuf d;
+    PinBuf h;
+    hipError_t init()
     {
-        hipError_t e = hipSuccess;
-        if (dev_bytes > d_bytes) {
-            if (d) (void)hipFree(d);
-            d = nullptr; d_bytes = 0;
-            const size_t want = dev_bytes + dev_bytes / 4;
-            if ((e = hipMalloc((void **)&d, want)) != hipSuccess) return e;
-            d_bytes = want;
-        }
-        if (host_bytes > h_bytes) {
-            if (h) (void)hipHostFree(h);
-            h = nullptr; h_bytes = 0;
-            const size_t want = host_bytes + host_bytes / 4;
-            if ((e = hipHostMalloc((void **)&h, want, hipHostMallocDefault)) != hipSuccess) return e;
-            h_bytes = want;
+        hipError_t e;
+        if ((e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) != hipSuccess || (e = hipEventCreate(&e0)) != hipSuccess ||
+            (e = hipEventCreate(&e1)) != hipSuccess) {
+            if (e0) (void)hipEventDestroy(e0);
+            if (stream) (void)hipStreamDestroy(stream);
         }
         return e;
     }
-};
-std::mutex g_work_mu;
-std::vector<BaWork *> g_work_idle; // never destroyed: the HIP runtime may be gone when static destructors run
-
-struct BaLease {
-    BaWork *w = nullptr;
-    ~BaLease()
+    hipError_t need(size_t dev_bytes, size_t host_bytes)
     {
-        if (!w) return;
-        (void)hipStreamSynchronize(w->stream); // an error return may leave work in flight: the next lessee must not meet it
-        std::lock_guard<std::mutex> lock(g_work_mu);
-        g_work_idle.push_back(w);
-    }
-    hipError_t acquire()
-    {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        {
-            std::lock_guard<std::mutex> lock(g_work_mu);
-            for (size_t i = 0; i < g_work_idle.size(); ++i)
-                if (g_work_idle[i]->device == dev) {
-                    w = g_work_idle[i];
-                    g_work_idle.erase(g_work_idle.begin() + (long)i);
-                    return hipSuccess;
-                }
-        }
-        BaWork *n = new BaWork();
-        n->device = dev;
-        if ((e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking)) != hipSuccess || (e = hipEventCreate(&n->e0)) != hipSuccess ||
-            (e = hipEventCreate(&n->e1)) != hipSuccess) {
-            if (n->e0) (void)hipEventDestroy(n->e0);
-            if (n->stream) (void)hipStreamDestroy(n->stream);
-            delete n;
-            return e;
-        }
-        w = n;
-        return hipSuccess;
+        hipError_t e = d.need(dev_bytes, dev_bytes + dev_bytes / 4);
+        return e == hipSuccess ? h.need(host_bytes, host_bytes + host_bytes / 4) : e;
     }
 };
+LeasePool<BaWork> g_work; // per process, keyed by device; never freed: the HIP runtime may be gone when static destructors run
 // offsets of a call's arrays in the arena (and, for the staged ones, in the page-locked block), 256-byte aligned
 struct Layout {
     size_t n = 0;
@@ -312,10 +263,8 @@ extern "C" int orbba_linearize(const orbba_problem *p, orbba_result *r, int devi
     if (p->n_poses < 1 || p->n_points < 1 || p->n_edges < 0) return orbx_set_error(ORBX_E_ARG, "bad sizes");
     if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || (p->n_edges && (!p->edge_pose || !p->edge_point || !p->edge_z || !p->edge_inv_sigma2)))
         return orbx_set_error(ORBX_E_ARG, "null input array");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device >= 0) B_TRY(hipSetDevice(device));
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
     const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
     // host-side index structures: edges per pose (CSR, edge order) and the contiguous range of each point
     std::vector<int> pose_off(NP + 1, 0), pose_edges(std::max(NE, 1)), point_off(NL + 1, 0);
@@ -345,12 +294,12 @@ extern "C" int orbba_linearize(const orbba_problem *p, orbba_result *r, int devi
     const size_t out_small_end = L.n;
     const size_t oHlp = L.add(144 * (size_t)NE);
     const size_t out_end = (r->H_lp && NE) ? L.n : out_small_end;
-    BaLease lease;
-    B_TRY(lease.acquire());
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
     BaWork *w = lease.w;
-    B_TRY(w->need(L.n, std::max(in_bytes, out_end - out_begin)));
+    ORB_TRY(w->need(L.n, std::max(in_bytes, out_end - out_begin)));
     hipStream_t s = w->stream;
-    uint8_t *d = w->d, *h = w->h;
+    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>();
     put(h, oR, p->pose_R, 72 * (size_t)NP); put(h, ot, p->pose_t, 24 * (size_t)NP); put(h, ofix, p->pose_fixed, NP);
     put(h, oP, p->points, 24 * (size_t)NL);
     if (NE) {
@@ -358,22 +307,22 @@ extern "C" int orbba_linearize(const orbba_problem *p, orbba_result *r, int devi
         put(h, ow, p->edge_inv_sigma2, 8 * (size_t)NE); put(h, ope, pose_edges.data(), 4 * (size_t)NE);
     }
     put(h, opo, pose_off.data(), 4 * (size_t)(NP + 1)); put(h, olo, point_off.data(), 4 * (size_t)(NL + 1));
-    B_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
     const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
     auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
     auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
-    B_TRY(hipEventRecord(w->e0, s));
+    ORB_TRY(hipEventRecord(w->e0, s));
     if (NE)
         hipLaunchKernelGGL(k_ba_edges, dim3((NE + 255) / 256), dim3(256), 0, s, cam, NE, D(oR), D(ot), d + ofix, D(oP), I(oep), I(oel), D(oz),
                            D(ow), (const uint8_t *)nullptr, D(ochi), D(oerr), D(oHlp), D(oCpp), D(oCll));
     hipLaunchKernelGGL(k_ba_reduce_pose, dim3(NP), dim3(256), 0, s, I(opo), I(ope), D(oCpp), D(oHpp), D(obp));
     hipLaunchKernelGGL(k_ba_reduce_point, dim3((NL + 255) / 256), dim3(256), 0, s, NL, I(olo), D(oCll), D(oHll), D(obl));
-    B_TRY(hipEventRecord(w->e1, s));
-    B_TRY(hipGetLastError());
-    B_TRY(hipMemcpyAsync(h, d + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, s));
-    B_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipEventRecord(w->e1, s));
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(h, d + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     float ms = 0;
-    B_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
+    ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
     r->kernel_ms = ms;
     auto O = [&](size_t off) { return h + (off - out_begin); }; // an output's place in the staging block
     if (r->chi2 && NE) memcpy(r->chi2, O(ochi), 8 * (size_t)NE);
@@ -759,10 +708,8 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
         !p->edge_inv_sigma2)
         return orbx_set_error(ORBX_E_ARG, "null input array");
     if (o->max_iterations < 0) return orbx_set_error(ORBX_E_ARG, "negative iteration count");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device >= 0) B_TRY(hipSetDevice(device));
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
     const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
     const double tau = o->tau > 0 ? o->tau : 1e-5, lower = o->good_step_lower > 0 ? o->good_step_lower : 1.0 / 3.0,
                  upper = o->good_step_upper > 0 ? o->good_step_upper : 2.0 / 3.0;
@@ -816,13 +763,13 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
     // page-locked block: [read-back][inputs up / results down]
     Layout HL;
     const size_t hrb = HL.add(8 * (size_t)RB_N), hio = HL.add(std::max(in_bytes, est_bytes + 8 * (size_t)NE + 256));
-    BaLease lease;
-    B_TRY(lease.acquire());
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
     BaWork *w = lease.w;
-    B_TRY(w->need(L.n, HL.n));
+    ORB_TRY(w->need(L.n, HL.n));
     hipStream_t s = w->stream;
-    uint8_t *d = w->d, *h = w->h + hio;
-    double *const rb = reinterpret_cast<double *>(w->h + hrb);
+    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>() + hio;
+    double *const rb = reinterpret_cast<double *>(w->h.as<uint8_t>() + hrb);
     put(h, oR, p->pose_R, 72 * (size_t)NP); put(h, ot, p->pose_t, 24 * (size_t)NP); put(h, oP, p->points, 24 * (size_t)NL);
     put(h, ofix, p->pose_fixed, NP); put(h, oep, p->edge_pose, 4 * (size_t)NE); put(h, oel, p->edge_point, 4 * (size_t)NE);
     put(h, oz, p->edge_z, 16 * (size_t)NE); put(h, ow, p->edge_inv_sigma2, 8 * (size_t)NE);
@@ -830,12 +777,12 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
     put(h, opo, pose_off.data(), 4 * (size_t)(NP + 1)); put(h, ope, pose_edges.data(), 4 * (size_t)NE);
     put(h, olo, point_off.data(), 4 * (size_t)(NL + 1)); put(h, ofree, free_pose.data(), 4 * (size_t)NF);
     put(h, oslot, pose_slot.data(), 4 * (size_t)NP); put(h, oeo, edge_of.data(), (size_t)4 * NF * NL);
-    B_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
     auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
     auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
     const uint8_t *d_active = o->edge_active ? d + oact : nullptr;
     const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
-    B_TRY(hipEventRecord(w->e0, s));
+    ORB_TRY(hipEventRecord(w->e0, s));
 
     // errors at the current estimate (+ the whole linearisation when `full`); activeRobustChi2 as partial sums into the
     // read-back block's slot `slot`
@@ -851,9 +798,9 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
     };
     // the read-back block in host memory: the call's only waits besides the final one
     auto read_back = [&]() -> int {
-        B_TRY(hipGetLastError());
-        B_TRY(hipMemcpyAsync(rb, d + orb, 8 * (size_t)RB_N, hipMemcpyDeviceToHost, s));
-        B_TRY(hipStreamSynchronize(s));
+        ORB_TRY(hipGetLastError());
+        ORB_TRY(hipMemcpyAsync(rb, d + orb, 8 * (size_t)RB_N, hipMemcpyDeviceToHost, s));
+        ORB_TRY(hipStreamSynchronize(s));
         return ORBX_OK;
     };
     auto sum = [&](int from, int n) { double v = 0.0; for (int b = 0; b < n; ++b) v += rb[from + b]; return v; };
@@ -878,7 +825,7 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
         int qmax = 0;
         do {
             // push(): keep the estimates
-            B_TRY(hipMemcpyAsync(d + oRb, d + oR, est_bytes, hipMemcpyDeviceToDevice, s)); // R, t, P and their copies are laid out alike
+            ORB_TRY(hipMemcpyAsync(d + oRb, d + oR, est_bytes, hipMemcpyDeviceToDevice, s)); // R, t, P and their copies are laid out alike
             hipLaunchKernelGGL(k_lm_points, dim3(LB), dim3(256), 0, s, NL, lam, D(oHll), D(obl), D(oinv), D(otl));
             hipLaunchKernelGGL(k_lm_schur, dim3(NF * (NF + 1) / 2), dim3(256), 0, s, NF, NL, lam, I(ofree), I(oeo), D(oHpp), D(obp), D(oHlp),
                                D(oinv), D(otl), D(oS), D(orhs));
@@ -897,7 +844,7 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
             }
             if (!in_lds) {
                 hipLaunchKernelGGL(k_lm_chol_solve, dim3(1), dim3(256), 0, s, N, D(oS), D(orhs), D(oxp), d_flag);
-                B_TRY(hipGetLastError());
+                ORB_TRY(hipGetLastError());
             }
             hipLaunchKernelGGL(k_lm_backsub, dim3(LB), dim3(256), 0, s, NL, lam, I(olo), I(oep), I(oslot), D(oHlp), D(oxp), D(obl), D(oinv),
                                D(oxl), D(orb) + RB_SCL);
@@ -926,7 +873,7 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
                 lam *= ni;
                 ni *= 2;
                 // pop(): restore
-                B_TRY(hipMemcpyAsync(d + oR, d + oRb, est_bytes, hipMemcpyDeviceToDevice, s));
+                ORB_TRY(hipMemcpyAsync(d + oR, d + oRb, est_bytes, hipMemcpyDeviceToDevice, s));
                 if (!std::isfinite(lam)) break;
             }
             ++qmax;
@@ -935,15 +882,15 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
         if (qmax == max_trials || rho == 0 || !std::isfinite(lam)) break; // Terminate
     }
     evaluate(false, RB_TRY);
-    B_TRY(hipEventRecord(w->e1, s));
-    B_TRY(hipGetLastError());
-    B_TRY(hipMemcpyAsync(rb, d + orb, 8 * (size_t)RB_N, hipMemcpyDeviceToHost, s));
-    B_TRY(hipMemcpyAsync(h, d, est_bytes, hipMemcpyDeviceToHost, s));
-    if (r->chi2) B_TRY(hipMemcpyAsync(h + est_bytes, d + ochi, 8 * (size_t)NE, hipMemcpyDeviceToHost, s));
-    B_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipEventRecord(w->e1, s));
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(rb, d + orb, 8 * (size_t)RB_N, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(h, d, est_bytes, hipMemcpyDeviceToHost, s));
+    if (r->chi2) ORB_TRY(hipMemcpyAsync(h + est_bytes, d + ochi, 8 * (size_t)NE, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     const double final_chi = sum(RB_TRY, EB);
     float ms = 0;
-    B_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
+    ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
     r->iterations = its;
     r->trials = trials_total;
     r->lambda = lam;
@@ -1300,10 +1247,8 @@ extern "C" int orbba_pose_optimize_batch(const orbba_pose_problem *p, orbba_pose
             return orbx_set_error(ORBX_E_ARG, "edge offsets must start at 0 and be non-decreasing");
     if (NE > 0 && (!p->points || !p->edge_z || !p->edge_inv_sigma2)) return orbx_set_error(ORBX_E_ARG, "null edge array");
     if (!r->pose_R || !r->pose_t || !r->n_inliers || (NE > 0 && !r->inlier)) return orbx_set_error(ORBX_E_ARG, "null output array");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device >= 0) B_TRY(hipSetDevice(device));
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
     // arena: [inputs, one copy up][results, one copy down]
     Layout L;
     const size_t ooff = L.add(4 * (size_t)(B + 1)), oR0 = L.add(72 * (size_t)B), ot0 = L.add(24 * (size_t)B), oP = L.add(24 * (size_t)NE),
@@ -1313,31 +1258,31 @@ extern "C" int orbba_pose_optimize_batch(const orbba_pose_problem *p, orbba_pose
     const size_t out_small_end = L.n;
     const size_t ochi = L.add(8 * (size_t)NE);
     const size_t out_end = (NE && r->chi2) ? L.n : out_small_end;
-    BaLease lease;
-    B_TRY(lease.acquire());
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
     BaWork *w = lease.w;
-    B_TRY(w->need(L.n, std::max(in_bytes, out_end - in_bytes)));
+    ORB_TRY(w->need(L.n, std::max(in_bytes, out_end - in_bytes)));
     hipStream_t s = w->stream;
-    uint8_t *d = w->d, *h = w->h;
+    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>();
     put(h, ooff, p->edge_off, 4 * (size_t)(B + 1)); put(h, oR0, p->pose_R, 72 * (size_t)B); put(h, ot0, p->pose_t, 24 * (size_t)B);
     if (NE) { put(h, oP, p->points, 24 * (size_t)NE); put(h, oz, p->edge_z, 16 * (size_t)NE); put(h, ow, p->edge_inv_sigma2, 8 * (size_t)NE); }
-    B_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
     const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
     auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
-    B_TRY(hipEventRecord(w->e0, s));
+    ORB_TRY(hipEventRecord(w->e0, s));
     int max_n = 0;
     for (int f = 0; f < B; ++f) max_n = std::max(max_n, p->edge_off[f + 1] - p->edge_off[f]);
     const int cap = std::min(pose_lds_cap(), max_n); // (no more LDS than the largest frame needs: more workgroups per CU for a big batch)
-    B_TRY(pose_lds_configure(cap));
+    ORB_TRY(pose_lds_configure(cap));
     hipLaunchKernelGGL(k_pose_optimize, dim3(B), dim3(256), pose_lds_bytes(cap), s, cam, p->rounds > 0 ? p->rounds : 4,
                        p->iterations > 0 ? p->iterations : 10, cap, reinterpret_cast<int *>(d + ooff), D(oR0), D(ot0), D(oP), D(oz), D(ow),
                        D(oR), D(ot), d + oin, reinterpret_cast<int *>(d + oni), D(ochi));
-    B_TRY(hipEventRecord(w->e1, s));
-    B_TRY(hipGetLastError());
-    B_TRY(hipMemcpyAsync(h, d + in_bytes, out_end - in_bytes, hipMemcpyDeviceToHost, s));
-    B_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipEventRecord(w->e1, s));
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(h, d + in_bytes, out_end - in_bytes, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     float ms = 0;
-    B_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
+    ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
     r->kernel_ms = ms;
     auto O = [&](size_t off) { return h + (off - in_bytes); }; // a result's place in the staging block
     memcpy(r->pose_R, O(oR), 72 * (size_t)B);
@@ -1395,7 +1340,7 @@ extern "C" int orbba_pose_edges_device(int n2, int nq, const int32_t *d_frame_mp
         return orbx_set_error(ORBX_E_ARG, "bad argument");
     hipLaunchKernelGGL(k_pose_edges, dim3(1), dim3(1024), 0, (hipStream_t)stream, n2, nq, d_frame_mp, (const orbx_kp *)d_kps,
                        d_q_points, d_edge_off, d_points, d_edge_z, d_edge_inv_sigma2, d_edge_kp);
-    B_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 extern "C" int orbba_pose_optimize_batch_device(const orbba_pose_problem *p, orbba_pose_result *r, void *stream)
@@ -1406,11 +1351,11 @@ extern "C" int orbba_pose_optimize_batch_device(const orbba_pose_problem *p, orb
         return orbx_set_error(ORBX_E_ARG, "null array (every pointer is device memory here, chi2 included)");
     const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
     const int cap = pose_lds_cap(); // (the edge counts are on the device: the full capacity, one workgroup per CU)
-    B_TRY(pose_lds_configure(cap));
+    ORB_TRY(pose_lds_configure(cap));
     hipLaunchKernelGGL(k_pose_optimize, dim3(p->n_frames), dim3(256), pose_lds_bytes(cap), (hipStream_t)stream, cam, p->rounds > 0 ? p->rounds : 4,
                        p->iterations > 0 ? p->iterations : 10, cap, p->edge_off, p->pose_R, p->pose_t, p->points, p->edge_z,
                        p->edge_inv_sigma2, r->pose_R, r->pose_t, r->inlier, r->n_inliers, r->chi2);
-    B_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     r->kernel_ms = 0.f;
     return ORBX_OK;
 }

@@ -8,8 +8,7 @@
 
 #include "../../include/orbd.h"
 #include "../../include/orbx.h"
-
-int orbx_set_error(int code, const std::string &msg);
+#include "orb_host.h"
 
 namespace {
 // the few RCCL entry points used, with the signatures of /opt/rocm/include/rccl/rccl.h
@@ -52,13 +51,6 @@ struct Rccl {
 };
 Rccl g_rccl;
 
-int need_device()
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    return ORBX_OK;
-}
 int rccl_fail(const char *what, int rc)
 {
     return orbx_set_error(ORBX_E_NO_DEVICE, std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error"));
@@ -71,12 +63,11 @@ struct orbd_comm {
 };
 
 #define D_NCCL(call, what) do { int rc_ = (call); if (rc_ != 0) return rccl_fail(what, rc_); } while (0)
-#define D_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return orbx_set_error(ORBX_E_NO_DEVICE, hipGetErrorString(e_)); } while (0)
 
 extern "C" int orbd_unique_id(uint8_t id[ORBD_ID_BYTES])
 {
     if (!id) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (int rc = need_device()) return rc;
+    if (int rc = orb_need_device()) return rc;
     if (!g_rccl.load()) return orbx_set_error(ORBX_E_UNSUPPORTED, g_rccl.err);
     nccl_id u;
     D_NCCL(g_rccl.GetUniqueId(&u), "ncclGetUniqueId");
@@ -88,10 +79,9 @@ extern "C" int orbd_create(int rank, int world, const uint8_t id[ORBD_ID_BYTES],
 {
     if (!out || !id || world < 1 || rank < 0 || rank >= world) return orbx_set_error(ORBX_E_ARG, "bad argument");
     *out = nullptr;
-    if (int rc = need_device()) return rc;
+    if (int rc = orb_need_device(&device)) return rc;
     if (!g_rccl.load()) return orbx_set_error(ORBX_E_UNSUPPORTED, g_rccl.err);
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-    D_HIP(hipSetDevice(device));
+    ORB_TRY(hipSetDevice(device));
     nccl_id u;
     memcpy(u.internal, id, ORBD_ID_BYTES);
     nccl_comm comm = nullptr;
@@ -151,14 +141,14 @@ extern "C" int orbd_gather_records(orbd_t *c, int root, int n_frames, int cap, c
         return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (c->rank == root && (!d_n_all || !d_kp_all || !d_desc_all)) return orbx_set_error(ORBX_E_ARG, "the root needs the receive buffers");
     if (n_frames == 0) return ORBX_OK;
-    D_HIP(hipSetDevice(c->device));
+    ORB_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t bn = (size_t)n_frames * sizeof(int32_t), bk = (size_t)n_frames * cap * sizeof(orbx_kp), bd = (size_t)n_frames * cap * 32;
     if (c->rank == root) {
         // the root's own block is a device copy; every peer's three arrays arrive over that peer's link
-        D_HIP(hipMemcpyAsync((uint8_t *)d_n_all + (size_t)root * bn, d_n, bn, hipMemcpyDeviceToDevice, s));
-        if (bk) D_HIP(hipMemcpyAsync((uint8_t *)d_kp_all + (size_t)root * bk, d_kp, bk, hipMemcpyDeviceToDevice, s));
-        if (bd) D_HIP(hipMemcpyAsync(d_desc_all + (size_t)root * bd, d_desc, bd, hipMemcpyDeviceToDevice, s));
+        ORB_TRY(hipMemcpyAsync((uint8_t *)d_n_all + (size_t)root * bn, d_n, bn, hipMemcpyDeviceToDevice, s));
+        if (bk) ORB_TRY(hipMemcpyAsync((uint8_t *)d_kp_all + (size_t)root * bk, d_kp, bk, hipMemcpyDeviceToDevice, s));
+        if (bd) ORB_TRY(hipMemcpyAsync(d_desc_all + (size_t)root * bd, d_desc, bd, hipMemcpyDeviceToDevice, s));
         if (c->world > 1) {
             // inside a group every call is made even after a failure and the group is always closed: an early return
             // between ncclGroupStart and ncclGroupEnd would leave the communicator with an open group
@@ -193,7 +183,7 @@ extern "C" int orbd_allgather_records(orbd_t *c, int n_frames, int cap, const in
     if (!c || !d_n || !d_kp || !d_desc || !d_n_all || !d_kp_all || !d_desc_all || n_frames < 0 || cap < 0)
         return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (n_frames == 0) return ORBX_OK;
-    D_HIP(hipSetDevice(c->device));
+    ORB_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t bn = (size_t)n_frames * sizeof(int32_t), bk = (size_t)n_frames * cap * sizeof(orbx_kp), bd = (size_t)n_frames * cap * 32;
     D_NCCL(g_rccl.GroupStart(), "ncclGroupStart");

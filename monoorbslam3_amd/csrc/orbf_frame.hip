@@ -10,15 +10,8 @@
 #include <vector>
 
 #include "../../include/orbf.h"
+#include "orb_host.h"
 #include "orb_math.h"
-
-int orbx_set_error(int code, const std::string &msg);
-
-#define F_TRY(expr)                                                                                              \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return orbx_set_error(ORBX_E_NO_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
 
 struct OrbfCam {
     int width, height, cols, rows;
@@ -29,17 +22,11 @@ struct OrbfCam {
 };
 
 struct orbf_ctx {
-    int device = 0;
+    HandleStream hs;
     OrbfCam cam{};
     float *d_scale = nullptr;
-    hipStream_t stream = nullptr;
-    bool null_pending = false; // a device call was enqueued on stream 0 (NULL): the next host-pointer call and destroy wait for it
-    int32_t *d_cell_of = nullptr, *d_tmp = nullptr;
-    size_t scratch_items = 0;
-    // host-convenience staging
-    orbx_kp *d_raw = nullptr, *d_un = nullptr;
-    int32_t *d_start = nullptr, *d_items = nullptr, *d_n = nullptr;
-    size_t stage_cap = 0;
+    DevBuf cell_of, tmp;                 // scratch of the grid kernel
+    DevBuf raw, un, start, items, n;     // host-convenience staging
 };
 
 // cv::undistortPoints(src, dst, K, dist, noArray(), K) for one point: OpenCV 4.2 cvUndistortPointsInternal with
@@ -170,13 +157,10 @@ extern "C" int orbf_create(const orbf_camera *cam, int device, orbf_t **out)
     if (cam->width <= 0 || cam->height <= 0 || cam->n_dist < 0 || cam->n_dist > ORBF_MAX_DIST)
         return orbx_set_error(ORBX_E_ARG, "bad camera: size must be positive and n_dist in 0..12");
     if (cam->fx == 0.f || cam->fy == 0.f) return orbx_set_error(ORBX_E_ARG, "bad camera: zero focal length");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return orbx_set_error(ORBX_E_ARG, "device index out of range");
-    F_TRY(hipSetDevice(device));
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
     orbf_ctx *c = new orbf_ctx();
-    c->device = device;
+    c->hs.device = device;
     OrbfCam &k = c->cam;
     k.width = cam->width;
     k.height = cam->height;
@@ -191,7 +175,7 @@ extern "C" int orbf_create(const orbf_camera *cam, int device, orbf_t **out)
         delete c;
         return orbx_set_error(ORBX_E_ARG, "image too large for the grid kernel (more than 7679 cells)");
     }
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking); // host-pointer calls only (include/orbx.h, "Streams")
+    hipError_t e = c->hs.create();
     if (e == hipSuccess && cam->size_scale) {
         const size_t bytes = (size_t)cam->width * cam->height * 4;
         e = hipMalloc(&c->d_scale, bytes);
@@ -209,13 +193,9 @@ extern "C" int orbf_create(const orbf_camera *cam, int device, orbf_t **out)
 extern "C" void orbf_destroy(orbf_t *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->null_pending) (void)hipStreamSynchronize((hipStream_t)0);
-    for (void *p : {(void *)c->d_scale, (void *)c->d_cell_of, (void *)c->d_tmp, (void *)c->d_raw, (void *)c->d_un,
-                    (void *)c->d_start, (void *)c->d_items, (void *)c->d_n})
-        if (p) (void)hipFree(p);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    c->hs.destroy();
+    if (c->d_scale) (void)hipFree(c->d_scale);
+    for (DevBuf *b : {&c->cell_of, &c->tmp, &c->raw, &c->un, &c->start, &c->items, &c->n}) b->release();
     delete c;
 }
 
@@ -234,25 +214,17 @@ extern "C" int orbf_frame_post_device(orbf_t *c, int n_frames, orbx_kp *d_kp_raw
         return orbx_set_error(ORBX_E_ARG, "null argument");
     if (n_frames < 0 || cap <= 0) return orbx_set_error(ORBX_E_ARG, "n_frames must be >= 0 and cap positive");
     if (n_frames == 0) return ORBX_OK;
-    F_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
-    const size_t need = (size_t)n_frames * cap;
-    if (need > c->scratch_items) { // scratch grows geometrically; nothing may be in flight on the old one
-        F_TRY(hipDeviceSynchronize());
-        if (c->d_cell_of) (void)hipFree(c->d_cell_of);
-        if (c->d_tmp) (void)hipFree(c->d_tmp);
-        c->d_cell_of = c->d_tmp = nullptr;
-        c->scratch_items = 0;
-        const size_t grow = need + need / 2;
-        F_TRY(hipMalloc(&c->d_cell_of, grow * 4));
-        F_TRY(hipMalloc(&c->d_tmp, grow * 4));
-        c->scratch_items = grow;
-    }
+    ORB_TRY(c->hs.device_call(s));
+    const size_t items = (size_t)n_frames * cap, grow = items + items / 2;
+    // scratch grows geometrically; nothing may be in flight on the old one
+    if (items * 4 > c->cell_of.cap || items * 4 > c->tmp.cap) ORB_TRY(hipDeviceSynchronize());
+    ORB_TRY(c->cell_of.need(items * 4, grow * 4));
+    ORB_TRY(c->tmp.need(items * 4, grow * 4));
     const int nc = c->cam.cols * c->cam.rows;
     hipLaunchKernelGGL(k_frame_post, dim3(n_frames), dim3(256), (size_t)(2 * nc + 1) * 4, s, c->cam, d_kp_raw, d_n, cap,
-                       d_kp_un, d_cell_start, d_cell_items, c->d_cell_of, c->d_tmp);
-    F_TRY(hipGetLastError());
+                       d_kp_un, d_cell_start, d_cell_items, c->cell_of.as<int32_t>(), c->tmp.as<int32_t>());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -261,33 +233,28 @@ extern "C" int orbf_frame_post(orbf_t *c, orbx_kp *kp_raw, int n, orbx_kp *kp_un
 {
     if (!c || !kp_raw || !kp_un || !cell_start || !cell_items) return orbx_set_error(ORBX_E_ARG, "null argument");
     if (n < 0) return orbx_set_error(ORBX_E_ARG, "negative key-point count");
-    F_TRY(hipSetDevice(c->device));
     // the handle's stream is non-blocking: NULL-stream device calls of this handle still in flight use the same scratch
-    if (c->null_pending) { F_TRY(hipStreamSynchronize((hipStream_t)0)); c->null_pending = false; }
+    ORB_TRY(c->hs.host_call());
     const int nc = c->cam.cols * c->cam.rows, cap = n > 0 ? n : 1;
-    if ((size_t)cap > c->stage_cap) {
-        F_TRY(hipStreamSynchronize(c->stream));
-        for (void **p : {(void **)&c->d_raw, (void **)&c->d_un, (void **)&c->d_start, (void **)&c->d_items, (void **)&c->d_n})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        c->stage_cap = 0;
-        const size_t grow = (size_t)cap + cap / 2 + 64;
-        F_TRY(hipMalloc(&c->d_raw, grow * sizeof(orbx_kp)));
-        F_TRY(hipMalloc(&c->d_un, grow * sizeof(orbx_kp)));
-        F_TRY(hipMalloc(&c->d_items, grow * 4));
-        F_TRY(hipMalloc(&c->d_start, (size_t)(nc + 1) * 4));
-        F_TRY(hipMalloc(&c->d_n, 4));
-        c->stage_cap = grow;
-    }
-    hipStream_t s = c->stream;
+    hipStream_t s = c->hs.stream;
+    const size_t grow = (size_t)cap + cap / 2 + 64, kp = sizeof(orbx_kp);
+    if (cap * kp > c->raw.cap || cap * kp > c->un.cap || (size_t)cap * 4 > c->items.cap) ORB_TRY(hipStreamSynchronize(s));
+    ORB_TRY(c->raw.need(cap * kp, grow * kp));
+    ORB_TRY(c->un.need(cap * kp, grow * kp));
+    ORB_TRY(c->items.need((size_t)cap * 4, grow * 4));
+    ORB_TRY(c->start.need((size_t)(nc + 1) * 4, (size_t)(nc + 1) * 4));
+    ORB_TRY(c->n.need(4, 4));
+    orbx_kp *d_raw = c->raw.as<orbx_kp>(), *d_un = c->un.as<orbx_kp>();
+    int32_t *d_start = c->start.as<int32_t>(), *d_items = c->items.as<int32_t>(), *d_n = c->n.as<int32_t>();
     const int32_t n32 = n;
-    F_TRY(hipMemcpyAsync(c->d_raw, kp_raw, (size_t)n * sizeof(orbx_kp), hipMemcpyHostToDevice, s));
-    F_TRY(hipMemcpyAsync(c->d_n, &n32, 4, hipMemcpyHostToDevice, s));
-    int rc = orbf_frame_post_device(c, 1, c->d_raw, c->d_n, cap, c->d_un, c->d_start, c->d_items, s);
+    ORB_TRY(hipMemcpyAsync(d_raw, kp_raw, (size_t)n * sizeof(orbx_kp), hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(d_n, &n32, 4, hipMemcpyHostToDevice, s));
+    int rc = orbf_frame_post_device(c, 1, d_raw, d_n, cap, d_un, d_start, d_items, s);
     if (rc) return rc;
-    F_TRY(hipMemcpyAsync(kp_raw, c->d_raw, (size_t)n * sizeof(orbx_kp), hipMemcpyDeviceToHost, s));
-    F_TRY(hipMemcpyAsync(kp_un, c->d_un, (size_t)n * sizeof(orbx_kp), hipMemcpyDeviceToHost, s));
-    F_TRY(hipMemcpyAsync(cell_start, c->d_start, (size_t)(nc + 1) * 4, hipMemcpyDeviceToHost, s));
-    F_TRY(hipMemcpyAsync(cell_items, c->d_items, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    F_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipMemcpyAsync(kp_raw, d_raw, (size_t)n * sizeof(orbx_kp), hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(kp_un, d_un, (size_t)n * sizeof(orbx_kp), hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(cell_start, d_start, (size_t)(nc + 1) * 4, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(cell_items, d_items, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     return ORBX_OK;
 }

@@ -15,25 +15,17 @@
 
 #include <algorithm>
 #include <string>
-#include <chrono>
 #include <vector>
 
 #include "../../include/orbm.h"
 #include "../../include/orbx.h"
+#include "orb_host.h"
 #include "orb_math.h"
 
 typedef unsigned long long u64;
 
 extern "C" const char *orbx_last_error(void);
-// error text is shared with the extractor (orbx_api.hip owns the thread-local string)
-int orbx_set_error(int code, const std::string &msg);
 hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes); // orbx_api.hip: dynamic LDS above 64 KB, per kernel and per device
-#define M_TRY(expr)                                                                                    \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess)                                                                          \
-            return orbx_set_error(ORBX_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // kernels
@@ -817,39 +809,10 @@ __global__ __launch_bounds__(256) void k_window_lists(const orbx_kp *__restrict_
 // ---------------------------------------------------------------------------------------------
 // handle
 // ---------------------------------------------------------------------------------------------
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        const size_t old_cap = cap;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = std::max(std::max(bytes, (size_t)4096), 2 * old_cap); // geometric growth: hipFree is costly
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-
-// pinned host staging: one copy in, one copy out per call of a window search
-struct PinBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 16);
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
+// growth of the handle's scratch: geometric for the device blocks (hipFree is costly), by half for the pinned host staging
+// (one copy in, one copy out per call of a window search)
+static hipError_t need(DevBuf &b, size_t bytes) { return b.need(bytes, std::max(std::max(bytes, (size_t)4096), 2 * b.cap)); }
+static hipError_t need(PinBuf &b, size_t bytes) { return b.need(bytes, std::max(bytes + bytes / 2, (size_t)1 << 16)); }
 
 // ---------------------------------------------------------------------------------------------
 // The greedy pass of SearchByProjection on the device (ORBMatcher.cpp:229-246 frame -> frame, :379-407 map points ->
@@ -1444,9 +1407,7 @@ __global__ __launch_bounds__(256) void k_bow_finish(int check_orientation, const
 }
 
 struct orbm_ctx {
-    int device;
-    hipStream_t stream;
-    bool null_pending = false; // a device call was enqueued on stream 0 (NULL): the next host-pointer call and destroy wait for it
+    HandleStream hs;
     DevBuf a, b, out, q_idx, c_begin, c_len, out_begin, c_idx, row_ok, col_ok, bidx, bbest, bsecond;
     DevBuf w_in, w_out, w_grid; // window searches: staged inputs, lists, CSR grid + scratch
     PinBuf h_in, h_out;
@@ -1459,28 +1420,14 @@ struct orbm_ctx {
     size_t window_last_total = 0; // candidates the previous window search returned (sizes the first copy-out)
 };
 
-// A host-pointer entry point starts here: the handle's device and -- the handle's stream being NON-BLOCKING, so that a second
-// thread's handle or a legacy-stream operation anywhere in the process never orders against it (include/orbx.h, "Streams") -- a
-// wait for NULL-stream device calls of THIS handle that may still be using its scratch.
-static hipError_t host_call_begin(orbm_ctx *c)
-{
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess && c->null_pending) { e = hipStreamSynchronize((hipStream_t)0); c->null_pending = false; }
-    return e;
-}
-
 extern "C" int orbm_create(int device, orbm_t **out)
 {
     if (!out) return orbx_set_error(ORBX_E_ARG, "null argument");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= ndev) return orbx_set_error(ORBX_E_ARG, "device ordinal out of range");
+    if (int rc = orb_need_device(&device)) return rc;
     orbm_ctx *c = new orbm_ctx();
-    c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { // host-pointer calls only (include/orbx.h, "Streams")
+    c->hs.device = device;
+    if (hipSetDevice(device) != hipSuccess || c->hs.create() != hipSuccess) {
         delete c;
         return orbx_set_error(ORBX_E_NO_DEVICE, "stream creation failed");
     }
@@ -1503,14 +1450,11 @@ extern "C" int orbm_set_variant(orbm_t *c, int which, int value)
 extern "C" void orbm_destroy(orbm_t *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->null_pending) (void)hipStreamSynchronize((hipStream_t)0);
+    c->hs.destroy();
     DevBuf *bufs[] = {&c->a, &c->b, &c->out, &c->q_idx, &c->c_begin, &c->c_len, &c->out_begin, &c->c_idx,
                       &c->row_ok, &c->col_ok, &c->bidx, &c->bbest, &c->bsecond, &c->w_in, &c->w_out, &c->w_grid};
     for (DevBuf *d : bufs) d->release();
     c->h_in.release(); c->h_out.release();
-    (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -1520,10 +1464,10 @@ extern "C" int orbm_hamming_matrix_device(orbm_t *c, const uint8_t *d_a, int na,
     if (!c || !d_a || !d_b || !d_out || na < 0 || nb < 0) return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (na == 0 || nb == 0) return ORBX_OK;
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call(s));
     dim3 grid((nb + 63) / 64, (na + 63) / 64);
     hipLaunchKernelGGL(k_hamming_matrix, grid, dim3(256), 0, s, d_a, na, d_b, nb, d_out);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -1531,17 +1475,17 @@ extern "C" int orbm_hamming_matrix(orbm_t *c, const uint8_t *a, int na, const ui
 {
     if (!c || !a || !b || !out || na < 0 || nb < 0) return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (na == 0 || nb == 0) return ORBX_OK;
-    M_TRY(host_call_begin(c));
-    M_TRY(c->a.need((size_t)na * 32));
-    M_TRY(c->b.need((size_t)nb * 32));
-    M_TRY(c->out.need((size_t)na * nb * 2));
-    M_TRY(hipMemcpyAsync(c->a.p, a, (size_t)na * 32, hipMemcpyHostToDevice, c->stream));
-    M_TRY(hipMemcpyAsync(c->b.p, b, (size_t)nb * 32, hipMemcpyHostToDevice, c->stream));
+    ORB_TRY(c->hs.host_call());
+    ORB_TRY(need(c->a, (size_t)na * 32));
+    ORB_TRY(need(c->b, (size_t)nb * 32));
+    ORB_TRY(need(c->out, (size_t)na * nb * 2));
+    ORB_TRY(hipMemcpyAsync(c->a.p, a, (size_t)na * 32, hipMemcpyHostToDevice, c->hs.stream));
+    ORB_TRY(hipMemcpyAsync(c->b.p, b, (size_t)nb * 32, hipMemcpyHostToDevice, c->hs.stream));
     int rc = orbm_hamming_matrix_device(c, (const uint8_t *)c->a.p, na, (const uint8_t *)c->b.p, nb, (uint16_t *)c->out.p,
-                                        c->stream);
+                                        c->hs.stream);
     if (rc) return rc;
-    M_TRY(hipMemcpyAsync(out, c->out.p, (size_t)na * nb * 2, hipMemcpyDeviceToHost, c->stream));
-    M_TRY(hipStreamSynchronize(c->stream));
+    ORB_TRY(hipMemcpyAsync(out, c->out.p, (size_t)na * nb * 2, hipMemcpyDeviceToHost, c->hs.stream));
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
     return ORBX_OK;
 }
 
@@ -1555,7 +1499,7 @@ extern "C" int orbm_best2_device(orbm_t *c, int n_pairs, const uint8_t *d_a, siz
     if (nb_max >= (1 << 23)) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 2^23 candidates per problem");
     if (na_max == 0) return ORBX_OK;
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call(s));
     // the matrix-pipe kernel takes every problem without a candidate mask and at most BM_MAX_CAND (8160) candidates --
     // 16 * tile + register must stay below the 4096 free low bits of its keys; anything else runs k_best2;
     // ORBM_VAR_BEST2 = 2 keeps everything on the VALU kernel (the parity twin), 1 takes the i8 matrix kernel
@@ -1573,20 +1517,20 @@ extern "C" int orbm_best2_device(orbm_t *c, int n_pairs, const uint8_t *d_a, siz
         else
             hipLaunchKernelGGL(k_best2_fp4<false>, dim3(grid), dim3(BF_WAVES * 64), 0, s, d_a, a_stride, d_na, na_max, d_b, b_stride, d_nb,
                                nb_max, d_row_ok, d_best_idx, d_best, d_second, blocks_x, (int)n_blocks);
-        M_TRY(hipGetLastError());
+        ORB_TRY(hipGetLastError());
         return ORBX_OK;
     }
     if (use_mfma && !d_col_ok && nb_max <= BM_MAX_CAND) {
         dim3 grid((na_max + BM_WAVES * 32 - 1) / (BM_WAVES * 32), n_pairs);
         hipLaunchKernelGGL(k_best2_mfma, grid, dim3(BM_WAVES * 64), 0, s, d_a, a_stride, d_na, na_max, d_b, b_stride, d_nb,
                            nb_max, d_row_ok, d_best_idx, d_best, d_second);
-        M_TRY(hipGetLastError());
+        ORB_TRY(hipGetLastError());
         return ORBX_OK;
     }
     dim3 grid((na_max + 4 * B2_ROWS - 1) / (4 * B2_ROWS), n_pairs);
     hipLaunchKernelGGL(k_best2, grid, dim3(256), 0, s, d_a, a_stride, d_na, na_max, d_b, b_stride, d_nb, nb_max,
                        d_row_ok, d_col_ok, d_best_idx, d_best, d_second);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -1596,42 +1540,31 @@ extern "C" int orbm_best2(orbm_t *c, const uint8_t *a, int na, const uint8_t *b,
     if (!c || !a || !best_idx || !best || !second || na < 0 || nb < 0 || (nb > 0 && !b))
         return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (na == 0) return ORBX_OK;
-    M_TRY(host_call_begin(c));
-    hipStream_t s = c->stream;
-    M_TRY(c->a.need((size_t)na * 32));
-    M_TRY(c->b.need((size_t)std::max(nb, 1) * 32));
-    M_TRY(c->bidx.need((size_t)na * 4));
-    M_TRY(c->bbest.need((size_t)na * 2));
-    M_TRY(c->bsecond.need((size_t)na * 2));
-    M_TRY(hipMemcpyAsync(c->a.p, a, (size_t)na * 32, hipMemcpyHostToDevice, s));
-    if (nb) M_TRY(hipMemcpyAsync(c->b.p, b, (size_t)nb * 32, hipMemcpyHostToDevice, s));
+    ORB_TRY(c->hs.host_call());
+    hipStream_t s = c->hs.stream;
+    ORB_TRY(need(c->a, (size_t)na * 32));
+    ORB_TRY(need(c->b, (size_t)std::max(nb, 1) * 32));
+    ORB_TRY(need(c->bidx, (size_t)na * 4));
+    ORB_TRY(need(c->bbest, (size_t)na * 2));
+    ORB_TRY(need(c->bsecond, (size_t)na * 2));
+    ORB_TRY(hipMemcpyAsync(c->a.p, a, (size_t)na * 32, hipMemcpyHostToDevice, s));
+    if (nb) ORB_TRY(hipMemcpyAsync(c->b.p, b, (size_t)nb * 32, hipMemcpyHostToDevice, s));
     const uint8_t *d_row = nullptr, *d_col = nullptr;
-    if (row_ok) { M_TRY(c->row_ok.need(na)); M_TRY(hipMemcpyAsync(c->row_ok.p, row_ok, na, hipMemcpyHostToDevice, s)); d_row = (const uint8_t *)c->row_ok.p; }
-    if (col_ok && nb) { M_TRY(c->col_ok.need(nb)); M_TRY(hipMemcpyAsync(c->col_ok.p, col_ok, nb, hipMemcpyHostToDevice, s)); d_col = (const uint8_t *)c->col_ok.p; }
+    if (row_ok) { ORB_TRY(need(c->row_ok, na)); ORB_TRY(hipMemcpyAsync(c->row_ok.p, row_ok, na, hipMemcpyHostToDevice, s)); d_row = (const uint8_t *)c->row_ok.p; }
+    if (col_ok && nb) { ORB_TRY(need(c->col_ok, nb)); ORB_TRY(hipMemcpyAsync(c->col_ok.p, col_ok, nb, hipMemcpyHostToDevice, s)); d_col = (const uint8_t *)c->col_ok.p; }
     int rc = orbm_best2_device(c, 1, (const uint8_t *)c->a.p, na, nullptr, na, (const uint8_t *)c->b.p, std::max(nb, 1),
                                nullptr, nb, d_row, d_col, (int32_t *)c->bidx.p, (uint16_t *)c->bbest.p,
-                               (uint16_t *)c->bsecond.p, c->stream);
+                               (uint16_t *)c->bsecond.p, c->hs.stream);
     if (rc) return rc;
-    M_TRY(hipMemcpyAsync(best_idx, c->bidx.p, (size_t)na * 4, hipMemcpyDeviceToHost, s));
-    M_TRY(hipMemcpyAsync(best, c->bbest.p, (size_t)na * 2, hipMemcpyDeviceToHost, s));
-    M_TRY(hipMemcpyAsync(second, c->bsecond.p, (size_t)na * 2, hipMemcpyDeviceToHost, s));
-    M_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipMemcpyAsync(best_idx, c->bidx.p, (size_t)na * 4, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(best, c->bbest.p, (size_t)na * 2, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(second, c->bsecond.p, (size_t)na * 2, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     return ORBX_OK;
 }
 
 // distances for per-query candidate lists; the lists may alias each other (queries of one BoW
 // node share the node's candidate list), outputs are disjoint
-struct PhaseTrace { // ORBM_TRACE=1: host time stamps of the phases of a window search on stderr
-    bool on; std::chrono::steady_clock::time_point t0;
-    PhaseTrace() : on(getenv("ORBM_TRACE") != nullptr), t0(std::chrono::steady_clock::now()) {}
-    void mark(const char *what) {
-        if (!on) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[orbm] %-24s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - t0).count());
-        t0 = t;
-    }
-};
-
 static int hamming_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b, int nb,
                          const std::vector<int32_t> &q_idx, const std::vector<int32_t> &c_begin,
                          const std::vector<int32_t> &c_len, const std::vector<int32_t> &out_begin,
@@ -1640,17 +1573,17 @@ static int hamming_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b
     out.resize(n_out);
     const int nq = (int)q_idx.size();
     if (nq == 0 || n_out == 0) return ORBX_OK;
-    M_TRY(host_call_begin(c));
-    hipStream_t s = c->stream;
+    ORB_TRY(c->hs.host_call());
+    hipStream_t s = c->hs.stream;
     // one page-locked block up, one down (as topk_lists below): [a][b][q_idx][c_begin][c_len][out_begin][c_idx]
     auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
     const size_t o_a = 0, o_b = al(o_a + (size_t)na * 32), o_q = al(o_b + (size_t)nb * 32), o_cb = al(o_q + (size_t)nq * 4),
                  o_cl = al(o_cb + (size_t)nq * 4), o_ob = al(o_cl + (size_t)nq * 4), o_ci = al(o_ob + (size_t)nq * 4),
                  in_bytes = al(o_ci + n_cidx * 4);
-    M_TRY(c->h_in.need(in_bytes));
-    M_TRY(c->w_in.need(in_bytes));
-    M_TRY(c->h_out.need(n_out * 2));
-    M_TRY(c->out.need(n_out * 2));
+    ORB_TRY(need(c->h_in, in_bytes));
+    ORB_TRY(need(c->w_in, in_bytes));
+    ORB_TRY(need(c->h_out, n_out * 2));
+    ORB_TRY(need(c->out, n_out * 2));
     uint8_t *hp = (uint8_t *)c->h_in.p;
     memcpy(hp + o_a, a, (size_t)na * 32);
     memcpy(hp + o_b, b, (size_t)nb * 32);
@@ -1659,14 +1592,14 @@ static int hamming_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b
     memcpy(hp + o_cl, c_len.data(), (size_t)nq * 4);
     memcpy(hp + o_ob, out_begin.data(), (size_t)nq * 4);
     memcpy(hp + o_ci, c_idx, n_cidx * 4);
-    M_TRY(hipMemcpyAsync(c->w_in.p, hp, in_bytes, hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(c->w_in.p, hp, in_bytes, hipMemcpyHostToDevice, s));
     const uint8_t *dp = (const uint8_t *)c->w_in.p;
     hipLaunchKernelGGL(k_hamming_lists, dim3((nq + 3) / 4), dim3(256), 0, s, dp + o_a, dp + o_b, (const int32_t *)(dp + o_q),
                        (const int32_t *)(dp + o_cb), (const int32_t *)(dp + o_cl), (const int32_t *)(dp + o_ob), nq, (const int32_t *)(dp + o_ci),
                        (uint16_t *)c->out.p);
-    M_TRY(hipGetLastError());
-    M_TRY(hipMemcpyAsync(c->h_out.p, c->out.p, n_out * 2, hipMemcpyDeviceToHost, s));
-    M_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(c->h_out.p, c->out.p, n_out * 2, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     memcpy(out.data(), c->h_out.p, n_out * 2);
     return ORBX_OK;
 }
@@ -1683,8 +1616,8 @@ static int topk_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b, i
     *k_out = TOPK;
     out.assign((size_t)nq * TOPK, 0xFFFFFFFFu);
     if (nq == 0 || n_cidx == 0) return ORBX_OK;
-    M_TRY(host_call_begin(c));
-    hipStream_t s = c->stream;
+    ORB_TRY(c->hs.host_call());
+    hipStream_t s = c->hs.stream;
     // One page-locked block up, one down (round 6; seven copies from pageable memory and one to it before: every one of those is
     // staged by the runtime and holds the calling thread for 10-20 us).  Layout, 16-byte aligned:
     // [a][b][q_idx][c_begin][c_len][c_idx][cand_free]
@@ -1693,10 +1626,10 @@ static int topk_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b, i
                  o_cl = al(o_cb + (size_t)nq * 4), o_ci = al(o_cl + (size_t)nq * 4), o_fr = al(o_ci + n_cidx * 4),
                  in_bytes = al(o_fr + (cand_free ? (size_t)nb : 0));
     const size_t out_bytes = (size_t)nq * TOPK * 4;
-    M_TRY(c->h_in.need(in_bytes));
-    M_TRY(c->w_in.need(in_bytes));
-    M_TRY(c->h_out.need(out_bytes));
-    M_TRY(c->out.need(out_bytes));
+    ORB_TRY(need(c->h_in, in_bytes));
+    ORB_TRY(need(c->w_in, in_bytes));
+    ORB_TRY(need(c->h_out, out_bytes));
+    ORB_TRY(need(c->out, out_bytes));
     uint8_t *hp = (uint8_t *)c->h_in.p;
     memcpy(hp + o_a, a, (size_t)na * 32);
     memcpy(hp + o_b, b, (size_t)nb * 32);
@@ -1705,7 +1638,7 @@ static int topk_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b, i
     memcpy(hp + o_cl, c_len.data(), (size_t)nq * 4);
     memcpy(hp + o_ci, c_idx, n_cidx * 4);
     if (cand_free) memcpy(hp + o_fr, cand_free, (size_t)nb);
-    M_TRY(hipMemcpyAsync(c->w_in.p, hp, in_bytes, hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(c->w_in.p, hp, in_bytes, hipMemcpyHostToDevice, s));
     const uint8_t *dp = (const uint8_t *)c->w_in.p;
     const uint8_t *d_free = cand_free ? dp + o_fr : nullptr;
     if (TOPK == 16)
@@ -1716,9 +1649,9 @@ static int topk_lists(orbm_ctx *c, const uint8_t *a, int na, const uint8_t *b, i
         hipLaunchKernelGGL(k_topk_lists<8>, dim3((nq + 3) / 4), dim3(256), 0, s, dp + o_a, dp + o_b, (const int32_t *)(dp + o_q),
                            (const int32_t *)(dp + o_cb), (const int32_t *)(dp + o_cl), nq, (const int32_t *)(dp + o_ci), d_free,
                            (uint32_t *)c->out.p);
-    M_TRY(hipGetLastError());
-    M_TRY(hipMemcpyAsync(c->h_out.p, c->out.p, out_bytes, hipMemcpyDeviceToHost, s));
-    M_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(c->h_out.p, c->out.p, out_bytes, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     memcpy(out.data(), c->h_out.p, out_bytes);
     return ORBX_OK;
 }
@@ -1761,11 +1694,10 @@ extern "C" int orbm_distinctive_descriptors_device(orbm_t *c, const uint8_t *d_d
     if (!c || !d_desc || !d_off || !d_best_idx) return orbx_set_error(ORBX_E_ARG, "null argument");
     if (n_groups < 0) return orbx_set_error(ORBX_E_ARG, "negative group count");
     if (n_groups == 0) return ORBX_OK;
-    M_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call(s));
     hipLaunchKernelGGL(k_medoid, dim3(n_groups), dim3(64), 0, s, d_desc, d_off, n_groups, d_best_idx);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -1782,18 +1714,18 @@ extern "C" int orbm_distinctive_descriptors(orbm_t *c, const uint8_t *desc, cons
             return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 1024 observations of one map point");
     }
     if (total > 0 && !desc) return orbx_set_error(ORBX_E_ARG, "null descriptors");
-    M_TRY(host_call_begin(c));
-    hipStream_t s = c->stream;
-    M_TRY(c->a.need((size_t)std::max(total, 1) * 32));
-    M_TRY(c->c_begin.need((size_t)(n_groups + 1) * 4));
-    M_TRY(c->bidx.need((size_t)n_groups * 4));
-    if (total > 0) M_TRY(hipMemcpyAsync(c->a.p, desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
-    M_TRY(hipMemcpyAsync(c->c_begin.p, off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, s));
+    ORB_TRY(c->hs.host_call());
+    hipStream_t s = c->hs.stream;
+    ORB_TRY(need(c->a, (size_t)std::max(total, 1) * 32));
+    ORB_TRY(need(c->c_begin, (size_t)(n_groups + 1) * 4));
+    ORB_TRY(need(c->bidx, (size_t)n_groups * 4));
+    if (total > 0) ORB_TRY(hipMemcpyAsync(c->a.p, desc, (size_t)total * 32, hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(c->c_begin.p, off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, s));
     int rc = orbm_distinctive_descriptors_device(c, (const uint8_t *)c->a.p, (const int32_t *)c->c_begin.p, n_groups,
                                                  (int32_t *)c->bidx.p, s);
     if (rc) return rc;
-    M_TRY(hipMemcpyAsync(best_idx, c->bidx.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, s));
-    M_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipMemcpyAsync(best_idx, c->bidx.p, (size_t)n_groups * 4, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     return ORBX_OK;
 }
 
@@ -1877,7 +1809,7 @@ extern "C" int orbm_search_by_bow(orbm_t *c, float nn_ratio, int check_orientati
         return orbx_set_error(ORBX_E_ARG, "null argument");
     *n_matches = 0;
     if (n1 <= 0 || n2 <= 0) return ORBX_OK;
-    PhaseTrace tr;
+    PhaseTrace tr("orbm", "ORBM_TRACE");
     std::vector<NodePair> nodes;
     shared_nodes(fv1, fv2, nodes);
     NodeQueries q;
@@ -2116,8 +2048,8 @@ static int window_candidates(orbm_ctx *c, bool strict, const float *sigma2, int 
     const int nc = cols * rows;
     bool on_device = c->window_on_device && nc > 0 && (size_t)(2 * nc + 1) * 4 <= 60000 && n2 < (1 << 22);
     if (on_device) {
-        M_TRY(host_call_begin(c));
-        hipStream_t s = c->stream;
+        ORB_TRY(c->hs.host_call());
+        hipStream_t s = c->hs.stream;
         auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
         size_t o = 0;
         const size_t o_kps = o; o = al(o + (size_t)n2 * sizeof(orbx_kp));
@@ -2129,9 +2061,9 @@ static int window_candidates(orbm_ctx *c, bool strict, const float *sigma2, int 
         const size_t o_max = o; o = al(o + (size_t)nq * 4);
         const size_t o_ok = o; o = al(o + (size_t)nq);
         const size_t o_s2 = o; o = al(o + (size_t)std::max(n_sigma, 1) * 4);
-        PhaseTrace tr;
-        M_TRY(c->h_in.need(o));
-        M_TRY(c->w_in.need(o));
+        PhaseTrace tr("orbm", "ORBM_TRACE");
+        ORB_TRY(need(c->h_in, o));
+        ORB_TRY(need(c->w_in, o));
         uint8_t *hp = (uint8_t *)c->h_in.p;
         memcpy(hp + o_kps, kps2, (size_t)n2 * sizeof(orbx_kp));
         memcpy(hp + o_desc, desc2, (size_t)n2 * 32);
@@ -2143,17 +2075,17 @@ static int window_candidates(orbm_ctx *c, bool strict, const float *sigma2, int 
         memcpy(hp + o_ok, q_ok, (size_t)nq);
         if (sigma2) memcpy(hp + o_s2, sigma2, (size_t)n_sigma * 4);
         tr.mark("stage inputs");
-        M_TRY(hipMemcpyAsync(c->w_in.p, hp, o, hipMemcpyHostToDevice, s));
+        ORB_TRY(hipMemcpyAsync(c->w_in.p, hp, o, hipMemcpyHostToDevice, s));
         const uint8_t *dp = (const uint8_t *)c->w_in.p;
         const size_t g_bytes = ((size_t)nc + 1 + 3 * (size_t)n2) * 4;
-        M_TRY(c->w_grid.need(g_bytes));
+        ORB_TRY(need(c->w_grid, g_bytes));
         int32_t *cell_start = (int32_t *)c->w_grid.p, *cell_items = cell_start + nc + 1, *cell_of = cell_items + n2, *tmp = cell_of + n2;
         // device output: [total, pad x3][counts nq][offs nq][pool]; the lists are packed, `cap` entries per query on average
         const size_t pool_cap = (size_t)nq * cap, head = 16 + (size_t)nq * 8;
         // what one copy brings back (the rest only if needed): the previous call's total is the best guess for this one
         const size_t first = std::min(pool_cap, std::max((size_t)nq * 12 + 256, c->window_last_total + c->window_last_total / 8 + 64));
-        M_TRY(c->w_out.need(head + pool_cap * 4));
-        M_TRY(c->h_out.need(head + pool_cap * 4));
+        ORB_TRY(need(c->w_out, head + pool_cap * 4));
+        ORB_TRY(need(c->h_out, head + pool_cap * 4));
         int32_t *d_total = (int32_t *)c->w_out.p, *d_counts = d_total + 4, *d_offs = d_counts + nq;
         uint32_t *d_pool = (uint32_t *)(d_offs + nq);
         hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(GB_T), (size_t)(2 * nc + 1) * 4, s, (const orbx_kp *)(dp + o_kps), n2, img_w,
@@ -2163,10 +2095,10 @@ static int window_candidates(orbm_ctx *c, bool strict, const float *sigma2, int 
                            (const int32_t *)(dp + o_min), (const int32_t *)(dp + o_max), dp + o_ok, nq, strict ? 1 : 0,
                            sigma2 ? (const float *)(dp + o_s2) : nullptr, (int)std::min(pool_cap, (size_t)INT_MAX), d_counts,
                            d_pool, d_total, d_offs);
-        M_TRY(hipGetLastError());
-        M_TRY(hipMemcpyAsync(c->h_out.p, c->w_out.p, head + first * 4, hipMemcpyDeviceToHost, s));
+        ORB_TRY(hipGetLastError());
+        ORB_TRY(hipMemcpyAsync(c->h_out.p, c->w_out.p, head + first * 4, hipMemcpyDeviceToHost, s));
         tr.mark("enqueue");
-        M_TRY(hipStreamSynchronize(s));
+        ORB_TRY(hipStreamSynchronize(s));
         tr.mark("device + first copy");
         const int32_t *h_total = (const int32_t *)c->h_out.p, *counts = h_total + 4, *offs = counts + nq;
         const uint32_t *pool = (const uint32_t *)(offs + nq);
@@ -2174,9 +2106,9 @@ static int window_candidates(orbm_ctx *c, bool strict, const float *sigma2, int 
         c->window_last_total = total;
         if (total > pool_cap) on_device = false; // windows longer than the pool: redo on the host
         else if (total > first) {
-            M_TRY(hipMemcpyAsync((uint8_t *)c->h_out.p + head + first * 4, (uint8_t *)c->w_out.p + head + first * 4,
+            ORB_TRY(hipMemcpyAsync((uint8_t *)c->h_out.p + head + first * 4, (uint8_t *)c->w_out.p + head + first * 4,
                                  (total - first) * 4, hipMemcpyDeviceToHost, s));
-            M_TRY(hipStreamSynchronize(s));
+            ORB_TRY(hipStreamSynchronize(s));
         }
         tr.mark("second copy");
         if (on_device) {
@@ -2423,15 +2355,14 @@ static int projection_device(orbm_ctx *c, int mode, float nn_ratio, int check_or
     if (n2 >= (1 << 22)) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 2^22 key points");
     const size_t lds = ((size_t)n2 + (size_t)nq) * 4;
     if (lds > 150 * 1024) return orbx_set_error(ORBX_E_UNSUPPORTED, "nq + n2 above 38400: the greedy pass keeps both in LDS");
-    M_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call(s));
     // scratch: [total, pad x3][counts nq][offs nq][lo nq][hi nq][pool nq * list_cap]
     const size_t pool_cap = (size_t)nq * list_cap, head = 16 + (size_t)nq * 16;
-    M_TRY(c->w_out.need(head + pool_cap * 4 + 16));
+    ORB_TRY(need(c->w_out, head + pool_cap * 4 + 16));
     int32_t *d_total = (int32_t *)c->w_out.p, *d_counts = d_total + 4, *d_offs = d_counts + nq, *d_lo = d_offs + nq, *d_hi = d_lo + nq;
     uint32_t *d_pool = (uint32_t *)(d_hi + nq);
-    M_TRY(hipMemsetAsync(d_total, 0, 16, s));
+    ORB_TRY(hipMemsetAsync(d_total, 0, 16, s));
     if (nq > 0) {
         hipLaunchKernelGGL(k_projection_levels, dim3((nq + 255) / 256), dim3(256), 0, s, d_q_level, nq, mode == 0 ? 1 : 0, d_lo, d_hi);
         hipLaunchKernelGGL(k_window_lists, dim3((nq + 3) / 4), dim3(256), 0, s, (const orbx_kp *)d_kps2, d_desc2, d_cell_start,
@@ -2439,15 +2370,15 @@ static int projection_device(orbm_ctx *c, int mode, float nn_ratio, int check_or
                            (int)std::min(pool_cap, (size_t)INT_MAX), d_counts, d_pool, d_total, d_offs);
     }
     // once per device, thread-safe (the matcher entry points are re-entrant)
-    M_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_projection_resolve<0>), 150 * 1024));
-    M_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_projection_resolve<1>), 150 * 1024));
+    ORB_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_projection_resolve<0>), 150 * 1024));
+    ORB_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_projection_resolve<1>), 150 * 1024));
     if (mode == 0)
         hipLaunchKernelGGL(k_projection_resolve<0>, dim3(1), dim3(PR_T), lds, s, d_counts, d_offs, d_pool, (int)std::min(pool_cap, (size_t)INT_MAX),
                            d_total, nq, n2, (const orbx_kp *)d_kps2, d_q_angle, nn_ratio, check_orientation, d_frame_mp, d_result);
     else
         hipLaunchKernelGGL(k_projection_resolve<1>, dim3(1), dim3(PR_T), lds, s, d_counts, d_offs, d_pool, (int)std::min(pool_cap, (size_t)INT_MAX),
                            d_total, nq, n2, (const orbx_kp *)d_kps2, d_q_angle, nn_ratio, check_orientation, d_frame_mp, d_result);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 extern "C" int orbm_search_by_projection_frame_device(orbm_t *c, int check_orientation, const uint8_t *d_q_desc, const float *d_q_xy,
@@ -2511,14 +2442,13 @@ extern "C" int orbm_search_fuse_device(orbm_t *c, const uint8_t *d_q_desc, const
     if (!c || !d_q_desc || !d_q_xy || !d_q_radius || !d_q_level || !d_q_ok || !d_kps || !d_desc || !d_cell_start || !d_cell_items ||
         !d_sigma2 || !d_best_idx || !d_best_dist || !d_result || grid_cols < 1 || grid_rows < 1 || nq < 0 || list_cap < 1)
         return orbx_set_error(ORBX_E_ARG, "bad argument");
-    M_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
-    M_TRY(hipMemsetAsync(d_result, 0, 32, s));
+    ORB_TRY(c->hs.device_call(s));
+    ORB_TRY(hipMemsetAsync(d_result, 0, 32, s));
     if (nq == 0) return ORBX_OK;
     // scratch: [counts nq][lo nq][lists nq * list_cap]
     const size_t N = (size_t)nq;
-    M_TRY(c->w_out.need(N * 8 + N * list_cap * 4 + 16));
+    ORB_TRY(need(c->w_out, N * 8 + N * list_cap * 4 + 16));
     int32_t *d_counts = (int32_t *)c->w_out.p, *d_lo = d_counts + N;
     uint32_t *d_lists = (uint32_t *)(d_lo + N);
     hipLaunchKernelGGL(k_fuse_levels, dim3((nq + 255) / 256), dim3(256), 0, s, d_q_level, nq, d_lo);
@@ -2526,7 +2456,7 @@ extern "C" int orbm_search_fuse_device(orbm_t *c, const uint8_t *d_q_desc, const
                        grid_cols, grid_rows, d_q_desc, d_q_xy, d_q_radius, d_lo, d_q_level, d_q_ok, nq, 1, d_sigma2, list_cap, d_counts,
                        d_lists, nullptr, nullptr);
     hipLaunchKernelGGL(k_fuse_best, dim3((nq + 255) / 256), dim3(256), 0, s, d_counts, d_lists, list_cap, nq, d_best_idx, d_best_dist, d_result);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -2543,30 +2473,29 @@ extern "C" int orbm_search_for_initialization_device(orbm_t *c, float nn_ratio, 
     if (n2 >= (1 << 22)) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 2^22 key points");
     const size_t lds = ((size_t)n2 + 5 * (size_t)n1) * 4;
     if (lds > 150 * 1024) return orbx_set_error(ORBX_E_UNSUPPORTED, "n2 + 5 n1 above 38400: the resolve keeps the claims in LDS");
-    M_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
-    M_TRY(hipMemsetAsync(d_result, 0, 32, s));
+    ORB_TRY(c->hs.device_call(s));
+    ORB_TRY(hipMemsetAsync(d_result, 0, 32, s));
     if (n1 == 0) return ORBX_OK;
-    if (n2 == 0) { M_TRY(hipMemsetAsync(d_matches12, 0xFF, sizeof(int32_t) * (size_t)n1, s)); return ORBX_OK; }
+    if (n2 == 0) { ORB_TRY(hipMemsetAsync(d_matches12, 0xFF, sizeof(int32_t) * (size_t)n1, s)); return ORBX_OK; }
     // scratch: [total, pad x3][counts n1][offs n1][level n1][radius n1][ok n1 bytes, padded][pool n1 * list_cap]
     const size_t pool_cap = (size_t)n1 * list_cap, N = (size_t)n1, okb = (N + 15) / 16 * 16;
-    M_TRY(c->w_out.need(16 + N * 16 + okb + pool_cap * 4 + 16));
+    ORB_TRY(need(c->w_out, 16 + N * 16 + okb + pool_cap * 4 + 16));
     int32_t *d_total = (int32_t *)c->w_out.p, *d_counts = d_total + 4, *d_offs = d_counts + N, *d_lv = d_offs + N;
     float *d_r = (float *)(d_lv + N);
     uint8_t *d_ok = (uint8_t *)(d_r + N);
     uint32_t *d_pool = (uint32_t *)(d_ok + okb);
-    M_TRY(hipMemsetAsync(d_total, 0, 16, s));
+    ORB_TRY(hipMemsetAsync(d_total, 0, 16, s));
     hipLaunchKernelGGL(k_init_queries, dim3((n1 + 255) / 256), dim3(256), 0, s, (const orbx_kp *)d_kps1, n1, (float)window_size, d_ok, d_r, d_lv);
     hipLaunchKernelGGL(k_window_lists, dim3((n1 + 3) / 4), dim3(256), 0, s, (const orbx_kp *)d_kps2, d_desc2, d_cell_start2, d_cell_items2,
                        grid_cols, grid_rows, d_desc1, d_pre, d_r, d_lv, d_lv, d_ok, n1, 0, nullptr, (int)std::min(pool_cap, (size_t)INT_MAX),
                        d_counts, d_pool, d_total, d_offs);
-    M_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_init_resolve), 150 * 1024));
+    ORB_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_init_resolve), 150 * 1024));
     hipLaunchKernelGGL(k_init_resolve, dim3(1), dim3(PR_T), lds, s, d_counts, d_offs, d_pool, (int)std::min(pool_cap, (size_t)INT_MAX), d_total,
                        n1, n2, (const orbx_kp *)d_kps1, (const orbx_kp *)d_kps2, nn_ratio, check_orientation,
                        c->init_max_sweeps > 0 ? c->init_max_sweeps : ORBM_INIT_MAX_SWEEPS, c->init_lanes, d_matches12,
                        d_pre, d_result);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -2584,20 +2513,19 @@ static int bow_device(orbm_ctx *c, int mode, float nn_ratio, int check_orientati
         !d_fv2_idx || !d_n_fv2 || !d_result || !d_kps1 || !d_kps2 || (mode == 0 ? !d_frame_mp : (!d_matches12 || !d_busy2)))
         return orbx_set_error(ORBX_E_ARG, "null argument");
     if (n1 < 0 || n2 < 0) return orbx_set_error(ORBX_E_ARG, "bad size");
-    M_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
-    M_TRY(hipMemsetAsync(d_result, 0, 32, s));
-    if (mode == 1 && n1 > 0) M_TRY(hipMemsetAsync(d_matches12, 0xFF, sizeof(int32_t) * (size_t)n1, s)); // -1 (:457)
+    ORB_TRY(c->hs.device_call(s));
+    ORB_TRY(hipMemsetAsync(d_result, 0, 32, s));
+    if (mode == 1 && n1 > 0) ORB_TRY(hipMemsetAsync(d_matches12, 0xFF, sizeof(int32_t) * (size_t)n1, s)); // -1 (:457)
     if (n1 == 0 || n2 == 0) return ORBX_OK;
     // scratch (the handle's, one call in flight per handle): node_p2[n1], node_qbegin[n1 + 1], q_idx / c_begin / c_len / q_node [n1],
     // n_queries, hist[30], match_list[2 n1], topk[n1 * K]
     const size_t N = (size_t)n1;
-    M_TRY(c->w_grid.need(sizeof(int32_t) * (N * 8 + 64 + N * BR_TOPK + 8)));
+    ORB_TRY(need(c->w_grid, sizeof(int32_t) * (N * 8 + 64 + N * BR_TOPK + 8)));
     int32_t *node_p2 = (int32_t *)c->w_grid.p, *node_qbegin = node_p2 + N, *q_idx = node_qbegin + N + 1, *c_begin = q_idx + N, *c_len = c_begin + N,
             *q_node = c_len + N, *n_queries = q_node + N, *hist = n_queries + 1, *match_list = hist + 32;
     uint32_t *topk = (uint32_t *)(match_list + 2 * N);
-    M_TRY(hipMemsetAsync(n_queries, 0, sizeof(int32_t) * 33, s));
+    ORB_TRY(hipMemsetAsync(n_queries, 0, sizeof(int32_t) * 33, s));
     const BowFv f1 = {d_fv1_nodes, d_fv1_off, d_fv1_idx, d_n_fv1}, f2 = {d_fv2_nodes, d_fv2_off, d_fv2_idx, d_n_fv2};
     hipLaunchKernelGGL(k_bow_queries, dim3(1), dim3(BQ_T), 0, s, f1, f2, d_mask1, mode == 0 ? 1 : 0, n1, n1, node_p2, node_qbegin, q_idx, c_begin,
                        c_len, q_node, n_queries, d_result);
@@ -2614,7 +2542,7 @@ static int bow_device(orbm_ctx *c, int mode, float nn_ratio, int check_orientati
         hipLaunchKernelGGL(k_bow_finish<0>, dim3(1), dim3(256), 0, s, check_orientation, hist, match_list, d_frame_mp, d_matches12, d_result);
     else
         hipLaunchKernelGGL(k_bow_finish<1>, dim3(1), dim3(256), 0, s, check_orientation, hist, match_list, d_frame_mp, d_matches12, d_result);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 extern "C" int orbm_search_by_bow_device(orbm_t *c, float nn_ratio, int check_orientation, const uint8_t *d_desc1, const void *d_kps1,
@@ -2648,10 +2576,10 @@ extern "C" int orbm_window_lists_device(orbm_t *c, const void *d_kps, const uint
         return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (nq == 0) return ORBX_OK;
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call(s));
     hipLaunchKernelGGL(k_window_lists, dim3((nq + 3) / 4), dim3(256), 0, s, (const orbx_kp *)d_kps, d_desc, d_cell_start,
                        d_cell_items, grid_cols, grid_rows, d_q_desc, d_q_xy, d_q_radius, d_q_min_level, d_q_max_level, d_q_ok,
                        nq, strict ? 1 : 0, d_sigma2, cap, d_counts, d_lists, nullptr, nullptr);
-    M_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }

@@ -16,21 +16,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/orbv.h"
+#include "orb_host.h"
 #include "orb_math.h"
 
-int orbx_set_error(int code, const std::string &msg);
 hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes); // orbx_api.hip: dynamic LDS above 64 KB, per kernel and per device
-
-#define V_TRY(expr)                                                                                                    \
-    do {                                                                                                               \
-        hipError_t e_ = (expr);                                                                                        \
-        if (e_ != hipSuccess) return orbx_set_error(ORBX_E_NO_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
 
 struct VocDev {
     const int32_t *first;    // [n_nodes + 1] start of node's children in the packed arrays
@@ -42,14 +35,14 @@ struct VocDev {
 };
 
 struct VocLane {
+    int device = 0;
     hipStream_t stream = nullptr;
-    // per-feature scratch of the batch transform
-    uint32_t *s_word = nullptr, *s_node = nullptr;
-    double *s_w = nullptr;
-    size_t s_items = 0;
+    // per-feature scratch of the batch transform: word and node ids (4 B), weights (8 B)
+    DevBuf s_word, s_node, s_w;
     // host-pointer staging: ONE device block and its page-locked mirror, laid out for `h_cap` features:
     // [descriptors 32 B][counts n, n_words, n_fv + pad: 16 B][bow ids 4 B][bow values 8 B][fv nodes 4 B][fv offsets 4 B (+1)][fv indices 4 B]
-    uint8_t *d_blk = nullptr, *h_blk = nullptr;
+    DevBuf d_blk;
+    PinBuf h_blk;
     size_t h_cap = 0;
     static size_t al(size_t x) { return (x + 15) & ~(size_t)15; }
     size_t o_cnt() const { return al(h_cap * 32); }
@@ -59,32 +52,30 @@ struct VocLane {
     size_t o_off() const { return al(o_nodes() + h_cap * 4); }
     size_t o_idx() const { return al(o_off() + (h_cap + 1) * 4); }
     size_t bytes() const { return al(o_idx() + h_cap * 4); }
+    hipError_t init() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
     void release()
     {
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); stream = nullptr; }
-        for (void *p : {(void *)s_word, (void *)s_node, (void *)s_w, (void *)d_blk})
-            if (p) (void)hipFree(p);
-        if (h_blk) (void)hipHostFree(h_blk);
-        s_word = s_node = nullptr; s_w = nullptr; s_items = 0;
-        d_blk = h_blk = nullptr; h_cap = 0;
+        for (DevBuf *b : {&s_word, &s_node, &s_w, &d_blk}) b->release();
+        h_blk.release();
+        h_cap = 0;
     }
 };
 
 struct orbv_ctx {
-    int device = 0, k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;
+    HandleStream hs; // the device and the NULL-stream bookkeeping; host-pointer calls lease a lane's stream instead
+    int k = 0, L = 0, scoring = 0, weighting = 0, n_nodes = 0, n_words = 0;
     std::vector<int32_t> parent;
     std::vector<uint8_t> is_leaf, desc;
     std::vector<double> weight;
     VocDev dev{};
     void *d_first = nullptr, *d_pk_id = nullptr, *d_pk_desc = nullptr, *d_word_id = nullptr, *d_weight = nullptr;
-    bool null_pending = false; // a device call was enqueued on stream 0 (NULL): destroy waits for it too
     // The reference's vocabulary is ONE object that Tracking (Frame::computeBow, Frame.cpp:168-178) and LocalMapping
     // (KeyFrame::computeBow, LocalMapping.cpp:90) call at the same time: the tree above is read-only, everything a call writes
     // lives in a lane.  The device entry points use `dev_lane` (scratch only; one call in flight per handle, as orbv.h says);
     // every host-pointer call leases a lane of its own -- non-blocking stream, scratch, staging -- so orbv_transform is re-entrant.
     VocLane dev_lane;
-    std::mutex mu;
-    std::vector<VocLane *> idle;
+    LeasePool<VocLane> lanes; // freed by orbv_destroy
 };
 
 __device__ __forceinline__ int ham256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
@@ -299,16 +290,16 @@ static int upload(orbv_ctx *c)
         if (c->is_leaf[i]) word_id[i] = (uint32_t)n_words++; // :1408-1414
     }
     c->n_words = n_words;
-    V_TRY(hipMalloc(&c->d_first, first.size() * 4));
-    V_TRY(hipMalloc(&c->d_pk_id, pk_id.size() * 4));
-    V_TRY(hipMalloc(&c->d_pk_desc, pk_desc.size()));
-    V_TRY(hipMalloc(&c->d_word_id, word_id.size() * 4));
-    V_TRY(hipMalloc(&c->d_weight, (size_t)n * 8));
-    V_TRY(hipMemcpy(c->d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(c->d_pk_id, pk_id.data(), pk_id.size() * 4, hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(c->d_pk_desc, pk_desc.data(), pk_desc.size(), hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(c->d_word_id, word_id.data(), word_id.size() * 4, hipMemcpyHostToDevice));
-    V_TRY(hipMemcpy(c->d_weight, c->weight.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+    ORB_TRY(hipMalloc(&c->d_first, first.size() * 4));
+    ORB_TRY(hipMalloc(&c->d_pk_id, pk_id.size() * 4));
+    ORB_TRY(hipMalloc(&c->d_pk_desc, pk_desc.size()));
+    ORB_TRY(hipMalloc(&c->d_word_id, word_id.size() * 4));
+    ORB_TRY(hipMalloc(&c->d_weight, (size_t)n * 8));
+    ORB_TRY(hipMemcpy(c->d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice));
+    ORB_TRY(hipMemcpy(c->d_pk_id, pk_id.data(), pk_id.size() * 4, hipMemcpyHostToDevice));
+    ORB_TRY(hipMemcpy(c->d_pk_desc, pk_desc.data(), pk_desc.size(), hipMemcpyHostToDevice));
+    ORB_TRY(hipMemcpy(c->d_word_id, word_id.data(), word_id.size() * 4, hipMemcpyHostToDevice));
+    ORB_TRY(hipMemcpy(c->d_weight, c->weight.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     c->dev = VocDev{(const int32_t *)c->d_first, (const uint32_t *)c->d_pk_id, (const uint4 *)c->d_pk_desc,
                     (const uint32_t *)c->d_word_id, (const double *)c->d_weight, c->L, c->n_words, c->scoring, c->weighting};
     return ORBX_OK;
@@ -325,13 +316,10 @@ extern "C" int orbv_create(int k, int L, int scoring, int weighting, int n_nodes
     for (int i = 1; i < n_nodes; ++i)
         if (parent[i] < 0 || parent[i] >= i)
             return orbx_set_error(ORBX_E_ARG, "node " + std::to_string(i) + ": parent must be an earlier node");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return orbx_set_error(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= n_dev) return orbx_set_error(ORBX_E_ARG, "device index out of range");
-    V_TRY(hipSetDevice(device));
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
     orbv_ctx *c = new orbv_ctx();
-    c->device = device; c->k = k; c->L = L; c->scoring = scoring; c->weighting = weighting; c->n_nodes = n_nodes;
+    c->hs.device = device; c->k = k; c->L = L; c->scoring = scoring; c->weighting = weighting; c->n_nodes = n_nodes;
     c->parent.assign((size_t)n_nodes, 0);
     c->is_leaf.assign((size_t)n_nodes, 0);
     c->desc.assign((size_t)n_nodes * 32, 0);
@@ -425,9 +413,8 @@ extern "C" int orbv_load_text(const char *path, int device, orbv_t **out)
 extern "C" void orbv_destroy(orbv_t *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->null_pending) (void)hipStreamSynchronize((hipStream_t)0);
-    for (VocLane *ln : c->idle) { ln->release(); delete ln; }
+    c->hs.destroy();
+    for (VocLane *ln : c->lanes.idle) { ln->release(); delete ln; }
     c->dev_lane.release();
     for (void *p : {c->d_first, c->d_pk_id, c->d_pk_desc, c->d_word_id, c->d_weight})
         if (p) (void)hipFree(p);
@@ -470,12 +457,11 @@ extern "C" int orbv_transform_features_device(orbv_t *c, const uint8_t *d_desc, 
     if (check_levelsup(levelsup)) return ORBX_E_ARG;
     if (c->n_words == 0) return orbx_set_error(ORBX_E_ARG, "empty vocabulary");
     if (n == 0) return ORBX_OK;
-    V_TRY(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call(s));
     hipLaunchKernelGGL(k_voc_descend, dim3((n + 255) / 256, 1), dim3(256), 0, s, c->dev, d_desc, (const int32_t *)nullptr, n,
                        n, levelsup, d_word, d_node, d_weight);
-    V_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -484,31 +470,26 @@ static int transform_enqueue(orbv_ctx *c, VocLane &ln, int n_frames, const uint8
                              uint32_t *d_bow_ids, double *d_bow_vals, int32_t *d_n_words, uint32_t *d_fv_nodes, int32_t *d_fv_off,
                              uint32_t *d_fv_idx, int32_t *d_n_fv, hipStream_t s)
 {
-    const size_t need = (size_t)n_frames * cap;
-    if (need > ln.s_items) {
-        V_TRY(hipDeviceSynchronize());
-        for (void **p : {(void **)&ln.s_word, (void **)&ln.s_node, (void **)&ln.s_w})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
-        ln.s_items = 0;
-        const size_t grow = need + need / 2;
-        V_TRY(hipMalloc(&ln.s_word, grow * 4));
-        V_TRY(hipMalloc(&ln.s_node, grow * 4));
-        V_TRY(hipMalloc(&ln.s_w, grow * 8));
-        ln.s_items = grow;
-    }
+    const size_t items = (size_t)n_frames * cap, grow = items + items / 2;
+    if (items * 4 > ln.s_word.cap || items * 4 > ln.s_node.cap || items * 8 > ln.s_w.cap) ORB_TRY(hipDeviceSynchronize());
+    ORB_TRY(ln.s_word.need(items * 4, grow * 4));
+    ORB_TRY(ln.s_node.need(items * 4, grow * 4));
+    ORB_TRY(ln.s_w.need(items * 8, grow * 8));
+    uint32_t *s_word = ln.s_word.as<uint32_t>(), *s_node = ln.s_node.as<uint32_t>();
+    double *s_w = ln.s_w.as<double>();
     if (c->n_words > 0) { // empty vocabulary: transform() returns empty maps (:1133), k_voc_group handles it
         hipLaunchKernelGGL(k_voc_descend, dim3((std::min(cap, ORBV_MAX_FEATURES) + 255) / 256, n_frames), dim3(256), 0, s,
-                           c->dev, d_desc, d_n, 0, cap, levelsup, ln.s_word, ln.s_node, ln.s_w);
-        V_TRY(hipGetLastError());
+                           c->dev, d_desc, d_n, 0, cap, levelsup, s_word, s_node, s_w);
+        ORB_TRY(hipGetLastError());
     }
     int p_max = 256;
     while (p_max < std::min(cap, ORBV_MAX_FEATURES)) p_max <<= 1;
     const size_t lds = (size_t)p_max * 16;
     // more than 64 KB of dynamic LDS has to be requested once per device
-    V_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_voc_group), (size_t)ORBV_MAX_FEATURES * 16));
-    hipLaunchKernelGGL(k_voc_group, dim3(n_frames), dim3(256), lds, s, c->dev, d_n, cap, p_max, ln.s_word, ln.s_node, ln.s_w,
+    ORB_TRY(orbx_lds_opt_in(reinterpret_cast<const void *>(k_voc_group), (size_t)ORBV_MAX_FEATURES * 16));
+    hipLaunchKernelGGL(k_voc_group, dim3(n_frames), dim3(256), lds, s, c->dev, d_n, cap, p_max, s_word, s_node, s_w,
                        d_bow_ids, d_bow_vals, d_n_words, d_fv_nodes, d_fv_off, d_fv_idx, d_n_fv);
-    V_TRY(hipGetLastError());
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -526,39 +507,10 @@ extern "C" int orbv_transform_device(orbv_t *c, int n_frames, const uint8_t *d_d
         return orbx_set_error(ORBX_E_UNSUPPORTED, "cap exceeds ORBV_MAX_FEATURES features per frame");
     if (check_levelsup(levelsup)) return ORBX_E_ARG;
     if (n_frames == 0) return ORBX_OK;
-    V_TRY(hipSetDevice(c->device));
-    if (!stream) c->null_pending = true; // NULL is stream 0 itself (include/orbx.h, "Streams")
+    ORB_TRY(c->hs.device_call((hipStream_t)stream)); // NULL is stream 0 itself (include/orbx.h, "Streams")
     return transform_enqueue(c, c->dev_lane, n_frames, d_desc, d_n, cap, levelsup, d_bow_ids, d_bow_vals, d_n_words, d_fv_nodes, d_fv_off,
                              d_fv_idx, d_n_fv, (hipStream_t)stream);
 }
-
-namespace {
-// a host-pointer call's lane: taken from the handle's idle list (or made), given back when the call returns
-struct LaneLease {
-    orbv_ctx *c;
-    VocLane *ln = nullptr;
-    explicit LaneLease(orbv_ctx *ctx) : c(ctx) {}
-    ~LaneLease()
-    {
-        if (!ln) return;
-        (void)hipStreamSynchronize(ln->stream); // an error return may leave work in flight
-        std::lock_guard<std::mutex> lock(c->mu);
-        c->idle.push_back(ln);
-    }
-    hipError_t acquire()
-    {
-        {
-            std::lock_guard<std::mutex> lock(c->mu);
-            if (!c->idle.empty()) { ln = c->idle.back(); c->idle.pop_back(); return hipSuccess; }
-        }
-        VocLane *n = new VocLane();
-        hipError_t e = hipStreamCreateWithFlags(&n->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete n; return e; }
-        ln = n;
-        return hipSuccess;
-    }
-};
-} // namespace
 
 extern "C" int orbv_transform(orbv_t *c, const uint8_t *desc, int n, int levelsup, uint32_t *bow_ids, double *bow_vals,
                               int32_t *n_words, uint32_t *fv_nodes, int32_t *fv_off, uint32_t *fv_idx, int32_t *n_fv)
@@ -572,28 +524,28 @@ extern "C" int orbv_transform(orbv_t *c, const uint8_t *desc, int n, int levelsu
     fv_off[0] = 0;
     if (n == 0) return ORBX_OK;
     if (check_levelsup(levelsup)) return ORBX_E_ARG;
-    V_TRY(hipSetDevice(c->device));
-    LaneLease lease(c);
-    V_TRY(lease.acquire());
-    VocLane &ln = *lease.ln;
+    // (no wait for stream 0: the call runs in a lane of its own, not in the scratch of the NULL-stream device calls; and
+    // orbv_transform is re-entrant, so it must not touch the handle's bookkeeping)
+    ORB_TRY(hipSetDevice(c->hs.device));
+    Lease<VocLane> lease(c->lanes); // a lane of the handle's pool, given back when the call returns
+    ORB_TRY(lease.acquire(c->hs.device));
+    VocLane &ln = *lease.w;
     hipStream_t s = ln.stream;
     if ((size_t)n > ln.h_cap) {
-        V_TRY(hipStreamSynchronize(s));
-        if (ln.d_blk) { (void)hipFree(ln.d_blk); ln.d_blk = nullptr; }
-        if (ln.h_blk) { (void)hipHostFree(ln.h_blk); ln.h_blk = nullptr; }
+        ORB_TRY(hipStreamSynchronize(s));
         ln.h_cap = (size_t)n + n / 2 + 64;
         const size_t nb = ln.bytes();
-        hipError_t e = hipMalloc((void **)&ln.d_blk, nb);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&ln.h_blk, nb, hipHostMallocDefault);
-        if (e != hipSuccess) { ln.h_cap = 0; V_TRY(e); }
+        hipError_t e = ln.d_blk.need(nb, nb);
+        if (e == hipSuccess) e = ln.h_blk.need(nb, nb);
+        if (e != hipSuccess) { ln.h_cap = 0; ORB_TRY(e); }
     }
     // one copy up (descriptors + the count), the two kernels, one copy down (counts and the five arrays at their capacity), ONE wait:
     // the arrays then go to the caller from page-locked memory (was two waits and eight copies, five of them to pageable memory)
-    uint8_t *d = ln.d_blk, *h = ln.h_blk;
+    uint8_t *d = ln.d_blk.as<uint8_t>(), *h = ln.h_blk.as<uint8_t>();
     memcpy(h, desc, (size_t)n * 32);
     int32_t *hc = reinterpret_cast<int32_t *>(h + ln.o_cnt());
     hc[0] = n; hc[1] = 0; hc[2] = 0; hc[3] = 0;
-    V_TRY(hipMemcpyAsync(d, h, ln.o_ids(), hipMemcpyHostToDevice, s));
+    ORB_TRY(hipMemcpyAsync(d, h, ln.o_ids(), hipMemcpyHostToDevice, s));
     int32_t *cnt = reinterpret_cast<int32_t *>(d + ln.o_cnt()); // [0] n, [1] n_words, [2] n_fv
     int rc = transform_enqueue(c, ln, 1, d, cnt, n, levelsup, reinterpret_cast<uint32_t *>(d + ln.o_ids()), reinterpret_cast<double *>(d + ln.o_vals()),
                                cnt + 1, reinterpret_cast<uint32_t *>(d + ln.o_nodes()), reinterpret_cast<int32_t *>(d + ln.o_off()),
@@ -601,8 +553,8 @@ extern "C" int orbv_transform(orbv_t *c, const uint8_t *desc, int n, int levelsu
     if (rc) return rc;
     // (the arrays are laid out for h_cap features; only the first n -- n + 1 offsets -- of each can hold anything)
     const size_t down_end = ln.o_idx() + (size_t)n * 4;
-    V_TRY(hipMemcpyAsync(h + ln.o_cnt(), d + ln.o_cnt(), down_end - ln.o_cnt(), hipMemcpyDeviceToHost, s));
-    V_TRY(hipStreamSynchronize(s));
+    ORB_TRY(hipMemcpyAsync(h + ln.o_cnt(), d + ln.o_cnt(), down_end - ln.o_cnt(), hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
     const int nw = hc[1], nf = hc[2];
     if (nw < 0 || nw > n || nf < 0 || nf > n) return orbx_set_error(ORBX_E_NO_DEVICE, "orbv_transform: counts out of range");
     *n_words = nw;

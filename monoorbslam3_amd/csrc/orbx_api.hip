@@ -13,25 +13,15 @@
 #include <map>
 #include <mutex>
 #include <string>
-#include <chrono>
 #include <vector>
 
+#include "orb_host.h"
 #include "orb_math.h"
 #include "orbx_internal.h"
 
-#ifndef ORBX_HANDLE_STREAM_FLAGS // (a build with hipStreamDefault is round 5's blocking handle stream: tools/ab_latency.sh, tools/two_thread_latency.sh)
-#define ORBX_HANDLE_STREAM_FLAGS hipStreamNonBlocking
-#endif
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
-// shared with the matcher translation unit (orbm_matcher.hip)
-int orbx_set_error(int code, const std::string &msg) { return fail(code, msg); }
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(ORBX_E_NO_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+// the error path of every module (orb_host.h)
+int orbx_set_error(int code, const std::string &msg) { g_err = msg; return code; }
 
 hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes)
 {
@@ -50,7 +40,7 @@ hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes)
 
 struct orbx_ctx {
     orbx_cfg cfg;
-    int device;
+    HandleStream hs; // device, the handle's own stream, the NULL-stream bookkeeping
     int n_cus = ORBX_N_CUS; // the device's CU count (hipDeviceAttributeMultiprocessorCount at create): decides whether a few-frames
                             // quadtree launch gives every workgroup a CU of its own (orbx_octree_plan)
     // reference tables (ORBExtractor.h:109-121)
@@ -65,8 +55,6 @@ struct orbx_ctx {
     OrbxLevels levels;
     size_t l0_stage_pitch; // staging copy of level 0 for the host-pointer API
     // device state
-    hipStream_t stream;
-    bool null_pending = false; // a device call was enqueued on stream 0 (NULL) since the last host-side wait
     OrbxBuffers buf;
     OrbxLevels *d_levels;
     OrbxTap *d_xtap[ORBX_MAX_LEVELS], *d_ytap[ORBX_MAX_LEVELS];
@@ -132,15 +120,6 @@ struct orbx_ctx {
 // ------------------------------------------------------------------------------------------------
 // tables -- reference ORBExtractor.cpp:424-475
 // ------------------------------------------------------------------------------------------------
-// Host-side wait for everything enqueued through the handle: its own stream and, when a device call was given a NULL stream,
-// stream 0 (include/orbx.h, "Streams").
-static hipError_t sync_handle(orbx_ctx *c)
-{
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && c->null_pending) { e = hipStreamSynchronize((hipStream_t)0); c->null_pending = false; }
-    return e;
-}
-
 static void compute_quotas(orbx_ctx *c, int n_features)
 {
     // :443-452.  pow(float,int) is the double overload; the quotient is rounded once to float.
@@ -247,8 +226,8 @@ static int compute_geometry(const orbx_ctx *c, int w0, int h0, Geometry *g)
     for (int l = 0; l < LV.n_levels; ++l) {
         OrbxLevel &v = LV.lv[l];
         level_size(c, w0, h0, l, &v.w, &v.h);
-        if (v.w < 1 || v.h < 1) return fail(ORBX_E_ARG, "pyramid level collapses to zero size");
-        if (v.w > 32000 || v.h > 32000) return fail(ORBX_E_UNSUPPORTED, "image side above 32000 px");
+        if (v.w < 1 || v.h < 1) return orbx_set_error(ORBX_E_ARG, "pyramid level collapses to zero size");
+        if (v.w > 32000 || v.h > 32000) return orbx_set_error(ORBX_E_UNSUPPORTED, "image side above 32000 px");
         v.pitch = (int)align_up(v.w, 64);
         v.region_w = v.w - 2 * ORBX_EDGE;
         v.region_h = v.h - 2 * ORBX_EDGE;
@@ -289,7 +268,7 @@ static int compute_geometry(const orbx_ctx *c, int w0, int h0, Geometry *g)
     size_t p = 1;
     while (p < (size_t)max_quota) p <<= 1;
     g->sort_lds = p * sizeof(unsigned long long);
-    if (g->sort_lds > 60 * 1024) return fail(ORBX_E_UNSUPPORTED, "per-level quota above 7680 features");
+    if (g->sort_lds > 60 * 1024) return orbx_set_error(ORBX_E_UNSUPPORTED, "per-level quota above 7680 features");
     return ORBX_OK;
 }
 
@@ -311,94 +290,94 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
         g.img_fs = c->alloc_img_fs; g.cand_fs = c->alloc_cand_fs; g.node_fs = c->alloc_node_fs; g.l0_fs = c->alloc_l0_fs;
         g.l0_pitch = (int)c->l0_stage_pitch; g.sort_lds = c->sort_lds_bytes;
     }
-    HIP_TRY(hipSetDevice(c->device));
+    ORB_TRY(hipSetDevice(c->hs.device));
     const bool grow = batch > c->alloc_batch || g.img_fs > c->alloc_img_fs || g.cand_fs > c->alloc_cand_fs ||
                       g.node_fs > c->alloc_node_fs || g.l0_fs > c->alloc_l0_fs ||
                       g.levels.kcap_total > c->alloc_kcap_total;
     if (grow) {
         // arenas are about to be replaced: nothing enqueued earlier (on the handle's streams or the caller's) may
         // still be using them
-        HIP_TRY(hipDeviceSynchronize());
+        ORB_TRY(hipDeviceSynchronize());
         const int B = std::max(batch, c->alloc_batch);
         const size_t img_fs = std::max(g.img_fs, c->alloc_img_fs), cand_fs = std::max(g.cand_fs, c->alloc_cand_fs);
         const size_t node_fs = std::max(g.node_fs, c->alloc_node_fs), l0_fs = std::max(g.l0_fs, c->alloc_l0_fs);
         const int kcap = std::max(g.levels.kcap_total, c->alloc_kcap_total);
         OrbxBuffers &b = c->buf;
-        HIP_TRY(dev_alloc(&b.img_arena, img_fs * B));
-        HIP_TRY(dev_alloc(&b.cand, cand_fs * B));
-        HIP_TRY(dev_alloc(&b.pnode, cand_fs * B));
-        HIP_TRY(dev_alloc(&b.pcode, cand_fs * B));
-        HIP_TRY(dev_alloc(&b.cand_count, (size_t)ORBX_MAX_LEVELS * B));
-        HIP_TRY(dev_alloc(&b.bnd0, node_fs * B));
-        HIP_TRY(dev_alloc(&b.bnd1, node_fs * B));
-        HIP_TRY(dev_alloc(&b.cnt0, node_fs * B));
-        HIP_TRY(dev_alloc(&b.cnt1, node_fs * B));
-        HIP_TRY(dev_alloc(&b.rank, node_fs * B));
-        HIP_TRY(dev_alloc(&b.node_of_rank, node_fs * B));
-        HIP_TRY(dev_alloc(&b.newpos, node_fs * B));
-        HIP_TRY(dev_alloc(&b.childcnt, 4 * node_fs * B));
-        HIP_TRY(dev_alloc(&b.childpos, 4 * node_fs * B));
-        HIP_TRY(dev_alloc(&b.best, node_fs * B));
-        HIP_TRY(dev_alloc(&b.sel, (size_t)kcap * B));
-        HIP_TRY(dev_alloc(&b.kp_ang, (size_t)kcap * B));
-        HIP_TRY(dev_alloc(&b.sel_count, (size_t)ORBX_MAX_LEVELS * B));
-        HIP_TRY(dev_alloc(&b.sel_prefix, (size_t)ORBX_MAX_LEVELS * B));
-        HIP_TRY(dev_alloc(&c->d_l0_stage, l0_fs * B));
+        ORB_TRY(dev_alloc(&b.img_arena, img_fs * B));
+        ORB_TRY(dev_alloc(&b.cand, cand_fs * B));
+        ORB_TRY(dev_alloc(&b.pnode, cand_fs * B));
+        ORB_TRY(dev_alloc(&b.pcode, cand_fs * B));
+        ORB_TRY(dev_alloc(&b.cand_count, (size_t)ORBX_MAX_LEVELS * B));
+        ORB_TRY(dev_alloc(&b.bnd0, node_fs * B));
+        ORB_TRY(dev_alloc(&b.bnd1, node_fs * B));
+        ORB_TRY(dev_alloc(&b.cnt0, node_fs * B));
+        ORB_TRY(dev_alloc(&b.cnt1, node_fs * B));
+        ORB_TRY(dev_alloc(&b.rank, node_fs * B));
+        ORB_TRY(dev_alloc(&b.node_of_rank, node_fs * B));
+        ORB_TRY(dev_alloc(&b.newpos, node_fs * B));
+        ORB_TRY(dev_alloc(&b.childcnt, 4 * node_fs * B));
+        ORB_TRY(dev_alloc(&b.childpos, 4 * node_fs * B));
+        ORB_TRY(dev_alloc(&b.best, node_fs * B));
+        ORB_TRY(dev_alloc(&b.sel, (size_t)kcap * B));
+        ORB_TRY(dev_alloc(&b.kp_ang, (size_t)kcap * B));
+        ORB_TRY(dev_alloc(&b.sel_count, (size_t)ORBX_MAX_LEVELS * B));
+        ORB_TRY(dev_alloc(&b.sel_prefix, (size_t)ORBX_MAX_LEVELS * B));
+        ORB_TRY(dev_alloc(&c->d_l0_stage, l0_fs * B));
         c->alloc_batch = B; c->alloc_img_fs = img_fs; c->alloc_cand_fs = cand_fs; c->alloc_node_fs = node_fs;
         c->alloc_l0_fs = l0_fs; c->alloc_kcap_total = kcap;
         c->alloc_out_cap = 0; // host-API output staging is per (batch, cap)
     }
     if (out_cap > 0 && (out_cap > c->alloc_out_cap || grow)) {
-        HIP_TRY(hipDeviceSynchronize());
+        ORB_TRY(hipDeviceSynchronize());
         const int cap = std::max(out_cap, c->alloc_out_cap);
         const size_t B = (size_t)c->alloc_batch;
         c->out_kp_off = align_up(B * sizeof(int32_t), 256);
         c->out_desc_off = align_up(c->out_kp_off + B * cap * sizeof(orbx_kp), 256);
         c->out_block_bytes = c->out_desc_off + B * cap * 32;
-        HIP_TRY(dev_alloc(&c->d_out_block, c->out_block_bytes));
+        ORB_TRY(dev_alloc(&c->d_out_block, c->out_block_bytes));
         c->d_out_n = reinterpret_cast<int32_t *>(c->d_out_block);
         c->d_out_kp = reinterpret_cast<orbx_kp *>(c->d_out_block + c->out_kp_off);
         c->d_out_desc = c->d_out_block + c->out_desc_off;
         if (c->h_out_block) { (void)hipHostFree(c->h_out_block); c->h_out_block = nullptr; }
         c->h_out_dev = nullptr;
         if (c->out_block_bytes <= (size_t)4 << 20) {
-            HIP_TRY(hipHostMalloc((void **)&c->h_out_block, c->out_block_bytes, hipHostMallocMapped));
+            ORB_TRY(hipHostMalloc((void **)&c->h_out_block, c->out_block_bytes, hipHostMallocMapped));
             // the descriptor kernel writes a small call's records straight into this block (no copy back);
             // ORBX_VAR_ZERO_COPY = 0 keeps them in HBM and copies
-            HIP_TRY(hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out_block, 0));
+            ORB_TRY(hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out_block, 0));
         }
         c->alloc_out_cap = cap;
     }
     if (!same) {
-        HIP_TRY(hipDeviceSynchronize()); // the level / tap / cell tables below are read by in-flight kernels
+        ORB_TRY(hipDeviceSynchronize()); // the level / tap / cell tables below are read by in-flight kernels
         c->levels = g.levels;
         c->cur_w = w0; c->cur_h = h0;
         c->l0_stage_pitch = g.l0_pitch;
         c->sort_lds_bytes = g.sort_lds;
-        HIP_TRY(hipMemcpy(c->d_levels, &c->levels, sizeof(OrbxLevels), hipMemcpyHostToDevice));
+        ORB_TRY(hipMemcpy(c->d_levels, &c->levels, sizeof(OrbxLevels), hipMemcpyHostToDevice));
         {
             std::vector<int> sl((size_t)std::max(c->levels.kcap_total, 1), 0);
             for (int l = 0; l < c->levels.n_levels; ++l)
                 for (int k = c->levels.lv[l].kp_off; k < c->levels.lv[l].kp_off + c->levels.lv[l].kcap && k < c->levels.kcap_total; ++k)
                     sl[k] = l;
-            HIP_TRY(dev_alloc(&c->d_slot_level, sl.size()));
-            HIP_TRY(hipMemcpy(c->d_slot_level, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_slot_level, sl.size()));
+            ORB_TRY(hipMemcpy(c->d_slot_level, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice));
             c->buf.slot_level = c->d_slot_level;
         }
         {
             const int nc = orbx_build_fast_cells(c->levels, nullptr);
             std::vector<uint16_t> cells((size_t)std::max(nc, 1) * 4);
             orbx_build_fast_cells(c->levels, cells.data());
-            HIP_TRY(dev_alloc(&c->d_fast_cells, cells.size()));
-            HIP_TRY(hipMemcpy(c->d_fast_cells, cells.data(), cells.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_fast_cells, cells.size()));
+            ORB_TRY(hipMemcpy(c->d_fast_cells, cells.data(), cells.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
             c->n_fast_cells = nc;
         }
         {
             const int ns = orbx_build_fast_strips(c->levels, 0, c->levels.n_levels, nullptr);
             std::vector<uint16_t> st((size_t)std::max(ns, 1) * 4);
             orbx_build_fast_strips(c->levels, 0, c->levels.n_levels, st.data());
-            HIP_TRY(dev_alloc(&c->d_fast_strips, st.size()));
-            HIP_TRY(hipMemcpy(c->d_fast_strips, st.data(), st.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_fast_strips, st.size()));
+            ORB_TRY(hipMemcpy(c->d_fast_strips, st.data(), st.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
             c->n_fast_strips = ns;
             c->n_fast_strips0 = orbx_build_fast_strips(c->levels, 0, 1, nullptr);
         }
@@ -406,38 +385,38 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
             const int nt = orbx_build_blur_tiles(c->levels, nullptr);
             std::vector<uint16_t> tl((size_t)std::max(nt, 1) * 4);
             orbx_build_blur_tiles(c->levels, tl.data());
-            HIP_TRY(dev_alloc(&c->d_blur_tiles, tl.size()));
-            HIP_TRY(hipMemcpy(c->d_blur_tiles, tl.data(), tl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_blur_tiles, tl.size()));
+            ORB_TRY(hipMemcpy(c->d_blur_tiles, tl.data(), tl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
             c->n_blur_tiles = nt;
             std::vector<uint16_t> bs;
             std::vector<uint8_t> bh, bv;
             orbx_build_blur_mfma(c->levels, c->taps, bs, bh, bv, c->blur_tab, c->blur_strips_before);
             c->blur_mfma_levels = orbx_blur_mfma_levels(c->levels);
-            HIP_TRY(dev_alloc(&c->d_blur_strips, std::max(bs.size(), (size_t)2)));
-            HIP_TRY(dev_alloc(&c->d_band_h, std::max(bh.size(), (size_t)16)));
-            HIP_TRY(dev_alloc(&c->d_band_v, std::max(bv.size(), (size_t)16)));
-            if (!bs.empty()) HIP_TRY(hipMemcpy(c->d_blur_strips, bs.data(), bs.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            if (!bh.empty()) HIP_TRY(hipMemcpy(c->d_band_h, bh.data(), bh.size(), hipMemcpyHostToDevice));
-            if (!bv.empty()) HIP_TRY(hipMemcpy(c->d_band_v, bv.data(), bv.size(), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_blur_strips, std::max(bs.size(), (size_t)2)));
+            ORB_TRY(dev_alloc(&c->d_band_h, std::max(bh.size(), (size_t)16)));
+            ORB_TRY(dev_alloc(&c->d_band_v, std::max(bv.size(), (size_t)16)));
+            if (!bs.empty()) ORB_TRY(hipMemcpy(c->d_blur_strips, bs.data(), bs.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            if (!bh.empty()) ORB_TRY(hipMemcpy(c->d_band_h, bh.data(), bh.size(), hipMemcpyHostToDevice));
+            if (!bv.empty()) ORB_TRY(hipMemcpy(c->d_band_v, bv.data(), bv.size(), hipMemcpyHostToDevice));
             std::vector<uint16_t> bb;
             std::vector<uint8_t> bdh;
             orbx_build_blur_desc(c->levels, c->taps, c->blur_tab, bb, bdh, c->bd_tab, &c->bd_levels, &c->bd_bk_stride);
             c->n_bd_blocks = (int)(bb.size() / 2);
-            HIP_TRY(dev_alloc(&c->d_bd_blocks, std::max(bb.size(), (size_t)2)));
-            HIP_TRY(dev_alloc(&c->d_bd_band_h, std::max(bdh.size(), (size_t)16)));
-            if (!bb.empty()) HIP_TRY(hipMemcpy(c->d_bd_blocks, bb.data(), bb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            if (!bdh.empty()) HIP_TRY(hipMemcpy(c->d_bd_band_h, bdh.data(), bdh.size(), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_bd_blocks, std::max(bb.size(), (size_t)2)));
+            ORB_TRY(dev_alloc(&c->d_bd_band_h, std::max(bdh.size(), (size_t)16)));
+            if (!bb.empty()) ORB_TRY(hipMemcpy(c->d_bd_blocks, bb.data(), bb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            if (!bdh.empty()) ORB_TRY(hipMemcpy(c->d_bd_band_h, bdh.data(), bdh.size(), hipMemcpyHostToDevice));
         }
         std::vector<OrbxTap> taps, ytaps;
         for (int l = 1; l < c->levels.n_levels; ++l) {
             const OrbxLevel &d = c->levels.lv[l], &s = c->levels.lv[l - 1];
             linear_taps(d.w, s.w, true, taps);
             while (taps.size() % 4) taps.push_back(taps.back()); // k_resize reads the column taps four at a time
-            HIP_TRY(dev_alloc(&c->d_xtap[l], taps.size()));
-            HIP_TRY(hipMemcpy(c->d_xtap[l], taps.data(), taps.size() * sizeof(OrbxTap), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_xtap[l], taps.size()));
+            ORB_TRY(hipMemcpy(c->d_xtap[l], taps.data(), taps.size() * sizeof(OrbxTap), hipMemcpyHostToDevice));
             linear_taps(d.h, s.h, false, ytaps);
-            HIP_TRY(dev_alloc(&c->d_ytap[l], ytaps.size()));
-            HIP_TRY(hipMemcpy(c->d_ytap[l], ytaps.data(), ytaps.size() * sizeof(OrbxTap), hipMemcpyHostToDevice));
+            ORB_TRY(dev_alloc(&c->d_ytap[l], ytaps.size()));
+            ORB_TRY(hipMemcpy(c->d_ytap[l], ytaps.data(), ytaps.size() * sizeof(OrbxTap), hipMemcpyHostToDevice));
             // levels l - 1 and l from one launch (source: level l - 2): the patch of level l - 1 a tile of level l needs
             c->resize2_ok[l - 1] = l >= 2 && orbx_resize2_fits(taps.data(), ytaps.data(), s.w, s.h, d.w, d.h);
             c->resize_lds_ok[l] = orbx_resize_lds_fits(taps.data(), ytaps.data(), s.w, s.h, d.w, d.h);
@@ -445,12 +424,12 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
     }
     // k_blur_desc's per-frame bucket starts and 32-byte item records: grown with the batch, the slot count or the bucket count
     if (c->alloc_batch > c->alloc_bd_batch || c->levels.kcap_total > c->alloc_bd_kcap || c->bd_bk_stride > c->alloc_bd_stride) {
-        HIP_TRY(hipDeviceSynchronize());
+        ORB_TRY(hipDeviceSynchronize());
         c->alloc_bd_batch = std::max(c->alloc_batch, c->alloc_bd_batch);
         c->alloc_bd_kcap = std::max(c->levels.kcap_total, c->alloc_bd_kcap);
         c->alloc_bd_stride = std::max(c->bd_bk_stride, c->alloc_bd_stride);
-        HIP_TRY(dev_alloc(&c->d_bd_bk_start, (size_t)c->alloc_bd_stride * c->alloc_bd_batch));
-        HIP_TRY(dev_alloc(&c->d_bd_items, (size_t)32 * std::max(c->alloc_bd_kcap, 1) * c->alloc_bd_batch));
+        ORB_TRY(dev_alloc(&c->d_bd_bk_start, (size_t)c->alloc_bd_stride * c->alloc_bd_batch));
+        ORB_TRY(dev_alloc(&c->d_bd_items, (size_t)32 * std::max(c->alloc_bd_kcap, 1) * c->alloc_bd_batch));
     }
     // frame strides of the arenas are the allocated ones
     c->buf.img_frame_stride = c->alloc_img_fs;
@@ -465,54 +444,48 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
 // ------------------------------------------------------------------------------------------------
 static int create_common(const orbx_cfg *cfg, const int *quotas_override, orbx_t **out)
 {
-    if (!cfg || !out) return fail(ORBX_E_ARG, "null argument");
+    if (!cfg || !out) return orbx_set_error(ORBX_E_ARG, "null argument");
     *out = nullptr;
-    if (cfg->n_levels < 1 || cfg->n_levels > ORBX_MAX_LEVELS) return fail(ORBX_E_ARG, "n_levels out of range");
-    if (cfg->n_features < 1) return fail(ORBX_E_ARG, "n_features must be >= 1");
-    if (!(cfg->scale_factor > 1.0f)) return fail(ORBX_E_ARG, "scale_factor must be > 1");
+    if (cfg->n_levels < 1 || cfg->n_levels > ORBX_MAX_LEVELS) return orbx_set_error(ORBX_E_ARG, "n_levels out of range");
+    if (cfg->n_features < 1) return orbx_set_error(ORBX_E_ARG, "n_features must be >= 1");
+    if (!(cfg->scale_factor > 1.0f)) return orbx_set_error(ORBX_E_ARG, "scale_factor must be > 1");
     if (fabs((double)cfg->scale_factor - 2.0) < 1e-6)
-        return fail(ORBX_E_UNSUPPORTED, "scale_factor 2.0 takes cv::resize's INTER_AREA shortcut, not implemented");
+        return orbx_set_error(ORBX_E_UNSUPPORTED, "scale_factor 2.0 takes cv::resize's INTER_AREA shortcut, not implemented");
     if (cfg->ini_th_fast < 1 || cfg->min_th_fast < 1 || cfg->ini_th_fast > 254 || cfg->min_th_fast > 254)
-        return fail(ORBX_E_ARG, "FAST thresholds must be in [1,254]");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return fail(ORBX_E_NO_DEVICE, "no HIP device available (this library has no CPU path)");
+        return orbx_set_error(ORBX_E_ARG, "FAST thresholds must be in [1,254]");
+    int dev = cfg->device;
+    if (int rc = orb_need_device(&dev)) return rc;
     orbx_ctx *c = new orbx_ctx(); // value-initialised: every member is zero
     c->cfg = *cfg;
     if (c->cfg.max_batch < 1) c->cfg.max_batch = 1;
-    int dev = cfg->device;
-    if (dev < 0) { if (hipGetDevice(&dev) != hipSuccess) dev = 0; }
-    if (dev >= ndev) { delete c; return fail(ORBX_E_ARG, "device ordinal out of range"); }
-    c->device = dev;
+    c->hs.device = dev;
     compute_tables(c);
     if (quotas_override) memcpy(c->quotas, quotas_override, sizeof(int) * cfg->n_levels);
     c->cur_w = c->cur_h = -1;
     auto cleanup = [&](int code) { orbx_destroy(c); return code; };
-    if (hipSetDevice(dev) != hipSuccess) return cleanup(fail(ORBX_E_NO_DEVICE, "hipSetDevice failed"));
+    if (hipSetDevice(dev) != hipSuccess) return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipSetDevice failed"));
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) c->n_cus = cus; }
-    // The handle's own stream serves the HOST-POINTER entry points only (a NULL stream argument of a device entry point is
-    // stream 0 itself) and is NON-BLOCKING: such a call uploads, computes, downloads and waits on it, so nothing of it has to be
-    // ordered with the legacy stream -- and a blocking stream would make every legacy-stream operation of any thread of the
-    // process (another thread's hipMemcpy, its NULL-stream device calls) a barrier against this handle's work: the reference runs
-    // Tracking and LocalMapping side by side (include/orbx.h, "Streams").  The internal side / sub-streams below are forked
+    // The handle's own stream (orb_host.h, HandleStream) is NON-BLOCKING: a blocking one would make every legacy-stream operation
+    // of any thread of the process (another thread's hipMemcpy, its NULL-stream device calls) a barrier against this handle's
+    // work, and the reference runs Tracking and LocalMapping side by side.  The internal side / sub-streams below are forked
     // from and joined into the stream of the call with events.
-    if (hipStreamCreateWithFlags(&c->stream, ORBX_HANDLE_STREAM_FLAGS) != hipSuccess)
-        return cleanup(fail(ORBX_E_NO_DEVICE, "hipStreamCreate failed"));
+    if (c->hs.create() != hipSuccess)
+        return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipStreamCreate failed"));
     for (int i = 0; i <= ORBX_N_STAGES; ++i)
-        if (hipEventCreate(&c->ev[i]) != hipSuccess) return cleanup(fail(ORBX_E_NO_DEVICE, "hipEventCreate failed"));
+        if (hipEventCreate(&c->ev[i]) != hipSuccess) return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipEventCreate failed"));
     for (int i = 0; i < 8; ++i)
         if (hipStreamCreateWithFlags(&c->sub[i], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming) != hipSuccess)
-            return cleanup(fail(ORBX_E_NO_DEVICE, "sub-stream creation failed"));
+            return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "sub-stream creation failed"));
     if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess)
-        return cleanup(fail(ORBX_E_NO_DEVICE, "hipEventCreate failed"));
+        return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipEventCreate failed"));
     for (int i = 0; i < 9; ++i)
         if (hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_pyr[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_blur[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_start[i], hipEventDisableTiming) != hipSuccess ||
             hipEventCreateWithFlags(&c->ev_fast0[i], hipEventDisableTiming) != hipSuccess)
-            return cleanup(fail(ORBX_E_NO_DEVICE, "side-stream creation failed"));
+            return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "side-stream creation failed"));
     // kernel-choice switches: defaults here, orbx_set_variant() changes them per handle (include/orbx.h)
     c->side_blur = 1;      // the blur on a side stream next to FAST
     c->early_fast = -1;    // level 0's FAST beside the pyramid unless the pyramid is k_resize_lds's (see enqueue)
@@ -531,10 +504,10 @@ static int create_common(const orbx_cfg *cfg, const int *quotas_override, orbx_t
     if (hipMalloc((void **)&c->d_levels, sizeof(OrbxLevels)) != hipSuccess ||
         hipMalloc((void **)&c->d_umax, sizeof(int) * 16) != hipSuccess ||
         hipMalloc((void **)&c->d_taps, sizeof(int) * 8) != hipSuccess)
-        return cleanup(fail(ORBX_E_NO_DEVICE, "hipMalloc failed"));
+        return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipMalloc failed"));
     if (hipMemcpy(c->d_umax, c->u_max, sizeof(int) * 16, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->d_taps, c->taps, sizeof(int) * 7, hipMemcpyHostToDevice) != hipSuccess)
-        return cleanup(fail(ORBX_E_NO_DEVICE, "hipMemcpy failed"));
+        return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipMemcpy failed"));
     if (cfg->max_width > 0 && cfg->max_height > 0) {
         int rc = ensure_geometry(c, cfg->max_width, cfg->max_height, c->cfg.max_batch, 0);
         if (rc) return cleanup(rc);
@@ -549,7 +522,7 @@ extern "C" int orbx_create(const orbx_cfg *cfg, orbx_t **out) { return create_co
 extern "C" int orbx_create_requota(const orbx_t *other, int n_features, orbx_t **out)
 {
     // reference ORBExtractor.cpp:477-493: same pyramid and thresholds, new quotas
-    if (!other) return fail(ORBX_E_ARG, "null argument");
+    if (!other) return orbx_set_error(ORBX_E_ARG, "null argument");
     orbx_cfg cfg = other->cfg;
     cfg.n_features = n_features;
     int rc = create_common(&cfg, nullptr, out);
@@ -564,8 +537,7 @@ extern "C" int orbx_create_requota(const orbx_t *other, int n_features, orbx_t *
 extern "C" void orbx_destroy(orbx_t *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)sync_handle(c);
+    c->hs.destroy();
     OrbxBuffers &b = c->buf;
     void *ptrs[] = {b.img_arena, b.cand, b.pnode, b.pcode, b.cand_count, b.bnd0, b.bnd1, b.cnt0, b.cnt1, b.rank, b.node_of_rank,
                     b.newpos, b.childcnt, b.childpos, b.best, b.sel, b.kp_ang, b.sel_count, b.sel_prefix, c->d_slot_level, c->d_levels, c->d_umax, c->d_taps,
@@ -592,14 +564,13 @@ extern "C" void orbx_destroy(orbx_t *c)
         if (c->ev_start[i]) (void)hipEventDestroy(c->ev_start[i]);
         if (c->ev_fast0[i]) (void)hipEventDestroy(c->ev_fast0[i]);
     }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
 extern "C" int orbx_tables(const orbx_t *c, int *n_levels, float *sf, float *isf, float *ss, float *iss, float *lsf,
                            int32_t *quotas, int32_t *u_max16)
 {
-    if (!c) return fail(ORBX_E_ARG, "null handle");
+    if (!c) return orbx_set_error(ORBX_E_ARG, "null handle");
     const int L = c->cfg.n_levels;
     if (n_levels) *n_levels = L;
     if (sf) memcpy(sf, c->scale_factors, sizeof(float) * L);
@@ -614,14 +585,14 @@ extern "C" int orbx_tables(const orbx_t *c, int *n_levels, float *sf, float *isf
 
 extern "C" int orbx_level_size(const orbx_t *c, int w0, int h0, int level, int *w, int *h)
 {
-    if (!c || level < 0 || level >= c->cfg.n_levels || !w || !h) return fail(ORBX_E_ARG, "bad argument");
+    if (!c || level < 0 || level >= c->cfg.n_levels || !w || !h) return orbx_set_error(ORBX_E_ARG, "bad argument");
     level_size(c, w0, h0, level, w, h);
     return ORBX_OK;
 }
 
 extern "C" int orbx_max_keypoints(const orbx_t *c, int w0, int h0)
 {
-    if (!c) return fail(ORBX_E_ARG, "null handle");
+    if (!c) return orbx_set_error(ORBX_E_ARG, "null handle");
     if (w0 == c->cur_w && h0 == c->cur_h) return c->levels.kcap_total;
     Geometry g;
     int rc = compute_geometry(c, w0, h0, &g);
@@ -632,17 +603,6 @@ extern "C" int orbx_max_keypoints(const orbx_t *c, int w0, int h0)
 // ------------------------------------------------------------------------------------------------
 // the pipeline
 // ------------------------------------------------------------------------------------------------
-struct PhaseTrace { // ORBX_TRACE=1: host time stamps of the phases of orbx_extract_batch on stderr
-    bool on; std::chrono::steady_clock::time_point t0;
-    PhaseTrace() : on(getenv("ORBX_TRACE") != nullptr), t0(std::chrono::steady_clock::now()) {}
-    void mark(const char *what) {
-        if (!on) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[orbx] %-24s %8.1f us\n", what, std::chrono::duration<double, std::micro>(t - t0).count());
-        t0 = t;
-    }
-};
-
 // the same arenas, seen from frame f0 on
 static OrbxBuffers offset_buffers(const OrbxBuffers &a, int f0, int kcap_total)
 {
@@ -678,7 +638,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     const OrbxBuffers b = offset_buffers(c->buf, f0, LV.kcap_total);
     d_l0 += (size_t)f0 * l0_fs;
     d_kp += (size_t)f0 * cap; d_desc += (size_t)f0 * cap * 32; d_n += f0;
-    if (t) HIP_TRY(hipEventRecord(c->ev[0], s));
+    if (t) ORB_TRY(hipEventRecord(c->ev[0], s));
     auto raw = [&](int l, const uint8_t **p, size_t *fs, int *pitch) {
         if (l == 0) { *p = d_l0; *fs = l0_fs; *pitch = l0_pitch; }
         else { *p = b.img_arena + LV.lv[l].raw_off; *fs = b.img_frame_stride; *pitch = LV.lv[l].pitch; }
@@ -778,7 +738,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     // the candidate counters are cleared by the first pyramid launch (one stream operation less ahead of every batch) unless
     // FAST starts before or without it: level 0's early launch, or a one-level pyramid
     const bool zero_in_resize = !split && !early && L > 1;
-    if (!split && !zero_in_resize) HIP_TRY(hipMemsetAsync(b.cand_count, 0, sizeof(int) * ORBX_MAX_LEVELS * n_frames, s));
+    if (!split && !zero_in_resize) ORB_TRY(hipMemsetAsync(b.cand_count, 0, sizeof(int) * ORBX_MAX_LEVELS * n_frames, s));
     if (split) {
         // The host needs 2-3 us per launch, about what a small resize takes on the device: the chain the call waits for
         // (resize x7 -> FAST -> quadtree of levels 1..) is issued first and back to back, the two side chains (level 0;
@@ -796,10 +756,10 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         // From a megapixel on the side chain is therefore ISSUED as soon as its inputs exist, ahead of the remaining resizes.
         const bool side_first = (size_t)LV.lv[0].w * (size_t)LV.lv[0].h >= (size_t)ORBX_SIDE_FIRST_PIXELS;
         auto launch_side = [&]() -> int {
-            HIP_TRY(hipStreamWaitEvent(c->side[slot], c->ev_start[slot], 0));
+            ORB_TRY(hipStreamWaitEvent(c->side[slot], c->ev_start[slot], 0));
             launch_fast(c->side[slot], d_units, cells_before[G]);
             orbx_launch_octree(c->side[slot], c->d_levels, LV, b, n_frames, c->sort_lds_bytes, 0, G, c->n_cus);
-            HIP_TRY(hipEventRecord(c->ev_fast0[slot], c->side[slot]));
+            ORB_TRY(hipEventRecord(c->ev_fast0[slot], c->side[slot]));
             return ORBX_OK;
         };
         bool started = false;
@@ -807,29 +767,29 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
             // the first launch also clears the candidate counters
             const int done = launch_resize(s, l, l == 1 ? b.cand_count : nullptr); // last level this launch produced
             if (!started && done >= std::max(G - 1, 1)) { // counters are zero, levels < G exist
-                HIP_TRY(hipEventRecord(c->ev_start[slot], s));
+                ORB_TRY(hipEventRecord(c->ev_start[slot], s));
                 started = true;
                 if (side_first) { int rc = launch_side(); if (rc) return rc; }
             }
             l = done + 1;
         }
-        HIP_TRY(hipEventRecord(c->ev_pyr[bslot], s));
+        ORB_TRY(hipEventRecord(c->ev_pyr[bslot], s));
         if (cells_before[L] > cells_before[G]) launch_fast(s, d_units + 4 * cells_before[G], cells_before[L] - cells_before[G]);
         orbx_launch_octree(s, c->d_levels, LV, b, n_frames, c->sort_lds_bytes, G, L, c->n_cus);
         if (!side_first) { int rc = launch_side(); if (rc) return rc; }
-        HIP_TRY(hipStreamWaitEvent(c->side[bslot], c->ev_pyr[bslot], 0));
+        ORB_TRY(hipStreamWaitEvent(c->side[bslot], c->ev_pyr[bslot], 0));
         launch_blur(c->side[bslot], 0, L);
-        HIP_TRY(hipEventRecord(c->ev_blur[bslot], c->side[bslot]));
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_fast0[slot], 0));
+        ORB_TRY(hipEventRecord(c->ev_blur[bslot], c->side[bslot]));
+        ORB_TRY(hipStreamWaitEvent(s, c->ev_fast0[slot], 0));
         launch_desc(c->ev_blur[bslot]);
-        HIP_TRY(hipGetLastError());
+        ORB_TRY(hipGetLastError());
         return ORBX_OK;
     }
     if (early) {
-        HIP_TRY(hipEventRecord(c->ev_start[slot], s)); // candidate counters are zero from here on
-        HIP_TRY(hipStreamWaitEvent(c->side[slot], c->ev_start[slot], 0));
+        ORB_TRY(hipEventRecord(c->ev_start[slot], s)); // candidate counters are zero from here on
+        ORB_TRY(hipStreamWaitEvent(c->side[slot], c->ev_start[slot], 0));
         launch_fast(c->side[slot], d_units, n_cells0);
-        HIP_TRY(hipEventRecord(c->ev_fast0[slot], c->side[slot]));
+        ORB_TRY(hipEventRecord(c->ev_fast0[slot], c->side[slot]));
         if (early_fast > 1) // level 0 needs no pyramid for its blur either
             launch_blur(c->side[slot], 0, 1);
     }
@@ -840,42 +800,42 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         InStep rt(c, ORBX_STAGE_RESIZE, s);
         for (int l = 1; l < L;) l = launch_resize(s, l, l == 1 && zero_in_resize ? b.cand_count : nullptr) + 1;
     }
-    if (t) HIP_TRY(hipEventRecord(c->ev[1], s));
+    if (t) ORB_TRY(hipEventRecord(c->ev[1], s));
     // (nothing to fork when k_blur_desc describes every level: no blur pass, and no event pair in the stream between the pyramid and FAST)
     const bool side = !t && c->side_blur && slot >= 0 && fl < L;
     auto fork_blur = [&]() -> int { // the blur only needs the pyramid: side stream, joined before the descriptor kernel
-        HIP_TRY(hipEventRecord(c->ev_pyr[bslot], s));
-        HIP_TRY(hipStreamWaitEvent(c->side[bslot], c->ev_pyr[bslot], 0));
+        ORB_TRY(hipEventRecord(c->ev_pyr[bslot], s));
+        ORB_TRY(hipStreamWaitEvent(c->side[bslot], c->ev_pyr[bslot], 0));
         launch_blur(c->side[bslot], (early && early_fast > 1) ? 1 : 0, L);
-        HIP_TRY(hipEventRecord(c->ev_blur[bslot], c->side[bslot]));
+        ORB_TRY(hipEventRecord(c->ev_blur[bslot], c->side[bslot]));
         return ORBX_OK;
     };
     if (side && c->side_blur == 1) { int rc = fork_blur(); if (rc) return rc; } // next to FAST
     if (early) {
         launch_fast(s, d_units + 4 * n_cells0, n_units - n_cells0);
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_fast0[slot], 0));
+        ORB_TRY(hipStreamWaitEvent(s, c->ev_fast0[slot], 0));
     } else {
         launch_fast(s, d_units, n_units);
     }
-    if (t) HIP_TRY(hipEventRecord(c->ev[2], s));
+    if (t) ORB_TRY(hipEventRecord(c->ev[2], s));
     if (slot == 8) { // (a batch split over sub-streams records the event once, behind the join of all of them: enqueue_batch)
-        if (!c->ev_after_fast) HIP_TRY(hipEventCreateWithFlags(&c->ev_after_fast, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_after_fast, s)); // what follows (quadtree, orientation) leaves the vector ALUs mostly idle
+        if (!c->ev_after_fast) ORB_TRY(hipEventCreateWithFlags(&c->ev_after_fast, hipEventDisableTiming));
+        ORB_TRY(hipEventRecord(c->ev_after_fast, s)); // what follows (quadtree, orientation) leaves the vector ALUs mostly idle
         c->after_fast_valid = true;
     }
     if (side && c->side_blur == 2) { int rc = fork_blur(); if (rc) return rc; } // next to the quadtree and orientation
     if (!side)
         launch_blur(s, 0, L);
-    if (t) HIP_TRY(hipEventRecord(c->ev[3], s));
+    if (t) ORB_TRY(hipEventRecord(c->ev[3], s));
     {
         InStep ot(c, ORBX_STAGE_OCTREE, s);
         orbx_launch_octree(s, c->d_levels, LV, b, n_frames, c->sort_lds_bytes, 0, L, c->n_cus);
     }
-    if (t) HIP_TRY(hipEventRecord(c->ev[4], s));
+    if (t) ORB_TRY(hipEventRecord(c->ev[4], s));
     if (side && c->side_blur >= 3) { int rc = fork_blur(); if (rc) return rc; } // next to the orientation only
     launch_desc(side ? c->ev_blur[bslot] : nullptr); // (records ev[5] between orientation and descriptors when timed)
-    if (t) { HIP_TRY(hipEventRecord(c->ev[ORBX_N_STAGES], s)); c->ev_valid = true; }
-    HIP_TRY(hipGetLastError());
+    if (t) { ORB_TRY(hipEventRecord(c->ev[ORBX_N_STAGES], s)); c->ev_valid = true; }
+    ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -888,19 +848,19 @@ static int enqueue_batch(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t
     for (int i = 0; i < ORBX_N_STAGES; ++i) c->ev_in_n[i] = 0;
     const int ns = c->timing == 1 ? 1 : std::min(c->n_sub, n_frames / 8);
     if (ns <= 1) return enqueue(c, s, d_l0, l0_fs, l0_pitch, 0, n_frames, d_kp, d_desc, cap, d_n, c->timing == 1, 8, latency);
-    HIP_TRY(hipEventRecord(c->ev_fork, s));
+    ORB_TRY(hipEventRecord(c->ev_fork, s));
     for (int i = 0; i < ns; ++i) {
         const int f0 = (int)((long long)n_frames * i / ns), f1 = (int)((long long)n_frames * (i + 1) / ns);
-        HIP_TRY(hipStreamWaitEvent(c->sub[i], c->ev_fork, 0));
+        ORB_TRY(hipStreamWaitEvent(c->sub[i], c->ev_fork, 0));
         int rc = enqueue(c, c->sub[i], d_l0, l0_fs, l0_pitch, f0, f1 - f0, d_kp, d_desc, cap, d_n, false, i, false);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(c->ev_join[i], c->sub[i]));
-        HIP_TRY(hipStreamWaitEvent(s, c->ev_join[i], 0));
+        ORB_TRY(hipEventRecord(c->ev_join[i], c->sub[i]));
+        ORB_TRY(hipStreamWaitEvent(s, c->ev_join[i], 0));
     }
     // orbx_stream_wait_fast must cover EVERY frame range: with the batch split, the event sits behind the join of all
     // sub-streams (conservative: the whole extraction, not only its FAST stages)
-    if (!c->ev_after_fast) HIP_TRY(hipEventCreateWithFlags(&c->ev_after_fast, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c->ev_after_fast, s));
+    if (!c->ev_after_fast) ORB_TRY(hipEventCreateWithFlags(&c->ev_after_fast, hipEventDisableTiming));
+    ORB_TRY(hipEventRecord(c->ev_after_fast, s));
     c->after_fast_valid = true;
     return ORBX_OK;
 }
@@ -909,31 +869,30 @@ extern "C" int orbx_extract_batch_device(orbx_t *c, const uint8_t *d_imgs, int n
                                          int stride, size_t frame_stride, orbx_kp *d_kp, uint8_t *d_desc, int cap,
                                          int32_t *d_n, void *stream)
 {
-    if (!c || !d_imgs || !d_kp || !d_desc || !d_n) return fail(ORBX_E_ARG, "null argument");
-    if (n_frames < 1 || width < 1 || height < 1 || stride < width || cap < 1) return fail(ORBX_E_ARG, "bad size");
+    if (!c || !d_imgs || !d_kp || !d_desc || !d_n) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (n_frames < 1 || width < 1 || height < 1 || stride < width || cap < 1) return orbx_set_error(ORBX_E_ARG, "bad size");
     int rc = ensure_geometry(c, width, height, n_frames, 0);
     if (rc) return rc;
-    // a NULL stream argument is stream 0 itself (include/orbx.h, "Streams"); the handle remembers it for its host-side waits
-    if (!stream) c->null_pending = true;
+    ORB_TRY(c->hs.device_call((hipStream_t)stream));
     return enqueue_batch(c, (hipStream_t)stream, d_imgs, frame_stride, stride, n_frames, d_kp,
                          d_desc, cap, d_n, false);
 }
 
 extern "C" int orbx_synchronize(orbx_t *c)
 {
-    if (!c) return fail(ORBX_E_ARG, "null handle");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(sync_handle(c));
+    if (!c) return orbx_set_error(ORBX_E_ARG, "null handle");
+    ORB_TRY(c->hs.host_call());
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
     return ORBX_OK;
 }
 
 extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, int width, int height, int stride,
                                   size_t frame_stride, orbx_kp *out_kp, uint8_t *out_desc, int cap, int32_t *n_out)
 {
-    if (!c || !n_out) return fail(ORBX_E_ARG, "null argument");
+    if (!c || !n_out) return orbx_set_error(ORBX_E_ARG, "null argument");
     for (int f = 0; f < n_frames; ++f) n_out[f] = 0;
     if (!imgs || width <= 0 || height <= 0) return ORBX_OK; // reference :497 -- empty image: silent no-op
-    if (n_frames < 1 || stride < width || cap < 1 || !out_kp || !out_desc) return fail(ORBX_E_ARG, "bad argument");
+    if (n_frames < 1 || stride < width || cap < 1 || !out_kp || !out_desc) return orbx_set_error(ORBX_E_ARG, "bad argument");
     int rc, dcap; // device-side staging holds every possible keypoint
     if (width == c->cur_w && height == c->cur_h) {
         dcap = c->levels.kcap_total;
@@ -946,10 +905,10 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
     rc = ensure_geometry(c, width, height, n_frames, dcap);
     if (rc) return rc;
     // a NULL-stream device call of this handle may still be in flight on the pyramid and scratch this call is about to use
-    if (c->null_pending) { HIP_TRY(hipStreamSynchronize((hipStream_t)0)); c->null_pending = false; }
+    ORB_TRY(c->hs.host_call());
     const int scap = c->alloc_out_cap;
-    hipStream_t s = c->stream;
-    PhaseTrace tr;
+    hipStream_t s = c->hs.stream;
+    PhaseTrace tr("orbx", "ORBX_TRACE"); // host time stamps of the phases on stderr
     // Level 0 goes to HBM as it is laid out on the host: dense rows (stride == width, the cv::Mat::clone() case of
     // Frame.cpp:17) are ONE linear copy (a pitched 2-D copy from pageable memory costs milliseconds); the kernels
     // accept any level-0 pitch.  Only a genuinely strided input takes the 2-D copy.
@@ -959,14 +918,14 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
         l0_pitch = width;
         l0_fs = (size_t)width * height;
         if (frame_stride == l0_fs)
-            HIP_TRY(hipMemcpyAsync(c->d_l0_stage, imgs, l0_fs * n_frames, hipMemcpyHostToDevice, s));
+            ORB_TRY(hipMemcpyAsync(c->d_l0_stage, imgs, l0_fs * n_frames, hipMemcpyHostToDevice, s));
         else
             for (int f = 0; f < n_frames; ++f)
-                HIP_TRY(hipMemcpyAsync(c->d_l0_stage + (size_t)f * l0_fs, imgs + (size_t)f * frame_stride, l0_fs,
+                ORB_TRY(hipMemcpyAsync(c->d_l0_stage + (size_t)f * l0_fs, imgs + (size_t)f * frame_stride, l0_fs,
                                        hipMemcpyHostToDevice, s));
     } else {
         for (int f = 0; f < n_frames; ++f)
-            HIP_TRY(hipMemcpy2DAsync(c->d_l0_stage + (size_t)f * l0_fs, l0_pitch, imgs + (size_t)f * frame_stride, stride,
+            ORB_TRY(hipMemcpy2DAsync(c->d_l0_stage + (size_t)f * l0_fs, l0_pitch, imgs + (size_t)f * frame_stride, stride,
                                      width, height, hipMemcpyHostToDevice, s));
     }
     tr.mark("copy-in call");
@@ -975,12 +934,12 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
         // the block was laid out for), one wait, and the live records go to the caller's buffers from pinned memory
         const size_t nb = (size_t)n_frames;
         if (n_frames == c->alloc_batch) {
-            HIP_TRY(hipMemcpyAsync(c->h_out_block, c->d_out_block, c->out_block_bytes, hipMemcpyDeviceToHost, s));
+            ORB_TRY(hipMemcpyAsync(c->h_out_block, c->d_out_block, c->out_block_bytes, hipMemcpyDeviceToHost, s));
         } else {
-            HIP_TRY(hipMemcpyAsync(c->h_out_block, c->d_out_block, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(c->h_out_block + c->out_kp_off, c->d_out_block + c->out_kp_off, nb * scap * sizeof(orbx_kp),
+            ORB_TRY(hipMemcpyAsync(c->h_out_block, c->d_out_block, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            ORB_TRY(hipMemcpyAsync(c->h_out_block + c->out_kp_off, c->d_out_block + c->out_kp_off, nb * scap * sizeof(orbx_kp),
                                    hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(c->h_out_block + c->out_desc_off, c->d_out_block + c->out_desc_off, nb * scap * 32,
+            ORB_TRY(hipMemcpyAsync(c->h_out_block + c->out_desc_off, c->d_out_block + c->out_desc_off, nb * scap * 32,
                                    hipMemcpyDeviceToHost, s));
         }
         return ORBX_OK;
@@ -999,7 +958,7 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
     tr.mark("kernel launches");
     int status = ORBX_OK;
     if (c->h_out_block) {
-        HIP_TRY(hipStreamSynchronize(s));
+        ORB_TRY(hipStreamSynchronize(s));
         tr.mark("device + records");
         const int32_t *counts = reinterpret_cast<const int32_t *>(c->h_out_block);
         for (int f = 0; f < n_frames; ++f) {
@@ -1012,23 +971,23 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
         }
     } else {
         std::vector<int32_t> counts(n_frames);
-        HIP_TRY(hipMemcpyAsync(counts.data(), c->d_out_n, sizeof(int32_t) * n_frames, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        ORB_TRY(hipMemcpyAsync(counts.data(), c->d_out_n, sizeof(int32_t) * n_frames, hipMemcpyDeviceToHost, s));
+        ORB_TRY(hipStreamSynchronize(s));
         tr.mark("device + counts");
         for (int f = 0; f < n_frames; ++f) {
             const int n = counts[f];
             n_out[f] = n;
             if (n == 0) continue; // reference :512 -- outputs untouched
             if (n > cap) { status = ORBX_E_CAPACITY; continue; }
-            HIP_TRY(hipMemcpyAsync(out_kp + (size_t)f * cap, c->d_out_kp + (size_t)f * scap, sizeof(orbx_kp) * n,
+            ORB_TRY(hipMemcpyAsync(out_kp + (size_t)f * cap, c->d_out_kp + (size_t)f * scap, sizeof(orbx_kp) * n,
                                    hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(out_desc + (size_t)f * cap * 32, c->d_out_desc + (size_t)f * scap * 32, (size_t)n * 32,
+            ORB_TRY(hipMemcpyAsync(out_desc + (size_t)f * cap * 32, c->d_out_desc + (size_t)f * scap * 32, (size_t)n * 32,
                                    hipMemcpyDeviceToHost, s));
         }
-        HIP_TRY(hipStreamSynchronize(s));
+        ORB_TRY(hipStreamSynchronize(s));
     }
     tr.mark("records out");
-    if (status == ORBX_E_CAPACITY) return fail(status, "output capacity too small");
+    if (status == ORBX_E_CAPACITY) return orbx_set_error(status, "output capacity too small");
     return ORBX_OK;
 }
 
@@ -1047,47 +1006,47 @@ extern "C" int orbx_extract(orbx_t *c, const uint8_t *img, int width, int height
 // ------------------------------------------------------------------------------------------------
 extern "C" int orbx_tap_level(orbx_t *c, int frame, int level, int blurred, uint8_t *out, size_t out_bytes)
 {
-    if (!c || !out || c->cur_w < 0 || !c->last_l0) return fail(ORBX_E_ARG, "no extract call yet");
+    if (!c || !out || c->cur_w < 0 || !c->last_l0) return orbx_set_error(ORBX_E_ARG, "no extract call yet");
     if (frame < 0 || frame >= c->last_frames || level < 0 || level >= c->levels.n_levels)
-        return fail(ORBX_E_ARG, "frame/level out of range");
+        return orbx_set_error(ORBX_E_ARG, "frame/level out of range");
     const OrbxLevel &v = c->levels.lv[level];
-    if (out_bytes < (size_t)v.w * v.h) return fail(ORBX_E_CAPACITY, "buffer too small");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(sync_handle(c));
+    if (out_bytes < (size_t)v.w * v.h) return orbx_set_error(ORBX_E_CAPACITY, "buffer too small");
+    ORB_TRY(c->hs.host_call());
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
     if (blurred && level < c->last_fused_levels) {
         // the last call described this level with k_blur_desc, which keeps the blurred rows in LDS only: the blur pass makes
         // the copy now (all frames of the call, so that later taps find it), on the raw level that is still in place
         if (level < c->blur_mfma_levels)
-            orbx_launch_blur_mfma(c->stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->levels, c->buf, c->blur_tab, c->d_blur_strips,
+            orbx_launch_blur_mfma(c->hs.stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->levels, c->buf, c->blur_tab, c->d_blur_strips,
                                   c->blur_strips_before, c->d_band_h, c->d_band_v, c->taps, c->last_frames, level, level + 1);
         else
-            orbx_launch_blur(c->stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->d_levels, c->levels, c->buf, c->d_blur_tiles,
+            orbx_launch_blur(c->hs.stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->d_levels, c->levels, c->buf, c->d_blur_tiles,
                              c->n_blur_tiles, c->d_taps, c->last_frames, level, level + 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
+        ORB_TRY(hipGetLastError());
+        ORB_TRY(hipStreamSynchronize(c->hs.stream));
     }
     const uint8_t *src; size_t pitch;
     if (blurred) { src = c->buf.img_arena + (size_t)frame * c->buf.img_frame_stride + v.blur_off; pitch = v.pitch; }
     else if (level == 0) { src = c->last_l0 + (size_t)frame * c->last_l0_fs; pitch = c->last_l0_pitch; }
     else { src = c->buf.img_arena + (size_t)frame * c->buf.img_frame_stride + v.raw_off; pitch = v.pitch; }
-    HIP_TRY(hipMemcpy2D(out, v.w, src, pitch, v.w, v.h, hipMemcpyDeviceToHost));
+    ORB_TRY(hipMemcpy2D(out, v.w, src, pitch, v.w, v.h, hipMemcpyDeviceToHost));
     return ORBX_OK;
 }
 
 extern "C" int orbx_tap_candidates(orbx_t *c, int frame, int level, uint16_t *xs, uint16_t *ys, uint8_t *resp, int cap,
                                    int *n_out)
 {
-    if (!c || !n_out || c->cur_w < 0 || !c->last_l0) return fail(ORBX_E_ARG, "no extract call yet");
+    if (!c || !n_out || c->cur_w < 0 || !c->last_l0) return orbx_set_error(ORBX_E_ARG, "no extract call yet");
     if (frame < 0 || frame >= c->last_frames || level < 0 || level >= c->levels.n_levels)
-        return fail(ORBX_E_ARG, "frame/level out of range");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(sync_handle(c));
+        return orbx_set_error(ORBX_E_ARG, "frame/level out of range");
+    ORB_TRY(c->hs.host_call());
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
     int n = 0;
-    HIP_TRY(hipMemcpy(&n, c->buf.cand_count + frame * ORBX_MAX_LEVELS + level, sizeof(int), hipMemcpyDeviceToHost));
+    ORB_TRY(hipMemcpy(&n, c->buf.cand_count + frame * ORBX_MAX_LEVELS + level, sizeof(int), hipMemcpyDeviceToHost));
     *n_out = n;
-    if (n > cap) return fail(ORBX_E_CAPACITY, "buffer too small");
+    if (n > cap) return orbx_set_error(ORBX_E_CAPACITY, "buffer too small");
     std::vector<unsigned long long> tmp(std::max(n, 1));
-    HIP_TRY(hipMemcpy(tmp.data(), c->buf.cand + (size_t)frame * c->buf.cand_frame_stride + c->levels.lv[level].cand_off,
+    ORB_TRY(hipMemcpy(tmp.data(), c->buf.cand + (size_t)frame * c->buf.cand_frame_stride + c->levels.lv[level].cand_off,
                       sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) {
         if (xs) xs[i] = (uint16_t)(tmp[i] & 0xFFFF);
@@ -1099,11 +1058,11 @@ extern "C" int orbx_tap_candidates(orbx_t *c, int frame, int level, uint16_t *xs
 
 extern "C" int orbx_tap_level_counts(orbx_t *c, int frame, int32_t *counts)
 {
-    if (!c || !counts || c->cur_w < 0 || !c->last_l0) return fail(ORBX_E_ARG, "no extract call yet");
-    if (frame < 0 || frame >= c->last_frames) return fail(ORBX_E_ARG, "frame out of range");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(sync_handle(c));
-    HIP_TRY(hipMemcpy(counts, c->buf.sel_count + frame * ORBX_MAX_LEVELS, sizeof(int) * c->levels.n_levels,
+    if (!c || !counts || c->cur_w < 0 || !c->last_l0) return orbx_set_error(ORBX_E_ARG, "no extract call yet");
+    if (frame < 0 || frame >= c->last_frames) return orbx_set_error(ORBX_E_ARG, "frame out of range");
+    ORB_TRY(c->hs.host_call());
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
+    ORB_TRY(hipMemcpy(counts, c->buf.sel_count + frame * ORBX_MAX_LEVELS, sizeof(int) * c->levels.n_levels,
                       hipMemcpyDeviceToHost));
     return ORBX_OK;
 }
@@ -1111,63 +1070,63 @@ extern "C" int orbx_tap_level_counts(orbx_t *c, int frame, int32_t *counts)
 void launch_tap_sincos(const float *d_ang, int n, float2 *d_out, hipStream_t st);
 extern "C" int orbx_tap_sincos(orbx_t *c, const float *angles_deg, int n, float *cos_sin)
 {
-    if (!c || !angles_deg || !cos_sin || n < 0) return fail(ORBX_E_ARG, "bad argument");
+    if (!c || !angles_deg || !cos_sin || n < 0) return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (n == 0) return ORBX_OK;
-    HIP_TRY(hipSetDevice(c->device));
+    ORB_TRY(hipSetDevice(c->hs.device));
     float *d_in = nullptr;
     float2 *d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_in, sizeof(float) * (size_t)n));
+    ORB_TRY(hipMalloc(&d_in, sizeof(float) * (size_t)n));
     hipError_t e = hipMalloc(&d_out, sizeof(float2) * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, angles_deg, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, angles_deg, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->hs.stream);
     if (e == hipSuccess) {
-        launch_tap_sincos(d_in, n, d_out, c->stream);
+        launch_tap_sincos(d_in, n, d_out, c->hs.stream);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(cos_sin, d_out, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(cos_sin, d_out, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->hs.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->hs.stream);
     (void)hipFree(d_in);
     (void)hipFree(d_out);
-    HIP_TRY(e);
+    ORB_TRY(e);
     return ORBX_OK;
 }
 
 extern "C" int orbx_set_stage_timing(orbx_t *c, int enable)
 {
-    if (!c) return fail(ORBX_E_ARG, "null handle");
+    if (!c) return orbx_set_error(ORBX_E_ARG, "null handle");
     c->timing = enable;
     c->ev_valid = false;
     for (int i = 0; i < ORBX_N_STAGES; ++i) c->ev_in_n[i] = 0;
     if (enable == 2 && !c->ev_in[0][0]) {
-        HIP_TRY(hipSetDevice(c->device));
+        ORB_TRY(hipSetDevice(c->hs.device));
         for (int st = ORBX_N_STAGES - 1; st >= 0; --st) // [0][0] last: it marks the set as complete
-            for (int i = 3; i >= 0; --i) HIP_TRY(hipEventCreate(&c->ev_in[st][i]));
+            for (int i = 3; i >= 0; --i) ORB_TRY(hipEventCreate(&c->ev_in[st][i]));
     }
     return ORBX_OK;
 }
 
 extern "C" int orbx_stream_wait_fast(orbx_t *c, void *stream)
 {
-    if (!c || !stream) return fail(ORBX_E_ARG, "null argument");
-    if (!c->after_fast_valid) return fail(ORBX_E_ARG, "no batched extract call enqueued yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, c->ev_after_fast, 0));
+    if (!c || !stream) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (!c->after_fast_valid) return orbx_set_error(ORBX_E_ARG, "no batched extract call enqueued yet");
+    ORB_TRY(hipSetDevice(c->hs.device));
+    ORB_TRY(hipStreamWaitEvent((hipStream_t)stream, c->ev_after_fast, 0));
     return ORBX_OK;
 }
 
 extern "C" int orbx_stage_times_in_step_ms(orbx_t *c, float *ms)
 {
-    if (!c || !ms) return fail(ORBX_E_ARG, "null argument");
-    if (c->timing != 2 || c->ev_in_n[ORBX_STAGE_FAST] < 1) return fail(ORBX_E_ARG, "no extract call in timing mode 2 yet");
+    if (!c || !ms) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (c->timing != 2 || c->ev_in_n[ORBX_STAGE_FAST] < 1) return orbx_set_error(ORBX_E_ARG, "no extract call in timing mode 2 yet");
     // a batch split over internal streams re-records the same events once per frame range: only the last range would be timed
-    if (c->n_sub > 1) return fail(ORBX_E_UNSUPPORTED, "in-step stage times need ORBX_VAR_STREAMS = 1");
-    HIP_TRY(hipSetDevice(c->device));
+    if (c->n_sub > 1) return orbx_set_error(ORBX_E_UNSUPPORTED, "in-step stage times need ORBX_VAR_STREAMS = 1");
+    ORB_TRY(hipSetDevice(c->hs.device));
     for (int st = 0; st < ORBX_N_STAGES; ++st) {
         ms[st] = 0.f;
         for (int i = 0; i < c->ev_in_n[st]; ++i) {
             float t = 0.f;
             hipEvent_t e0 = c->ev_in[st][2 * i];
-            HIP_TRY(hipEventSynchronize(c->ev_in[st][2 * i + 1]));
-            HIP_TRY(hipEventElapsedTime(&t, e0, c->ev_in[st][2 * i + 1]));
+            ORB_TRY(hipEventSynchronize(c->ev_in[st][2 * i + 1]));
+            ORB_TRY(hipEventElapsedTime(&t, e0, c->ev_in[st][2 * i + 1]));
             ms[st] += t;
         }
     }
@@ -1176,7 +1135,7 @@ extern "C" int orbx_stage_times_in_step_ms(orbx_t *c, float *ms)
 
 extern "C" int orbx_fast_times_in_step_ms(orbx_t *c, float *ms_sum, int *n_launches)
 {
-    if (!c || !ms_sum) return fail(ORBX_E_ARG, "null argument");
+    if (!c || !ms_sum) return orbx_set_error(ORBX_E_ARG, "null argument");
     float ms[ORBX_N_STAGES];
     int rc = orbx_stage_times_in_step_ms(c, ms);
     if (rc) return rc;
@@ -1187,11 +1146,11 @@ extern "C" int orbx_fast_times_in_step_ms(orbx_t *c, float *ms_sum, int *n_launc
 
 extern "C" int orbx_stage_times_ms(orbx_t *c, float *ms)
 {
-    if (!c || !ms) return fail(ORBX_E_ARG, "null argument");
-    if (!c->ev_valid) return fail(ORBX_E_ARG, "no timed extract call yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev[ORBX_N_STAGES]));
-    for (int i = 0; i < ORBX_N_STAGES; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
+    if (!c || !ms) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (!c->ev_valid) return orbx_set_error(ORBX_E_ARG, "no timed extract call yet");
+    ORB_TRY(hipSetDevice(c->hs.device));
+    ORB_TRY(hipEventSynchronize(c->ev[ORBX_N_STAGES]));
+    for (int i = 0; i < ORBX_N_STAGES; ++i) ORB_TRY(hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
     return ORBX_OK;
 }
 
@@ -1215,41 +1174,41 @@ static int *variant_field(orbx_ctx *c, int which, int *lo, int *hi)
 
 extern "C" int orbx_set_variant(orbx_t *c, int which, int value)
 {
-    if (!c) return fail(ORBX_E_ARG, "null handle");
+    if (!c) return orbx_set_error(ORBX_E_ARG, "null handle");
     int lo, hi;
     int *f = variant_field(c, which, &lo, &hi);
-    if (!f) return fail(ORBX_E_ARG, "unknown variant switch");
-    if (value < lo || value > hi) return fail(ORBX_E_ARG, "variant value out of range");
+    if (!f) return orbx_set_error(ORBX_E_ARG, "unknown variant switch");
+    if (value < lo || value > hi) return orbx_set_error(ORBX_E_ARG, "variant value out of range");
     // only the instantiated group sizes (orbx_get_variant must report what runs, not a value the launcher rounds down)
     if (which == ORBX_VAR_FAST_CELL_GROUP && value != 1 && value != 4 && value != 8 && value != 16)
-        return fail(ORBX_E_ARG, "FAST cell group must be 1, 4, 8 or 16");
+        return orbx_set_error(ORBX_E_ARG, "FAST cell group must be 1, 4, 8 or 16");
     // the first level of the main chain lies inside the pyramid: 0 (one chain) .. n_levels - 1
     if (which == ORBX_VAR_SPLIT_LEVEL0 && value > c->cfg.n_levels - 1)
-        return fail(ORBX_E_ARG, "split level must be below the handle's n_levels");
+        return orbx_set_error(ORBX_E_ARG, "split level must be below the handle's n_levels");
     *f = value;
     return ORBX_OK;
 }
 
 extern "C" int orbx_get_variant(const orbx_t *c, int which, int *value)
 {
-    if (!c || !value) return fail(ORBX_E_ARG, "null argument");
+    if (!c || !value) return orbx_set_error(ORBX_E_ARG, "null argument");
     int lo, hi;
     int *f = variant_field(const_cast<orbx_ctx *>(c), which, &lo, &hi);
-    if (!f) return fail(ORBX_E_ARG, "unknown variant switch");
+    if (!f) return orbx_set_error(ORBX_E_ARG, "unknown variant switch");
     *value = *f;
     return ORBX_OK;
 }
 
 extern "C" int orbx_host_register(void *ptr, size_t bytes)
 {
-    if (!ptr || !bytes) return fail(ORBX_E_ARG, "null argument");
-    HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
+    if (!ptr || !bytes) return orbx_set_error(ORBX_E_ARG, "null argument");
+    ORB_TRY(hipHostRegister(ptr, bytes, hipHostRegisterDefault));
     return ORBX_OK;
 }
 extern "C" int orbx_host_unregister(void *ptr)
 {
-    if (!ptr) return fail(ORBX_E_ARG, "null argument");
-    HIP_TRY(hipHostUnregister(ptr));
+    if (!ptr) return orbx_set_error(ORBX_E_ARG, "null argument");
+    ORB_TRY(hipHostUnregister(ptr));
     return ORBX_OK;
 }
 
@@ -1262,8 +1221,8 @@ extern "C" int orbx_dev_octree_plan(const orbx_cfg *cfg, int requota, int w0, in
                                     int64_t *out)
 {
     if (!cfg || !out || cfg->n_levels < 1 || cfg->n_levels > ORBX_MAX_LEVELS || cfg->n_features < 1 || !(cfg->scale_factor > 1.0f))
-        return fail(ORBX_E_ARG, "bad argument");
-    if (level_begin < 0 || level_end > cfg->n_levels || level_end <= level_begin || n_frames < 1) return fail(ORBX_E_ARG, "bad level range");
+        return orbx_set_error(ORBX_E_ARG, "bad argument");
+    if (level_begin < 0 || level_end > cfg->n_levels || level_end <= level_begin || n_frames < 1) return orbx_set_error(ORBX_E_ARG, "bad level range");
     orbx_ctx *c = new orbx_ctx();
     c->cfg = *cfg;
     compute_tables(c);
@@ -1285,35 +1244,35 @@ unsigned long long *orbx_dev_fast_prof_symbol();
 // development build only (make prof): k_fast_strip's stage counters since the last reset (tools/fast_mix.py)
 extern "C" int orbx_dev_fast_prof(orbx_t *c, unsigned long long *out16, int reset)
 {
-    if (!c || !out16) return fail(ORBX_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
+    if (!c || !out16) return orbx_set_error(ORBX_E_ARG, "null argument");
+    ORB_TRY(hipSetDevice(c->hs.device));
+    ORB_TRY(hipDeviceSynchronize());
     unsigned long long *sym = orbx_dev_fast_prof_symbol();
-    if (!sym) return fail(ORBX_E_ARG, "no counter symbol");
-    HIP_TRY(hipMemcpy(out16, sym, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(hipMemset(sym, 0, sizeof(unsigned long long) * 16));
+    if (!sym) return orbx_set_error(ORBX_E_ARG, "no counter symbol");
+    ORB_TRY(hipMemcpy(out16, sym, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost));
+    if (reset) ORB_TRY(hipMemset(sym, 0, sizeof(unsigned long long) * 16));
     return ORBX_OK;
 }
 unsigned long long *orbx_dev_fast_cell_times_symbol();
 // development build only (make prof): per-cell time stamps of k_fast_cells_wave, frame 0 (tools/fast_cell_times.py)
 extern "C" int orbx_dev_fast_cell_times(orbx_t *c, unsigned long long *out, int n_slots, int reset)
 {
-    if (!c || !out) return fail(ORBX_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipDeviceSynchronize());
+    if (!c || !out) return orbx_set_error(ORBX_E_ARG, "null argument");
+    ORB_TRY(hipSetDevice(c->hs.device));
+    ORB_TRY(hipDeviceSynchronize());
     unsigned long long *sym = orbx_dev_fast_cell_times_symbol();
-    if (!sym) return fail(ORBX_E_ARG, "no symbol");
-    HIP_TRY(hipMemcpy(out, sym, sizeof(unsigned long long) * 3 * n_slots, hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(hipMemset(sym, 0, sizeof(unsigned long long) * 3 * n_slots));
+    if (!sym) return orbx_set_error(ORBX_E_ARG, "no symbol");
+    ORB_TRY(hipMemcpy(out, sym, sizeof(unsigned long long) * 3 * n_slots, hipMemcpyDeviceToHost));
+    if (reset) ORB_TRY(hipMemset(sym, 0, sizeof(unsigned long long) * 3 * n_slots));
     return ORBX_OK;
 }
 // development build only (make prof): the quadtree kernel's phase time stamps of frame 0 (tools/octree_phases.py)
 extern "C" int orbx_dev_octree_phases(orbx_t *c, unsigned long long *out, int n_levels)
 {
-    if (!c || !out) return fail(ORBX_E_ARG, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(sync_handle(c));
-    HIP_TRY(hipMemcpy(out, c->buf.best, sizeof(unsigned long long) * 64 * n_levels, hipMemcpyDeviceToHost));
+    if (!c || !out) return orbx_set_error(ORBX_E_ARG, "null argument");
+    ORB_TRY(c->hs.host_call());
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
+    ORB_TRY(hipMemcpy(out, c->buf.best, sizeof(unsigned long long) * 64 * n_levels, hipMemcpyDeviceToHost));
     return ORBX_OK;
 }
 #endif

@@ -47,16 +47,17 @@ static inline unsigned orbx_xcd_grid(int per_frame, int n_frames)
 // Development hook (orbx_dev_set_lds_pad, not declared in include/): extra dynamic LDS per workgroup of a batch kernel, so that a
 // tool can cap the kernel's occupancy and measure what a co-resident partner would leave it (profiles/r06_pipeline_budget.md).
 // Stage ids: 0 k_resize_lds, 1 k_fast_strip, 2 oct_batch::k_octree_lds, 3 k_orient<false>, 4 k_blur_desc.  0 bytes = as shipped.
-static int g_dev_lds_pad[5] = {0, 0, 0, 0, 0};
+// (atomic: the launch of every batch reads it, possibly on another thread than the tool that sets it)
+static std::atomic<int> g_dev_lds_pad[5] = {};
 extern "C" int orbx_dev_set_lds_pad(int stage, int bytes)
 {
     if (stage < 0 || stage >= 5 || bytes < 0 || bytes > 159 * 1024) return ORBX_E_ARG;
-    g_dev_lds_pad[stage] = bytes;
+    g_dev_lds_pad[stage].store(bytes);
     return ORBX_OK;
 }
 template <typename K> static size_t dev_pad(K kernel, int stage, size_t static_and_dynamic)
 {
-    const size_t pad = (size_t)g_dev_lds_pad[stage];
+    const size_t pad = (size_t)g_dev_lds_pad[stage].load();
     if (pad) (void)orbx_lds_opt_in(reinterpret_cast<const void *>(kernel), static_and_dynamic + pad);
     return pad;
 }
