@@ -16,6 +16,12 @@
 // orbx_api.hip owns the thread-local text behind orbx_last_error(); returns `code`
 int orbx_set_error(int code, const std::string &msg);
 
+// More than 64 KB of dynamic LDS has to be requested per kernel AND per device (the attribute belongs to the device's code
+// object).  orbx_lds_opt_in (orbx_api.hip) keeps the largest size configured so far per (kernel, device of the calling thread)
+// under a mutex, raises it when `bytes` is larger, and returns the runtime's answer -- a handle on a second GPU of the process
+// gets its own opt-in, and a failed one is reported instead of being found out by a launch error later.
+hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes);
+
 // a failed HIP call returns ORBX_E_NO_DEVICE from the entry point, naming the call
 #define ORB_TRY(expr)                                                                                                   \
     do {                                                                                                                \
@@ -72,17 +78,22 @@ struct HandleStream {
     }
 };
 
-// Grow-only device (PINNED = false) or page-locked host (true) block.  need() keeps the block when `bytes` fit and otherwise
-// replaces it with one of `alloc` bytes: the growth policy is the caller's, and so is the wait for whatever may still use the
-// old block.
+// Grow-only device (PINNED = false) or page-locked host (true) block, owned: the destructor frees it and a copy does not
+// compile.  need() keeps the block when `bytes` fit and otherwise replaces it with one of `alloc` bytes (a pinned one with
+// hipHostMalloc's `flags`): the growth policy is the caller's, and so is the wait for whatever may still use the old block.
+// Never in an object of static storage duration: its destructor would run after the HIP runtime is gone (orbba.hip, g_work).
 template <bool PINNED> struct GrowBuf {
     void *p = nullptr;
     size_t cap = 0;
-    hipError_t need(size_t bytes, size_t alloc)
+    GrowBuf() = default;
+    GrowBuf(const GrowBuf &) = delete;
+    GrowBuf &operator=(const GrowBuf &) = delete;
+    ~GrowBuf() { release(); }
+    hipError_t need(size_t bytes, size_t alloc, unsigned flags = hipHostMallocDefault)
     {
         if (bytes <= cap) return hipSuccess;
         release();
-        hipError_t e = PINNED ? hipHostMalloc(&p, alloc, hipHostMallocDefault) : hipMalloc(&p, alloc);
+        hipError_t e = PINNED ? hipHostMalloc(&p, alloc, flags) : hipMalloc(&p, alloc);
         if (e == hipSuccess) cap = alloc; else p = nullptr;
         return e;
     }

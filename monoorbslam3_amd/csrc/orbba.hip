@@ -21,8 +21,6 @@
 #include "../../include/orbx.h"
 #include "orb_host.h"
 
-hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes); // orbx_api.hip: dynamic LDS above 64 KB, per kernel and per device
-
 // kernel-choice switches of the BA entry points (include/orbba.h: orbba_set_variant); the entry points take no handle, so the
 // switches are per process and read per call
 static std::atomic<int> g_ba_chol{0};        // ORBBA_VAR_CHOL: 0 = reduced system in LDS when it fits, 1 = global-memory kernel

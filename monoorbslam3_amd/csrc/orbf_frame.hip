@@ -24,7 +24,7 @@ struct OrbfCam {
 struct orbf_ctx {
     HandleStream hs;
     OrbfCam cam{};
-    float *d_scale = nullptr;
+    DevBuf d_scale;                      // cam.size_scale's table, when the camera has one
     DevBuf cell_of, tmp;                 // scratch of the grid kernel
     DevBuf raw, un, start, items, n;     // host-convenience staging
 };
@@ -178,9 +178,9 @@ extern "C" int orbf_create(const orbf_camera *cam, int device, orbf_t **out)
     hipError_t e = c->hs.create();
     if (e == hipSuccess && cam->size_scale) {
         const size_t bytes = (size_t)cam->width * cam->height * 4;
-        e = hipMalloc(&c->d_scale, bytes);
-        if (e == hipSuccess) e = hipMemcpy(c->d_scale, cam->size_scale, bytes, hipMemcpyHostToDevice);
-        k.size_scale = c->d_scale;
+        e = c->d_scale.need(bytes, bytes);
+        if (e == hipSuccess) e = hipMemcpy(c->d_scale.p, cam->size_scale, bytes, hipMemcpyHostToDevice);
+        k.size_scale = c->d_scale.as<float>();
     }
     if (e != hipSuccess) {
         orbf_destroy(c);
@@ -194,8 +194,6 @@ extern "C" void orbf_destroy(orbf_t *c)
 {
     if (!c) return;
     c->hs.destroy();
-    if (c->d_scale) (void)hipFree(c->d_scale);
-    for (DevBuf *b : {&c->cell_of, &c->tmp, &c->raw, &c->un, &c->start, &c->items, &c->n}) b->release();
     delete c;
 }
 

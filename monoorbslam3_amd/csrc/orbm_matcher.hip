@@ -24,9 +24,6 @@
 
 typedef unsigned long long u64;
 
-extern "C" const char *orbx_last_error(void);
-hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes); // orbx_api.hip: dynamic LDS above 64 KB, per kernel and per device
-
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
@@ -1451,10 +1448,6 @@ extern "C" void orbm_destroy(orbm_t *c)
 {
     if (!c) return;
     c->hs.destroy();
-    DevBuf *bufs[] = {&c->a, &c->b, &c->out, &c->q_idx, &c->c_begin, &c->c_len, &c->out_begin, &c->c_idx,
-                      &c->row_ok, &c->col_ok, &c->bidx, &c->bbest, &c->bsecond, &c->w_in, &c->w_out, &c->w_grid};
-    for (DevBuf *d : bufs) d->release();
-    c->h_in.release(); c->h_out.release();
     delete c;
 }
 

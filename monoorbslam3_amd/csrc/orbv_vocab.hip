@@ -23,8 +23,6 @@
 #include "orb_host.h"
 #include "orb_math.h"
 
-hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes); // orbx_api.hip: dynamic LDS above 64 KB, per kernel and per device
-
 struct VocDev {
     const int32_t *first;    // [n_nodes + 1] start of node's children in the packed arrays
     const uint32_t *pk_id;   // [n_nodes - 1] node id of each packed child
@@ -53,12 +51,10 @@ struct VocLane {
     size_t o_idx() const { return al(o_off() + (h_cap + 1) * 4); }
     size_t bytes() const { return al(o_idx() + h_cap * 4); }
     hipError_t init() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    // the stream's work is done and the stream gone; the blocks go with the lane
     void release()
     {
         if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); stream = nullptr; }
-        for (DevBuf *b : {&s_word, &s_node, &s_w, &d_blk}) b->release();
-        h_blk.release();
-        h_cap = 0;
     }
 };
 
@@ -69,7 +65,7 @@ struct orbv_ctx {
     std::vector<uint8_t> is_leaf, desc;
     std::vector<double> weight;
     VocDev dev{};
-    void *d_first = nullptr, *d_pk_id = nullptr, *d_pk_desc = nullptr, *d_word_id = nullptr, *d_weight = nullptr;
+    DevBuf d_first, d_pk_id, d_pk_desc, d_word_id, d_weight; // the blocks behind `dev`
     // The reference's vocabulary is ONE object that Tracking (Frame::computeBow, Frame.cpp:168-178) and LocalMapping
     // (KeyFrame::computeBow, LocalMapping.cpp:90) call at the same time: the tree above is read-only, everything a call writes
     // lives in a lane.  The device entry points use `dev_lane` (scratch only; one call in flight per handle, as orbv.h says);
@@ -290,18 +286,17 @@ static int upload(orbv_ctx *c)
         if (c->is_leaf[i]) word_id[i] = (uint32_t)n_words++; // :1408-1414
     }
     c->n_words = n_words;
-    ORB_TRY(hipMalloc(&c->d_first, first.size() * 4));
-    ORB_TRY(hipMalloc(&c->d_pk_id, pk_id.size() * 4));
-    ORB_TRY(hipMalloc(&c->d_pk_desc, pk_desc.size()));
-    ORB_TRY(hipMalloc(&c->d_word_id, word_id.size() * 4));
-    ORB_TRY(hipMalloc(&c->d_weight, (size_t)n * 8));
-    ORB_TRY(hipMemcpy(c->d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice));
-    ORB_TRY(hipMemcpy(c->d_pk_id, pk_id.data(), pk_id.size() * 4, hipMemcpyHostToDevice));
-    ORB_TRY(hipMemcpy(c->d_pk_desc, pk_desc.data(), pk_desc.size(), hipMemcpyHostToDevice));
-    ORB_TRY(hipMemcpy(c->d_word_id, word_id.data(), word_id.size() * 4, hipMemcpyHostToDevice));
-    ORB_TRY(hipMemcpy(c->d_weight, c->weight.data(), (size_t)n * 8, hipMemcpyHostToDevice));
-    c->dev = VocDev{(const int32_t *)c->d_first, (const uint32_t *)c->d_pk_id, (const uint4 *)c->d_pk_desc,
-                    (const uint32_t *)c->d_word_id, (const double *)c->d_weight, c->L, c->n_words, c->scoring, c->weighting};
+    auto put = [](DevBuf &d, const void *src, size_t bytes) {
+        const hipError_t e = d.need(bytes, bytes);
+        return e == hipSuccess ? hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice) : e;
+    };
+    ORB_TRY(put(c->d_first, first.data(), first.size() * 4));
+    ORB_TRY(put(c->d_pk_id, pk_id.data(), pk_id.size() * 4));
+    ORB_TRY(put(c->d_pk_desc, pk_desc.data(), pk_desc.size()));
+    ORB_TRY(put(c->d_word_id, word_id.data(), word_id.size() * 4));
+    ORB_TRY(put(c->d_weight, c->weight.data(), (size_t)n * 8));
+    c->dev = VocDev{c->d_first.as<const int32_t>(), c->d_pk_id.as<const uint32_t>(), c->d_pk_desc.as<const uint4>(),
+                    c->d_word_id.as<const uint32_t>(), c->d_weight.as<const double>(), c->L, c->n_words, c->scoring, c->weighting};
     return ORBX_OK;
 }
 
@@ -416,8 +411,6 @@ extern "C" void orbv_destroy(orbv_t *c)
     c->hs.destroy();
     for (VocLane *ln : c->lanes.idle) { ln->release(); delete ln; }
     c->dev_lane.release();
-    for (void *p : {c->d_first, c->d_pk_id, c->d_pk_desc, c->d_word_id, c->d_weight})
-        if (p) (void)hipFree(p);
     delete c;
 }
 

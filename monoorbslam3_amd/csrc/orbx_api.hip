@@ -38,6 +38,14 @@ hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes)
     return e;
 }
 
+// The blocks behind OrbxBuffers (the kernels' by-value view, filled by ensure_geometry) and level 0's staging copy for the
+// host-pointer API: frame-major, every one `batch` frames of its per-frame size
+struct OrbxArenas {
+    DevBuf img_arena, cand, pnode, pcode, cand_count, bnd0, bnd1, cnt0, cnt1, rank, node_of_rank, newpos, childcnt, childpos, best,
+        sel, kp_ang, sel_count, sel_prefix, l0_stage;
+};
+
+// Every device and pinned block is a GrowBuf member (orb_host.h): `delete` frees them all.
 struct orbx_ctx {
     orbx_cfg cfg;
     HandleStream hs; // device, the handle's own stream, the NULL-stream bookkeeping
@@ -55,40 +63,41 @@ struct orbx_ctx {
     OrbxLevels levels;
     size_t l0_stage_pitch; // staging copy of level 0 for the host-pointer API
     // device state
+    OrbxArenas arena;
     OrbxBuffers buf;
-    OrbxLevels *d_levels;
-    OrbxTap *d_xtap[ORBX_MAX_LEVELS], *d_ytap[ORBX_MAX_LEVELS];
+    DevBuf d_levels;                                            // OrbxLevels
+    DevBuf d_xtap[ORBX_MAX_LEVELS], d_ytap[ORBX_MAX_LEVELS];    // OrbxTap per column / row of level l (l >= 1)
     bool resize2_ok[ORBX_MAX_LEVELS]; // [l]: levels l and l + 1 can come out of one launch (k_resize2's patch fits)
     bool resize_lds_ok[ORBX_MAX_LEVELS]; // [l]: level l can be made by k_resize_lds (its source tiles fit)
     int resize_lds;                   // ORBX_VAR_RESIZE_LDS: 0 = never, 1 = resident batches (default), 2 = always
     int resize2;                      // ORBX_VAR_RESIZE2: 0 = never two levels per launch, 1 = calls with few frames (default), 2 = always
-    int *d_umax, *d_taps;
+    DevBuf d_umax, d_taps;                                      // int[16], int[8]
     hipEvent_t ev_after_fast; bool after_fast_valid; // recorded behind the FAST launches of every call (orbx_stream_wait_fast)
     // timing mode 2: events around the (up to two) launch groups of every stage of a step, on the stream they are launched on
     hipEvent_t ev_in[ORBX_N_STAGES][4]; int ev_in_n[ORBX_N_STAGES];
-    uint16_t *d_fast_cells; int n_fast_cells;
-    uint16_t *d_fast_strips; int n_fast_strips, n_fast_strips0; // strips of all levels / of level 0
+    DevBuf d_fast_cells; int n_fast_cells;                      // uint16_t[4] per cell
+    DevBuf d_fast_strips; int n_fast_strips, n_fast_strips0;    // uint16_t[4] per strip; strips of all levels / of level 0
     int fast_variant;                                           // ORBX_VAR_FAST: 0 = by call size (default), 1 = one wave per cell, 2 = strips
     int zero_copy;                                              // ORBX_VAR_ZERO_COPY
     int fast_cell_group;                                        // ORBX_VAR_FAST_CELL_GROUP: cells (one wave each) per workgroup of the few-frames FAST kernel: 1, 4, 8 (default) or 16
     int desc_variant;                                           // ORBX_VAR_DESC: 0 = by call size, 1 = blur pass + k_orient_desc, 2 = k_blur_desc (fused)
-    uint16_t *d_blur_tiles; int n_blur_tiles;
+    DevBuf d_blur_tiles; int n_blur_tiles;                      // uint16_t[4] per tile
     // the Gaussian on the matrix pipe: strip list, band tables, per-level record; levels [0, blur_mfma_levels)
-    uint16_t *d_blur_strips; uint8_t *d_band_h, *d_band_v;
+    DevBuf d_blur_strips, d_band_h, d_band_v;                   // uint16_t, uint8_t, uint8_t
     BlurMfmaLevels blur_tab; int blur_strips_before[ORBX_MAX_LEVELS + 1]; int blur_mfma_levels;
     // blur + descriptors in one pass (k_blur_desc): block list, H bands, bucket layout; levels [0, bd_levels)
-    uint16_t *d_bd_blocks; uint8_t *d_bd_band_h; int n_bd_blocks, bd_levels, bd_bk_stride;
+    DevBuf d_bd_blocks, d_bd_band_h; int n_bd_blocks, bd_levels, bd_bk_stride; // uint16_t, uint8_t
     BdLevels bd_tab;
-    int *d_bd_bk_start; uint8_t *d_bd_items;                    // per frame: bucket starts, 32-byte key-point records
+    DevBuf d_bd_bk_start, d_bd_items;                           // per frame: bucket starts (int), 32-byte key-point records
     int alloc_bd_batch, alloc_bd_kcap, alloc_bd_stride;
     int last_fused_levels;                                      // levels of the last call whose blurred copy was never written
     int blur_mfma;                                              // ORBX_VAR_BLUR: 1 = by call size (default), 0 = VALU kernels, 2 = matrix pipe for any batch
-    uint8_t *d_l0_stage; size_t l0_stage_fs;
-    int *d_slot_level;                                          // level of every key-point slot of the current geometry
+    size_t l0_stage_fs;
+    DevBuf d_slot_level;                                        // level (int) of every key-point slot of the current geometry
     // host-API output staging, one device block: [counts, 256 B aligned][key points][descriptors]; `h_out_block` is its
-    // pinned mirror while the block is small (a few frames): the records then come back in one copy and one wait
-    uint8_t *d_out_block; uint8_t *h_out_block; uint8_t *h_out_dev; size_t out_block_bytes, out_kp_off, out_desc_off;
-    orbx_kp *d_out_kp; uint8_t *d_out_desc; int32_t *d_out_n; int out_cap;
+    // mapped pinned mirror while the block is small (a few frames): the records then come back in one copy and one wait
+    DevBuf d_out_block; PinBuf h_out_block; uint8_t *h_out_dev; size_t out_block_bytes, out_kp_off, out_desc_off;
+    orbx_kp *d_out_kp; uint8_t *d_out_desc; int32_t *d_out_n; // views into d_out_block
     // capacities actually allocated
     int alloc_batch;
     size_t alloc_img_fs, alloc_cand_fs, alloc_node_fs, alloc_l0_fs;
@@ -272,10 +281,23 @@ static int compute_geometry(const orbx_ctx *c, int w0, int h0, Geometry *g)
     return ORBX_OK;
 }
 
-template <typename T> static hipError_t dev_alloc(T **p, size_t n)
+// A block of exactly n elements of T (at least one), kept while it is large enough and otherwise replaced: the caller has
+// waited for all work that may still read it (GrowBuf::need frees the old block at once).  `view`, if given, is set to it.
+template <typename T> static hipError_t need_exact(DevBuf &d, size_t n, T **view = nullptr)
 {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    return hipMalloc((void **)p, std::max(n, (size_t)1) * sizeof(T));
+    const size_t bytes = std::max(n, (size_t)1) * sizeof(T);
+    const hipError_t e = d.need(bytes, bytes);
+    if (view) *view = d.as<T>();
+    return e;
+}
+
+// A per-geometry table: written in full into a block of at least max(v.size(), min_n) elements, so that an empty table is
+// still a valid block
+template <typename T> static hipError_t upload(DevBuf &d, const std::vector<T> &v, size_t min_n = 1)
+{
+    hipError_t e = need_exact<T>(d, std::max(v.size(), min_n));
+    if (e == hipSuccess && !v.empty()) e = hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+    return e;
 }
 
 static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
@@ -295,34 +317,36 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
                       g.node_fs > c->alloc_node_fs || g.l0_fs > c->alloc_l0_fs ||
                       g.levels.kcap_total > c->alloc_kcap_total;
     if (grow) {
-        // arenas are about to be replaced: nothing enqueued earlier (on the handle's streams or the caller's) may
-        // still be using them
+        // arenas that grow are about to be replaced: nothing enqueued earlier (on the handle's streams or the caller's)
+        // may still be using them
         ORB_TRY(hipDeviceSynchronize());
         const int B = std::max(batch, c->alloc_batch);
         const size_t img_fs = std::max(g.img_fs, c->alloc_img_fs), cand_fs = std::max(g.cand_fs, c->alloc_cand_fs);
         const size_t node_fs = std::max(g.node_fs, c->alloc_node_fs), l0_fs = std::max(g.l0_fs, c->alloc_l0_fs);
         const int kcap = std::max(g.levels.kcap_total, c->alloc_kcap_total);
+        // (one that did not grow keeps its block: every arena is written before it is read in each call)
+        OrbxArenas &a = c->arena;
         OrbxBuffers &b = c->buf;
-        ORB_TRY(dev_alloc(&b.img_arena, img_fs * B));
-        ORB_TRY(dev_alloc(&b.cand, cand_fs * B));
-        ORB_TRY(dev_alloc(&b.pnode, cand_fs * B));
-        ORB_TRY(dev_alloc(&b.pcode, cand_fs * B));
-        ORB_TRY(dev_alloc(&b.cand_count, (size_t)ORBX_MAX_LEVELS * B));
-        ORB_TRY(dev_alloc(&b.bnd0, node_fs * B));
-        ORB_TRY(dev_alloc(&b.bnd1, node_fs * B));
-        ORB_TRY(dev_alloc(&b.cnt0, node_fs * B));
-        ORB_TRY(dev_alloc(&b.cnt1, node_fs * B));
-        ORB_TRY(dev_alloc(&b.rank, node_fs * B));
-        ORB_TRY(dev_alloc(&b.node_of_rank, node_fs * B));
-        ORB_TRY(dev_alloc(&b.newpos, node_fs * B));
-        ORB_TRY(dev_alloc(&b.childcnt, 4 * node_fs * B));
-        ORB_TRY(dev_alloc(&b.childpos, 4 * node_fs * B));
-        ORB_TRY(dev_alloc(&b.best, node_fs * B));
-        ORB_TRY(dev_alloc(&b.sel, (size_t)kcap * B));
-        ORB_TRY(dev_alloc(&b.kp_ang, (size_t)kcap * B));
-        ORB_TRY(dev_alloc(&b.sel_count, (size_t)ORBX_MAX_LEVELS * B));
-        ORB_TRY(dev_alloc(&b.sel_prefix, (size_t)ORBX_MAX_LEVELS * B));
-        ORB_TRY(dev_alloc(&c->d_l0_stage, l0_fs * B));
+        ORB_TRY(need_exact(a.img_arena, img_fs * B, &b.img_arena));
+        ORB_TRY(need_exact(a.cand, cand_fs * B, &b.cand));
+        ORB_TRY(need_exact(a.pnode, cand_fs * B, &b.pnode));
+        ORB_TRY(need_exact(a.pcode, cand_fs * B, &b.pcode));
+        ORB_TRY(need_exact(a.cand_count, (size_t)ORBX_MAX_LEVELS * B, &b.cand_count));
+        ORB_TRY(need_exact(a.bnd0, node_fs * B, &b.bnd0));
+        ORB_TRY(need_exact(a.bnd1, node_fs * B, &b.bnd1));
+        ORB_TRY(need_exact(a.cnt0, node_fs * B, &b.cnt0));
+        ORB_TRY(need_exact(a.cnt1, node_fs * B, &b.cnt1));
+        ORB_TRY(need_exact(a.rank, node_fs * B, &b.rank));
+        ORB_TRY(need_exact(a.node_of_rank, node_fs * B, &b.node_of_rank));
+        ORB_TRY(need_exact(a.newpos, node_fs * B, &b.newpos));
+        ORB_TRY(need_exact(a.childcnt, 4 * node_fs * B, &b.childcnt));
+        ORB_TRY(need_exact(a.childpos, 4 * node_fs * B, &b.childpos));
+        ORB_TRY(need_exact(a.best, node_fs * B, &b.best));
+        ORB_TRY(need_exact(a.sel, (size_t)kcap * B, &b.sel));
+        ORB_TRY(need_exact(a.kp_ang, (size_t)kcap * B, &b.kp_ang));
+        ORB_TRY(need_exact(a.sel_count, (size_t)ORBX_MAX_LEVELS * B, &b.sel_count));
+        ORB_TRY(need_exact(a.sel_prefix, (size_t)ORBX_MAX_LEVELS * B, &b.sel_prefix));
+        ORB_TRY(need_exact<uint8_t>(a.l0_stage, l0_fs * B));
         c->alloc_batch = B; c->alloc_img_fs = img_fs; c->alloc_cand_fs = cand_fs; c->alloc_node_fs = node_fs;
         c->alloc_l0_fs = l0_fs; c->alloc_kcap_total = kcap;
         c->alloc_out_cap = 0; // host-API output staging is per (batch, cap)
@@ -334,17 +358,19 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
         c->out_kp_off = align_up(B * sizeof(int32_t), 256);
         c->out_desc_off = align_up(c->out_kp_off + B * cap * sizeof(orbx_kp), 256);
         c->out_block_bytes = c->out_desc_off + B * cap * 32;
-        ORB_TRY(dev_alloc(&c->d_out_block, c->out_block_bytes));
-        c->d_out_n = reinterpret_cast<int32_t *>(c->d_out_block);
-        c->d_out_kp = reinterpret_cast<orbx_kp *>(c->d_out_block + c->out_kp_off);
-        c->d_out_desc = c->d_out_block + c->out_desc_off;
-        if (c->h_out_block) { (void)hipHostFree(c->h_out_block); c->h_out_block = nullptr; }
+        ORB_TRY(need_exact<uint8_t>(c->d_out_block, c->out_block_bytes));
+        uint8_t *blk = c->d_out_block.as<uint8_t>();
+        c->d_out_n = reinterpret_cast<int32_t *>(blk);
+        c->d_out_kp = reinterpret_cast<orbx_kp *>(blk + c->out_kp_off);
+        c->d_out_desc = blk + c->out_desc_off;
         c->h_out_dev = nullptr;
-        if (c->out_block_bytes <= (size_t)4 << 20) {
-            ORB_TRY(hipHostMalloc((void **)&c->h_out_block, c->out_block_bytes, hipHostMallocMapped));
+        if (c->out_block_bytes > (size_t)4 << 20) {
+            c->h_out_block.release();
+        } else {
+            ORB_TRY(c->h_out_block.need(c->out_block_bytes, c->out_block_bytes, hipHostMallocMapped));
             // the descriptor kernel writes a small call's records straight into this block (no copy back);
             // ORBX_VAR_ZERO_COPY = 0 keeps them in HBM and copies
-            ORB_TRY(hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out_block, 0));
+            ORB_TRY(hipHostGetDevicePointer((void **)&c->h_out_dev, c->h_out_block.p, 0));
         }
         c->alloc_out_cap = cap;
     }
@@ -354,30 +380,27 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
         c->cur_w = w0; c->cur_h = h0;
         c->l0_stage_pitch = g.l0_pitch;
         c->sort_lds_bytes = g.sort_lds;
-        ORB_TRY(hipMemcpy(c->d_levels, &c->levels, sizeof(OrbxLevels), hipMemcpyHostToDevice));
+        ORB_TRY(hipMemcpy(c->d_levels.p, &c->levels, sizeof(OrbxLevels), hipMemcpyHostToDevice));
         {
             std::vector<int> sl((size_t)std::max(c->levels.kcap_total, 1), 0);
             for (int l = 0; l < c->levels.n_levels; ++l)
                 for (int k = c->levels.lv[l].kp_off; k < c->levels.lv[l].kp_off + c->levels.lv[l].kcap && k < c->levels.kcap_total; ++k)
                     sl[k] = l;
-            ORB_TRY(dev_alloc(&c->d_slot_level, sl.size()));
-            ORB_TRY(hipMemcpy(c->d_slot_level, sl.data(), sl.size() * sizeof(int), hipMemcpyHostToDevice));
-            c->buf.slot_level = c->d_slot_level;
+            ORB_TRY(upload(c->d_slot_level, sl));
+            c->buf.slot_level = c->d_slot_level.as<int>();
         }
         {
             const int nc = orbx_build_fast_cells(c->levels, nullptr);
             std::vector<uint16_t> cells((size_t)std::max(nc, 1) * 4);
             orbx_build_fast_cells(c->levels, cells.data());
-            ORB_TRY(dev_alloc(&c->d_fast_cells, cells.size()));
-            ORB_TRY(hipMemcpy(c->d_fast_cells, cells.data(), cells.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_fast_cells, cells));
             c->n_fast_cells = nc;
         }
         {
             const int ns = orbx_build_fast_strips(c->levels, 0, c->levels.n_levels, nullptr);
             std::vector<uint16_t> st((size_t)std::max(ns, 1) * 4);
             orbx_build_fast_strips(c->levels, 0, c->levels.n_levels, st.data());
-            ORB_TRY(dev_alloc(&c->d_fast_strips, st.size()));
-            ORB_TRY(hipMemcpy(c->d_fast_strips, st.data(), st.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_fast_strips, st));
             c->n_fast_strips = ns;
             c->n_fast_strips0 = orbx_build_fast_strips(c->levels, 0, 1, nullptr);
         }
@@ -385,38 +408,30 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
             const int nt = orbx_build_blur_tiles(c->levels, nullptr);
             std::vector<uint16_t> tl((size_t)std::max(nt, 1) * 4);
             orbx_build_blur_tiles(c->levels, tl.data());
-            ORB_TRY(dev_alloc(&c->d_blur_tiles, tl.size()));
-            ORB_TRY(hipMemcpy(c->d_blur_tiles, tl.data(), tl.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_blur_tiles, tl));
             c->n_blur_tiles = nt;
             std::vector<uint16_t> bs;
             std::vector<uint8_t> bh, bv;
             orbx_build_blur_mfma(c->levels, c->taps, bs, bh, bv, c->blur_tab, c->blur_strips_before);
             c->blur_mfma_levels = orbx_blur_mfma_levels(c->levels);
-            ORB_TRY(dev_alloc(&c->d_blur_strips, std::max(bs.size(), (size_t)2)));
-            ORB_TRY(dev_alloc(&c->d_band_h, std::max(bh.size(), (size_t)16)));
-            ORB_TRY(dev_alloc(&c->d_band_v, std::max(bv.size(), (size_t)16)));
-            if (!bs.empty()) ORB_TRY(hipMemcpy(c->d_blur_strips, bs.data(), bs.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            if (!bh.empty()) ORB_TRY(hipMemcpy(c->d_band_h, bh.data(), bh.size(), hipMemcpyHostToDevice));
-            if (!bv.empty()) ORB_TRY(hipMemcpy(c->d_band_v, bv.data(), bv.size(), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_blur_strips, bs, 2));
+            ORB_TRY(upload(c->d_band_h, bh, 16));
+            ORB_TRY(upload(c->d_band_v, bv, 16));
             std::vector<uint16_t> bb;
             std::vector<uint8_t> bdh;
             orbx_build_blur_desc(c->levels, c->taps, c->blur_tab, bb, bdh, c->bd_tab, &c->bd_levels, &c->bd_bk_stride);
             c->n_bd_blocks = (int)(bb.size() / 2);
-            ORB_TRY(dev_alloc(&c->d_bd_blocks, std::max(bb.size(), (size_t)2)));
-            ORB_TRY(dev_alloc(&c->d_bd_band_h, std::max(bdh.size(), (size_t)16)));
-            if (!bb.empty()) ORB_TRY(hipMemcpy(c->d_bd_blocks, bb.data(), bb.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-            if (!bdh.empty()) ORB_TRY(hipMemcpy(c->d_bd_band_h, bdh.data(), bdh.size(), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_bd_blocks, bb, 2));
+            ORB_TRY(upload(c->d_bd_band_h, bdh, 16));
         }
         std::vector<OrbxTap> taps, ytaps;
         for (int l = 1; l < c->levels.n_levels; ++l) {
             const OrbxLevel &d = c->levels.lv[l], &s = c->levels.lv[l - 1];
             linear_taps(d.w, s.w, true, taps);
             while (taps.size() % 4) taps.push_back(taps.back()); // k_resize reads the column taps four at a time
-            ORB_TRY(dev_alloc(&c->d_xtap[l], taps.size()));
-            ORB_TRY(hipMemcpy(c->d_xtap[l], taps.data(), taps.size() * sizeof(OrbxTap), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_xtap[l], taps));
             linear_taps(d.h, s.h, false, ytaps);
-            ORB_TRY(dev_alloc(&c->d_ytap[l], ytaps.size()));
-            ORB_TRY(hipMemcpy(c->d_ytap[l], ytaps.data(), ytaps.size() * sizeof(OrbxTap), hipMemcpyHostToDevice));
+            ORB_TRY(upload(c->d_ytap[l], ytaps));
             // levels l - 1 and l from one launch (source: level l - 2): the patch of level l - 1 a tile of level l needs
             c->resize2_ok[l - 1] = l >= 2 && orbx_resize2_fits(taps.data(), ytaps.data(), s.w, s.h, d.w, d.h);
             c->resize_lds_ok[l] = orbx_resize_lds_fits(taps.data(), ytaps.data(), s.w, s.h, d.w, d.h);
@@ -428,8 +443,8 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
         c->alloc_bd_batch = std::max(c->alloc_batch, c->alloc_bd_batch);
         c->alloc_bd_kcap = std::max(c->levels.kcap_total, c->alloc_bd_kcap);
         c->alloc_bd_stride = std::max(c->bd_bk_stride, c->alloc_bd_stride);
-        ORB_TRY(dev_alloc(&c->d_bd_bk_start, (size_t)c->alloc_bd_stride * c->alloc_bd_batch));
-        ORB_TRY(dev_alloc(&c->d_bd_items, (size_t)32 * std::max(c->alloc_bd_kcap, 1) * c->alloc_bd_batch));
+        ORB_TRY(need_exact<int>(c->d_bd_bk_start, (size_t)c->alloc_bd_stride * c->alloc_bd_batch));
+        ORB_TRY(need_exact<uint8_t>(c->d_bd_items, (size_t)32 * std::max(c->alloc_bd_kcap, 1) * c->alloc_bd_batch));
     }
     // frame strides of the arenas are the allocated ones
     c->buf.img_frame_stride = c->alloc_img_fs;
@@ -501,12 +516,11 @@ static int create_common(const orbx_cfg *cfg, const int *quotas_override, orbx_t
     c->zero_copy = 1;
     c->desc_variant = 0;
     c->fast_cell_group = 8;
-    if (hipMalloc((void **)&c->d_levels, sizeof(OrbxLevels)) != hipSuccess ||
-        hipMalloc((void **)&c->d_umax, sizeof(int) * 16) != hipSuccess ||
-        hipMalloc((void **)&c->d_taps, sizeof(int) * 8) != hipSuccess)
+    if (need_exact<OrbxLevels>(c->d_levels, 1) != hipSuccess || need_exact<int>(c->d_umax, 16) != hipSuccess ||
+        need_exact<int>(c->d_taps, 8) != hipSuccess)
         return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipMalloc failed"));
-    if (hipMemcpy(c->d_umax, c->u_max, sizeof(int) * 16, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_taps, c->taps, sizeof(int) * 7, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(c->d_umax.p, c->u_max, sizeof(int) * 16, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_taps.p, c->taps, sizeof(int) * 7, hipMemcpyHostToDevice) != hipSuccess)
         return cleanup(orbx_set_error(ORBX_E_NO_DEVICE, "hipMemcpy failed"));
     if (cfg->max_width > 0 && cfg->max_height > 0) {
         int rc = ensure_geometry(c, cfg->max_width, cfg->max_height, c->cfg.max_batch, 0);
@@ -538,16 +552,6 @@ extern "C" void orbx_destroy(orbx_t *c)
 {
     if (!c) return;
     c->hs.destroy();
-    OrbxBuffers &b = c->buf;
-    void *ptrs[] = {b.img_arena, b.cand, b.pnode, b.pcode, b.cand_count, b.bnd0, b.bnd1, b.cnt0, b.cnt1, b.rank, b.node_of_rank,
-                    b.newpos, b.childcnt, b.childpos, b.best, b.sel, b.kp_ang, b.sel_count, b.sel_prefix, c->d_slot_level, c->d_levels, c->d_umax, c->d_taps,
-                    c->d_l0_stage, c->d_out_block, c->d_fast_cells, c->d_fast_strips, c->d_blur_tiles, c->d_blur_strips, c->d_band_h, c->d_band_v, c->d_bd_blocks, c->d_bd_band_h, c->d_bd_bk_start, c->d_bd_items};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (c->h_out_block) (void)hipHostFree(c->h_out_block);
-    for (int l = 0; l < ORBX_MAX_LEVELS; ++l) {
-        if (c->d_xtap[l]) (void)hipFree(c->d_xtap[l]);
-        if (c->d_ytap[l]) (void)hipFree(c->d_ytap[l]);
-    }
     for (int i = 0; i <= ORBX_N_STAGES; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int st = 0; st < ORBX_N_STAGES; ++st)
         for (int i = 0; i < 4; ++i) if (c->ev_in[st][i]) (void)hipEventDestroy(c->ev_in[st][i]);
@@ -564,7 +568,7 @@ extern "C" void orbx_destroy(orbx_t *c)
         if (c->ev_start[i]) (void)hipEventDestroy(c->ev_start[i]);
         if (c->ev_fast0[i]) (void)hipEventDestroy(c->ev_fast0[i]);
     }
-    delete c;
+    delete c; // and with it every device and pinned block
 }
 
 extern "C" int orbx_tables(const orbx_t *c, int *n_levels, float *sf, float *isf, float *ss, float *iss, float *lsf,
@@ -636,6 +640,9 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     const OrbxLevels &LV = c->levels;
     const int L = LV.n_levels;
     const OrbxBuffers b = offset_buffers(c->buf, f0, LV.kcap_total);
+    const OrbxLevels *d_levels = c->d_levels.as<OrbxLevels>();
+    auto xtap = [&](int l) { return c->d_xtap[l].as<OrbxTap>(); };
+    auto ytap = [&](int l) { return c->d_ytap[l].as<OrbxTap>(); };
     d_l0 += (size_t)f0 * l0_fs;
     d_kp += (size_t)f0 * cap; d_desc += (size_t)f0 * cap * 32; d_n += f0;
     if (t) ORB_TRY(hipEventRecord(c->ev[0], s));
@@ -654,19 +661,19 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         // after the other -- while a single 1242x375 frame is back 20 us sooner, 157 -> 138 us; ORBX_VAR_RESIZE2 = 2 forces it)
         if ((c->resize2 == 2 || (c->resize2 == 1 && n_frames < 24)) && l + 1 < L && c->resize2_ok[l]) {
             orbx_launch_resize2(st, sp, sfs, spitch, LV.lv[l - 1].w, LV.lv[l - 1].h, b.img_arena + LV.lv[l].raw_off, b.img_frame_stride,
-                                LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, c->d_xtap[l], c->d_ytap[l], b.img_arena + LV.lv[l + 1].raw_off,
-                                b.img_frame_stride, LV.lv[l + 1].pitch, LV.lv[l + 1].w, LV.lv[l + 1].h, c->d_xtap[l + 1],
-                                c->d_ytap[l + 1], n_frames, zero_counts);
+                                LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, xtap(l), ytap(l), b.img_arena + LV.lv[l + 1].raw_off,
+                                b.img_frame_stride, LV.lv[l + 1].pitch, LV.lv[l + 1].w, LV.lv[l + 1].h, xtap(l + 1),
+                                ytap(l + 1), n_frames, zero_counts);
             return l + 1;
         }
         if (lds_resize && c->resize_lds_ok[l]) {
             orbx_launch_resize_lds(st, sp, sfs, spitch, LV.lv[l - 1].w, LV.lv[l - 1].h, l == 1 ? LV.lv[0].w : spitch,
-                                   b.img_arena + LV.lv[l].raw_off, b.img_frame_stride, LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, c->d_xtap[l],
-                                   c->d_ytap[l], n_frames, zero_counts);
+                                   b.img_arena + LV.lv[l].raw_off, b.img_frame_stride, LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, xtap(l),
+                                   ytap(l), n_frames, zero_counts);
             return l;
         }
         orbx_launch_resize(st, sp, sfs, spitch, LV.lv[l - 1].w, LV.lv[l - 1].h, b.img_arena + LV.lv[l].raw_off, b.img_frame_stride,
-                           LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, c->d_xtap[l], c->d_ytap[l], n_frames, zero_counts);
+                           LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, xtap(l), ytap(l), n_frames, zero_counts);
         return l;
     };
     const bool side_ok = !t && c->side_blur && slot >= 0;
@@ -675,15 +682,15 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     // handful of frames is bounded by the longest wave instead, where one short wave per cell finishes sooner
     // (single 1242x375 frame: 31 us against 50; 16 frames: 63 against 69; 32 frames: 110 against 97).  Same candidates either way (tests).  ORBX_VAR_FAST = 1 / 2 force one.
     const bool strips = c->fast_variant == 2 || (c->fast_variant == 0 && n_frames >= 24);
-    const uint16_t *d_units = strips ? c->d_fast_strips : c->d_fast_cells;
+    const uint16_t *d_units = (strips ? c->d_fast_strips : c->d_fast_cells).as<uint16_t>();
     const int n_units = strips ? c->n_fast_strips : c->n_fast_cells;
     const int n_cells0 = strips ? c->n_fast_strips0 : LV.lv[0].n_cols * LV.lv[0].n_rows;
     auto launch_fast = [&](hipStream_t st, const uint16_t *units, int n) {
         // timing mode 2: the step keeps its streams, and HIP events on the launch's own stream bracket each launch group, so
         // that the kernels are timed as they run beside the others (orbx_stage_times_in_step_ms)
         InStep ft(c, ORBX_STAGE_FAST, st);
-        if (strips) orbx_launch_fast_strips(st, d_l0, l0_fs, l0_pitch, c->d_levels, LV, b, units, n, n_frames);
-        else orbx_launch_fast(st, d_l0, l0_fs, l0_pitch, c->d_levels, LV, b, units, n, n_frames, c->fast_cell_group);
+        if (strips) orbx_launch_fast_strips(st, d_l0, l0_fs, l0_pitch, d_levels, LV, b, units, n, n_frames);
+        else orbx_launch_fast(st, d_l0, l0_fs, l0_pitch, d_levels, LV, b, units, n, n_frames, c->fast_cell_group);
     };
     // 7x7 Gaussian of levels [lb, le): on the matrix pipe for the levels that are large enough when the call is a batch
     // (ORBX_VAR_BLUR = 2 forces it for any batch, 0 switches it off), the VALU kernels for the rest
@@ -698,10 +705,10 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         InStep bt(c, ORBX_STAGE_BLUR, st);
         const int lm = (c->blur_mfma == 2 || (c->blur_mfma == 1 && n_frames >= 8)) ? std::min(c->blur_mfma_levels, le) : 0;
         if (lm > lb)
-            orbx_launch_blur_mfma(st, d_l0, l0_fs, l0_pitch, LV, b, c->blur_tab, c->d_blur_strips, c->blur_strips_before,
-                                  c->d_band_h, c->d_band_v, c->taps, n_frames, lb, lm);
+            orbx_launch_blur_mfma(st, d_l0, l0_fs, l0_pitch, LV, b, c->blur_tab, c->d_blur_strips.p, c->blur_strips_before,
+                                  c->d_band_h.p, c->d_band_v.p, c->taps, n_frames, lb, lm);
         if (le > std::max(lb, lm))
-            orbx_launch_blur(st, d_l0, l0_fs, l0_pitch, c->d_levels, LV, b, c->d_blur_tiles, c->n_blur_tiles, c->d_taps, n_frames,
+            orbx_launch_blur(st, d_l0, l0_fs, l0_pitch, d_levels, LV, b, c->d_blur_tiles.p, c->n_blur_tiles, c->d_taps.as<int>(), n_frames,
                              std::max(lb, lm), le);
     };
     // orientation, then the descriptors: k_blur_desc for levels [0, fl), k_orient_desc (behind the blur pass) for the others
@@ -710,14 +717,14 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         // the launcher's own event standing between them)
         const bool in2 = c->timing == 2 && c->ev_in[0][0];
         if (in2) { (void)hipEventRecord(c->ev_in[ORBX_STAGE_ORIENT][0], s); c->ev_in_n[ORBX_STAGE_ORIENT] = 1; }
-        int *bk = c->d_bd_bk_start + (size_t)f0 * c->bd_bk_stride;
-        uint8_t *items = c->d_bd_items + (size_t)f0 * 32 * LV.kcap_total;
-        if (fl > 0) orbx_launch_desc_bins(s, c->d_levels, b, c->bd_tab, fl, bk, c->bd_bk_stride, items, cap, d_n, n_frames);
-        orbx_launch_orient_desc(s, d_l0, l0_fs, l0_pitch, c->d_levels, LV, b, c->d_umax, d_kp, d_desc, cap, d_n, n_frames,
+        int *bk = c->d_bd_bk_start.as<int>() + (size_t)f0 * c->bd_bk_stride;
+        uint8_t *items = c->d_bd_items.as<uint8_t>() + (size_t)f0 * 32 * LV.kcap_total;
+        if (fl > 0) orbx_launch_desc_bins(s, d_levels, b, c->bd_tab, fl, bk, c->bd_bk_stride, items, cap, d_n, n_frames);
+        orbx_launch_orient_desc(s, d_l0, l0_fs, l0_pitch, d_levels, LV, b, c->d_umax.as<int>(), d_kp, d_desc, cap, d_n, n_frames,
                                 fl < L ? blur_done : nullptr, fl, in2 ? c->ev_in[ORBX_STAGE_ORIENT][1] : (t ? c->ev[ORBX_STAGE_ORIENT + 1] : nullptr),
                                 fl > 0 ? items : nullptr, in2 ? c->ev_in[ORBX_STAGE_DESC][0] : nullptr);
         if (fl > 0)
-            orbx_launch_desc_fused(s, d_l0, l0_fs, l0_pitch, LV, b, c->bd_tab, fl, c->d_bd_blocks, c->n_bd_blocks, c->d_bd_band_h, c->d_band_v,
+            orbx_launch_desc_fused(s, d_l0, l0_fs, l0_pitch, LV, b, c->bd_tab, fl, c->d_bd_blocks.p, c->n_bd_blocks, c->d_bd_band_h.p, c->d_band_v.p,
                                    bk, c->bd_bk_stride, items, c->taps, d_kp, d_desc, cap, n_frames);
         // (the descriptor bracket was opened by the launcher, behind its wait for the side stream's blur)
         if (in2) { (void)hipEventRecord(c->ev_in[ORBX_STAGE_DESC][1], s); c->ev_in_n[ORBX_STAGE_DESC] = 1; }
@@ -758,7 +765,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         auto launch_side = [&]() -> int {
             ORB_TRY(hipStreamWaitEvent(c->side[slot], c->ev_start[slot], 0));
             launch_fast(c->side[slot], d_units, cells_before[G]);
-            orbx_launch_octree(c->side[slot], c->d_levels, LV, b, n_frames, c->sort_lds_bytes, 0, G, c->n_cus);
+            orbx_launch_octree(c->side[slot], d_levels, LV, b, n_frames, c->sort_lds_bytes, 0, G, c->n_cus);
             ORB_TRY(hipEventRecord(c->ev_fast0[slot], c->side[slot]));
             return ORBX_OK;
         };
@@ -775,7 +782,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         }
         ORB_TRY(hipEventRecord(c->ev_pyr[bslot], s));
         if (cells_before[L] > cells_before[G]) launch_fast(s, d_units + 4 * cells_before[G], cells_before[L] - cells_before[G]);
-        orbx_launch_octree(s, c->d_levels, LV, b, n_frames, c->sort_lds_bytes, G, L, c->n_cus);
+        orbx_launch_octree(s, d_levels, LV, b, n_frames, c->sort_lds_bytes, G, L, c->n_cus);
         if (!side_first) { int rc = launch_side(); if (rc) return rc; }
         ORB_TRY(hipStreamWaitEvent(c->side[bslot], c->ev_pyr[bslot], 0));
         launch_blur(c->side[bslot], 0, L);
@@ -829,7 +836,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     if (t) ORB_TRY(hipEventRecord(c->ev[3], s));
     {
         InStep ot(c, ORBX_STAGE_OCTREE, s);
-        orbx_launch_octree(s, c->d_levels, LV, b, n_frames, c->sort_lds_bytes, 0, L, c->n_cus);
+        orbx_launch_octree(s, d_levels, LV, b, n_frames, c->sort_lds_bytes, 0, L, c->n_cus);
     }
     if (t) ORB_TRY(hipEventRecord(c->ev[4], s));
     if (side && c->side_blur >= 3) { int rc = fork_blur(); if (rc) return rc; } // next to the orientation only
@@ -908,6 +915,8 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
     ORB_TRY(c->hs.host_call());
     const int scap = c->alloc_out_cap;
     hipStream_t s = c->hs.stream;
+    uint8_t *const l0_stage = c->arena.l0_stage.as<uint8_t>();
+    uint8_t *const d_blk = c->d_out_block.as<uint8_t>(), *const h_blk = c->h_out_block.as<uint8_t>(); // h_blk: null when unmirrored
     PhaseTrace tr("orbx", "ORBX_TRACE"); // host time stamps of the phases on stderr
     // Level 0 goes to HBM as it is laid out on the host: dense rows (stride == width, the cv::Mat::clone() case of
     // Frame.cpp:17) are ONE linear copy (a pitched 2-D copy from pageable memory costs milliseconds); the kernels
@@ -918,14 +927,14 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
         l0_pitch = width;
         l0_fs = (size_t)width * height;
         if (frame_stride == l0_fs)
-            ORB_TRY(hipMemcpyAsync(c->d_l0_stage, imgs, l0_fs * n_frames, hipMemcpyHostToDevice, s));
+            ORB_TRY(hipMemcpyAsync(l0_stage, imgs, l0_fs * n_frames, hipMemcpyHostToDevice, s));
         else
             for (int f = 0; f < n_frames; ++f)
-                ORB_TRY(hipMemcpyAsync(c->d_l0_stage + (size_t)f * l0_fs, imgs + (size_t)f * frame_stride, l0_fs,
+                ORB_TRY(hipMemcpyAsync(l0_stage + (size_t)f * l0_fs, imgs + (size_t)f * frame_stride, l0_fs,
                                        hipMemcpyHostToDevice, s));
     } else {
         for (int f = 0; f < n_frames; ++f)
-            ORB_TRY(hipMemcpy2DAsync(c->d_l0_stage + (size_t)f * l0_fs, l0_pitch, imgs + (size_t)f * frame_stride, stride,
+            ORB_TRY(hipMemcpy2DAsync(l0_stage + (size_t)f * l0_fs, l0_pitch, imgs + (size_t)f * frame_stride, stride,
                                      width, height, hipMemcpyHostToDevice, s));
     }
     tr.mark("copy-in call");
@@ -934,12 +943,12 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
         // the block was laid out for), one wait, and the live records go to the caller's buffers from pinned memory
         const size_t nb = (size_t)n_frames;
         if (n_frames == c->alloc_batch) {
-            ORB_TRY(hipMemcpyAsync(c->h_out_block, c->d_out_block, c->out_block_bytes, hipMemcpyDeviceToHost, s));
+            ORB_TRY(hipMemcpyAsync(h_blk, d_blk, c->out_block_bytes, hipMemcpyDeviceToHost, s));
         } else {
-            ORB_TRY(hipMemcpyAsync(c->h_out_block, c->d_out_block, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            ORB_TRY(hipMemcpyAsync(c->h_out_block + c->out_kp_off, c->d_out_block + c->out_kp_off, nb * scap * sizeof(orbx_kp),
+            ORB_TRY(hipMemcpyAsync(h_blk, d_blk, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            ORB_TRY(hipMemcpyAsync(h_blk + c->out_kp_off, d_blk + c->out_kp_off, nb * scap * sizeof(orbx_kp),
                                    hipMemcpyDeviceToHost, s));
-            ORB_TRY(hipMemcpyAsync(c->h_out_block + c->out_desc_off, c->d_out_block + c->out_desc_off, nb * scap * 32,
+            ORB_TRY(hipMemcpyAsync(h_blk + c->out_desc_off, d_blk + c->out_desc_off, nb * scap * 32,
                                    hipMemcpyDeviceToHost, s));
         }
         return ORBX_OK;
@@ -947,27 +956,27 @@ extern "C" int orbx_extract_batch(orbx_t *c, const uint8_t *imgs, int n_frames, 
     // (Replaying the call as one captured hipGraph -- kernels on three streams plus the record copy -- was measured and is
     // not used: 295 us per 1242x375 frame against 218 us for the eager launches, ROCm 7.2.)
     if (c->h_out_dev && c->zero_copy) { // the last kernel writes the records into the pinned block itself
-        rc = enqueue_batch(c, s, c->d_l0_stage, l0_fs, l0_pitch, n_frames, reinterpret_cast<orbx_kp *>(c->h_out_dev + c->out_kp_off),
+        rc = enqueue_batch(c, s, l0_stage, l0_fs, l0_pitch, n_frames, reinterpret_cast<orbx_kp *>(c->h_out_dev + c->out_kp_off),
                            c->h_out_dev + c->out_desc_off, scap, reinterpret_cast<int32_t *>(c->h_out_dev), true);
         if (rc) return rc;
     } else {
-        rc = enqueue_batch(c, s, c->d_l0_stage, l0_fs, l0_pitch, n_frames, c->d_out_kp, c->d_out_desc, scap, c->d_out_n, true);
+        rc = enqueue_batch(c, s, l0_stage, l0_fs, l0_pitch, n_frames, c->d_out_kp, c->d_out_desc, scap, c->d_out_n, true);
         if (rc) return rc;
-        if (c->h_out_block) { rc = copy_records(); if (rc) return rc; }
+        if (h_blk) { rc = copy_records(); if (rc) return rc; }
     }
     tr.mark("kernel launches");
     int status = ORBX_OK;
-    if (c->h_out_block) {
+    if (h_blk) {
         ORB_TRY(hipStreamSynchronize(s));
         tr.mark("device + records");
-        const int32_t *counts = reinterpret_cast<const int32_t *>(c->h_out_block);
+        const int32_t *counts = reinterpret_cast<const int32_t *>(h_blk);
         for (int f = 0; f < n_frames; ++f) {
             const int n = counts[f];
             n_out[f] = n;
             if (n == 0) continue; // reference :512 -- outputs untouched
             if (n > cap) { status = ORBX_E_CAPACITY; continue; }
-            memcpy(out_kp + (size_t)f * cap, c->h_out_block + c->out_kp_off + (size_t)f * scap * sizeof(orbx_kp), sizeof(orbx_kp) * n);
-            memcpy(out_desc + (size_t)f * cap * 32, c->h_out_block + c->out_desc_off + (size_t)f * scap * 32, (size_t)n * 32);
+            memcpy(out_kp + (size_t)f * cap, h_blk + c->out_kp_off + (size_t)f * scap * sizeof(orbx_kp), sizeof(orbx_kp) * n);
+            memcpy(out_desc + (size_t)f * cap * 32, h_blk + c->out_desc_off + (size_t)f * scap * 32, (size_t)n * 32);
         }
     } else {
         std::vector<int32_t> counts(n_frames);
@@ -1017,11 +1026,11 @@ extern "C" int orbx_tap_level(orbx_t *c, int frame, int level, int blurred, uint
         // the last call described this level with k_blur_desc, which keeps the blurred rows in LDS only: the blur pass makes
         // the copy now (all frames of the call, so that later taps find it), on the raw level that is still in place
         if (level < c->blur_mfma_levels)
-            orbx_launch_blur_mfma(c->hs.stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->levels, c->buf, c->blur_tab, c->d_blur_strips,
-                                  c->blur_strips_before, c->d_band_h, c->d_band_v, c->taps, c->last_frames, level, level + 1);
+            orbx_launch_blur_mfma(c->hs.stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->levels, c->buf, c->blur_tab, c->d_blur_strips.p,
+                                  c->blur_strips_before, c->d_band_h.p, c->d_band_v.p, c->taps, c->last_frames, level, level + 1);
         else
-            orbx_launch_blur(c->hs.stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->d_levels, c->levels, c->buf, c->d_blur_tiles,
-                             c->n_blur_tiles, c->d_taps, c->last_frames, level, level + 1);
+            orbx_launch_blur(c->hs.stream, c->last_l0, c->last_l0_fs, c->last_l0_pitch, c->d_levels.as<OrbxLevels>(), c->levels, c->buf, c->d_blur_tiles.p,
+                             c->n_blur_tiles, c->d_taps.as<int>(), c->last_frames, level, level + 1);
         ORB_TRY(hipGetLastError());
         ORB_TRY(hipStreamSynchronize(c->hs.stream));
     }
@@ -1073,20 +1082,14 @@ extern "C" int orbx_tap_sincos(orbx_t *c, const float *angles_deg, int n, float 
     if (!c || !angles_deg || !cos_sin || n < 0) return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (n == 0) return ORBX_OK;
     ORB_TRY(hipSetDevice(c->hs.device));
-    float *d_in = nullptr;
-    float2 *d_out = nullptr;
-    ORB_TRY(hipMalloc(&d_in, sizeof(float) * (size_t)n));
-    hipError_t e = hipMalloc(&d_out, sizeof(float2) * (size_t)n);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in, angles_deg, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->hs.stream);
-    if (e == hipSuccess) {
-        launch_tap_sincos(d_in, n, d_out, c->hs.stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(cos_sin, d_out, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->hs.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->hs.stream);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    ORB_TRY(e);
+    DevBuf in, out; // freed on every return
+    ORB_TRY(need_exact<float>(in, (size_t)n));
+    ORB_TRY(need_exact<float2>(out, (size_t)n));
+    ORB_TRY(hipMemcpyAsync(in.p, angles_deg, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->hs.stream));
+    launch_tap_sincos(in.as<float>(), n, out.as<float2>(), c->hs.stream);
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(cos_sin, out.p, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->hs.stream));
+    ORB_TRY(hipStreamSynchronize(c->hs.stream));
     return ORBX_OK;
 }
 

@@ -276,14 +276,48 @@ def test_fast_dense_corners_and_tiny_thresholds(oracle_mod, ini, mn, kind, varia
 
 
 def test_blur_tap_variant_and_handle_reuse(oracle_mod):
-    """the plain-rounded (sum 257) Gaussian tap set, and one handle used for several frame sizes in turn"""
-    from monoorbslam3_amd.extractor import ORBExtractor
+    """the plain-rounded (sum 257) Gaussian tap set, and one handle made for single frames taken through every way its
+    buffers grow: frame size up and down, the records written into the mapped pinned block and copied back, batches of 1,
+    9, B and 1 frames (B: a record block above the 4 MiB the pinned mirror is kept for), the device entry point with more
+    frames than that, then a smaller frame again.  The first and last frame of every call equal the oracle."""
+    import torch
+    from monoorbslam3_amd.extractor import ORBExtractor, KP_DTYPE
     ex = ORBExtractor(700, 1.2, 8, 20, 7, blur_variant=1)
     orc = oracle_mod.Oracle(700, 1.2, 8, 20, 7, blur_variant=1)
     for (w, h) in ((480, 270), (800, 300), (480, 270)):
         img = synth.make_frames(1, w, h, seed=w)[0]
         kps, desc = ex(img)
         _check_frame(ex, orc, img, kps, desc, stages=True)
+    for zero_copy in (0, 1):  # copied back into the pinned block, then written straight into it again
+        ex.set_variant("zero_copy", zero_copy)
+        img = synth.make_frames(1, 480, 270, seed=11 + zero_copy)[0]
+        kps, desc = ex(img)
+        _check_frame(ex, orc, img, kps, desc, stages=False)
+    w, h = 800, 300
+    cap = ex.max_keypoints(w, h)
+    B = (4 << 20) // (4 + 60 * cap) + 1  # counts, key points and descriptors of B frames: above 4 MiB
+    for n in (1, 9, B, 1):
+        imgs = synth.make_frames(n, w, h, seed=n)
+        out = ex.extract_batch(imgs)
+        for f in sorted({0, n - 1}):
+            _check_frame(ex, orc, imgs[f], out[f][0], out[f][1], frame=f, stages=(n == B and f == n - 1))
+    n = B + 4  # the device entry point grows the buffers past what the host calls asked for
+    imgs = synth.make_frames(n, w, h, seed=n)
+    d_img = torch.from_numpy(imgs).cuda()
+    d_kp = torch.zeros((n, cap, 28), dtype=torch.uint8, device="cuda")
+    d_desc = torch.zeros((n, cap, 32), dtype=torch.uint8, device="cuda")
+    d_n = torch.zeros(n, dtype=torch.int32, device="cuda")
+    ex.extract_batch_device(d_img.data_ptr(), n, w, h, w, w * h, d_kp.data_ptr(), d_desc.data_ptr(), cap, d_n.data_ptr())
+    ex.synchronize()
+    counts, kp, desc = d_n.cpu().numpy(), d_kp.cpu().numpy(), d_desc.cpu().numpy()
+    for f in (0, n - 1):
+        got = kp[f, :counts[f]].copy().view(KP_DTYPE).reshape(-1)
+        _check_frame(ex, orc, imgs[f], got, desc[f, :counts[f]], frame=f, stages=(f == n - 1))
+    for zero_copy in (0, 1):  # the record block is laid out again for n frames: no pinned mirror, both settings copy back
+        ex.set_variant("zero_copy", zero_copy)
+        img = synth.make_frames(1, 480, 270, seed=21 + zero_copy)[0]
+        kps, desc = ex(img)
+        _check_frame(ex, orc, img, kps, desc, stages=(zero_copy == 1))
 
 
 @pytest.mark.parametrize("w,h", [(1242, 375), (752, 480), (1920, 1080), (331, 77), (161, 40), (640, 9 * 4)])
