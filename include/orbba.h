@@ -142,6 +142,14 @@ int orbba_pose_optimize_batch_device(const orbba_pose_problem *p, orbba_pose_res
 int orbba_pose_edges_device(int n2, int nq, const int32_t *d_frame_mp, const void *d_kps, const float *d_q_points,
                             int32_t *d_edge_off, double *d_points, double *d_edge_z, double *d_edge_inv_sigma2,
                             int32_t *d_edge_kp, void *stream);
+/* poseOptimize's last step (Optimize.cpp:531-537) on the device: for every edge e < d_edge_off[1] (the count
+ * orbba_pose_edges_device left in device memory) with d_inlier[e] == 0 (as orbba_pose_optimize_batch_device leaves it), the
+ * frame loses the map point: d_frame_mp[d_edge_kp[e]] = -1.  Nothing else is written; edges past d_edge_off[1] are ignored, and
+ * so is an edge whose d_edge_kp lies outside [0, n2).  n2 = the length of d_frame_mp, which bounds the edges as well.  This is
+ * what lets the second stage of Tracking.cpp:386-427 start on the device: orbm_project_frustum_device (orbm.h) treats every index
+ * that d_frame_mp still holds as matched.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+int orbba_pose_drop_outliers_device(int n2, const int32_t *d_edge_off, const int32_t *d_edge_kp, const uint8_t *d_inlier,
+                                    int32_t *d_frame_mp, void *stream);
 
 /* Kernel-choice switches (parity twins; no reference counterpart).  The BA entry points take no handle, so a switch holds
  * for the process and is read per call.  Unknown switch / value out of range: ORBX_E_ARG. */

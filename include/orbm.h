@@ -266,6 +266,88 @@ int orbm_search_fuse_device(orbm_t *h, const uint8_t *d_q_desc, const float *d_q
                             const int32_t *d_cell_items, int grid_cols, int grid_rows, const float *d_sigma2, int list_cap,
                             int32_t *d_best_idx, int32_t *d_best_dist, int32_t *d_result, void *stream);
 
+/* ---- Projection-search queries built on the device -------------------------------------------------------------------------
+ * The three builders below turn a map-point table and a pose, both in device memory, into the query arrays the three projection
+ * searches above take (d_q_xy, d_q_radius, d_q_level / d_q_octave, d_q_angle, d_q_ok, in their layouts), so that a search whose
+ * queries depend on a pose the device has just computed -- the second stage of Tracking.cpp:386-427 reads the pose that
+ * orbba_pose_optimize_batch_device left -- needs no read-back, host loop and upload.  They are for callers that keep a map-point
+ * table on the device; the reference-signature shims (compat/ORBMatcher.h) keep their host loop over MapPoint objects.
+ *
+ * Camera: a host struct, copied into the launch's arguments.  min_x .. max_y are the bounds isInImage tests with `<` / `>=`
+ * (Pinhole.cpp:44-47; Fisheye.cpp:75-78: pass 0, width, 0, height).
+ * Pose: d_pose_R (9 doubles, row major) / d_pose_t (3 doubles) as orbba_pose_optimize_batch_device writes them.  The kernel rounds
+ * them to float first (the reference's Pose is Matrix3f / Vector3f, Optimize.cpp:528-529); everything after that is float.
+ * Map points, structure of arrays with nq entries: d_points [nq][3] getPos(), d_valid [nq] (non-null and not bad), and for the
+ * frustum and fuse forms d_normals [nq][3] getAverageDirection(), d_min_dist / d_max_dist [nq] get{Min,Max}DistanceInvariance().
+ * Level tables (frustum, fuse): scale_factors (host, n_levels <= 16 floats, ORBExtractor::getScaleFactors()) and
+ * log_scale_factor (getLogScaleFactor()), copied into the launch's arguments.
+ *
+ * Arithmetic (float, -ffp-contract=off: no fused multiply-add), fixed so that it can be checked bit for bit:
+ *   Pc_k  = ((R_k0 * x + R_k1 * y) + R_k2 * z) + t_k                          Pose::map (R * Pw + t)
+ *   O_w_k = -((R_0k * t_0 + R_1k * t_1) + R_2k * t_2)                         Pose.cpp:12-14
+ *   OP = Pw - O_w;  dist = sqrtf((ox * ox + oy * oy) + oz * oz);  OP . Pn = (ox * nx + oy * ny) + oz * nz
+ *   Pinhole  u = fx * (X / Z) + cx, v = fy * (Y / Z) + cy                     Pinhole.cpp:34-38
+ *   Fisheye  a = X / Z, b = Y / Z, r = sqrtf(a * a + b * b), theta = atanf(r),
+ *            theta_d = (((theta + k0 * theta3) + k1 * theta5) + k2 * theta7) + k3 * theta9,
+ *            u = ((fx * theta_d) * a) / r + cx                                Fisheye.cpp:52-66 (r = 0 gives NaN, which isInImage lets pass, as there)
+ *   level = clamp(ceil(logf(max_dist / dist) / log_scale_factor), 0, n_levels - 1)     MapPoint.cpp:159-170
+ * Division and square root are the correctly rounded ones; logf and atanf are the device library's, which are not correctly
+ * rounded: a level may differ from another logf's where log(max_dist / dist) / log_scale_factor is within rounding of an integer.
+ *
+ * Outputs: a query that is switched off has q_ok = 0 and zeros in every other array.  d_result (int32 x 8, device, written --
+ * not accumulated -- by the call): [0] queries switched on, then one count per gate that rejected a point, in the reference's
+ * order of tests (a point is counted at the first gate that rejects it); unused entries are 0.
+ * One launch of one workgroup per call (a few thousand points are latency-bound); the frustum form keeps its "already in the
+ * frame" mask in LDS, so no builder uses handle scratch, allocates or waits on the host; a builder followed by its search on the
+ * same handle and stream is the intended use.  nq <= 524288 (ORBX_E_UNSUPPORTED above: the mask is one bit per point in 64 KB).
+ * Arguments are checked first (ORBX_E_ARG); without a HIP device the call fails with ORBX_E_NO_DEVICE.  nq = 0 is allowed.
+ * Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+typedef struct orbm_proj_camera {
+    int32_t model;                    /* 0 = Pinhole (modules/Sensor/Pinhole.cpp), 1 = Fisheye (Kannala-Brandt, modules/Sensor/Fisheye.cpp) */
+    float fx, fy, cx, cy;
+    float k[4];                       /* Fisheye dist_coeffs k1..k4; ignored by Pinhole */
+    float min_x, max_x, min_y, max_y; /* isInImage: p.x < min_x || p.x >= max_x || p.y < min_y || p.y >= max_y is outside */
+} orbm_proj_camera;
+
+/* Frame / key frame -> frame: the per-feature part of SearchByProjection(lastFrame | lastKF, curFrame, th) ahead of the window
+ * (modules/ORB/ORBMatcher.cpp:212-229, :276-348; compat/ORBMatcher.h projectionFromFrame).  Point i belongs to feature i of the
+ * last frame, whose orbx_kp records are d_kps1: skip if !d_valid[i] (:214-217); Pc = R Pw + t; reject Pc.z < 0 (:221); project;
+ * reject outside the image (:224); then q_xy = p, q_radius = th * kps1[i].size, q_octave = kps1[i].octave, q_angle = kps1[i].angle.
+ * d_result: [0] on, [1] invalid, [2] negative depth, [3] outside the image. */
+int orbm_project_frame_device(orbm_t *h, const orbm_proj_camera *cam, const double *d_pose_R, const double *d_pose_t,
+                              const float *d_points, const uint8_t *d_valid, const void *d_kps1, int nq, float th,
+                              float *d_q_xy, float *d_q_radius, int32_t *d_q_octave, float *d_q_angle, uint8_t *d_q_ok,
+                              int32_t *d_result, void *stream);
+
+/* Local map -> frame: the loop of Tracking.cpp:403-412 with Frame::isInFrustum (modules/BasicObject/Frame.cpp:129-166) and the
+ * radius rule of ORBMatcher.cpp:360-365.  d_frame_mp [n2] is the frame's map-point slot per key point in the shared index space
+ * orbba_pose_edges_device documents: a point whose index occurs in it is already matched in this frame and is switched off (the
+ * `last_frame_seen == current_frame->id` test of Tracking.cpp:404; entries outside [0, nq) are ignored) -- run
+ * orbba_pose_drop_outliers_device first, so that the points poseOptimize dropped no longer count as matched.
+ * Gates in order: positive depth (Frame.cpp:137), in image (:140), min_dist <= dist <= max_dist (:148),
+ * viewCos = OP . Pn / dist >= view_cos_limit (:152-153).  Then level = predictScaleLevel(dist) (:156),
+ * q_radius = (th * (viewCos > 0.998 ? 2.5f : 4.f)) * scale_factors[level] (the comparison in double, as ORBMatcher.cpp:363).
+ * d_view_cos [nq] (may be NULL) receives track_view_cos.
+ * d_result: [0] on (numToMatch, Tracking.cpp:408), [1] invalid, [2] already in the frame, [3] negative depth, [4] outside the image,
+ * [5] distance, [6] viewing angle, [7] outView (Tracking.cpp:410) = [3] + [4] + [5] + [6]. */
+int orbm_project_frustum_device(orbm_t *h, const orbm_proj_camera *cam, const double *d_pose_R, const double *d_pose_t,
+                                const float *d_points, const uint8_t *d_valid, const float *d_normals, const float *d_min_dist,
+                                const float *d_max_dist, int nq, const int32_t *d_frame_mp, int n2, const float *scale_factors,
+                                int n_levels, float log_scale_factor, float th, float view_cos_limit, float *d_q_xy,
+                                float *d_q_radius, int32_t *d_q_level, uint8_t *d_q_ok, float *d_view_cos, int32_t *d_result,
+                                void *stream);
+
+/* Map points -> key frame: the tests of the static fuse SearchByProjection(keyFrame, mapPoints, Map*, th) that read no mutable
+ * state (ORBMatcher.cpp:536-553).  The three that do (:534: null / bad / already observed by the key frame) stay with the caller
+ * through d_valid, as in compat/ORBMatcher.h.  Gates in order: positive depth (:538), in image (:541), distance (:547),
+ * OP . Pn < 0.5 * dist rejects (:550).  level = predictScaleLevel(dist), q_radius = th * scale_factors[level] (:552-553).
+ * d_result: [0] on, [1] invalid, [2] negative depth, [3] outside the image, [4] distance, [5] viewing angle. */
+int orbm_project_fuse_device(orbm_t *h, const orbm_proj_camera *cam, const double *d_pose_R, const double *d_pose_t,
+                             const float *d_points, const uint8_t *d_valid, const float *d_normals, const float *d_min_dist,
+                             const float *d_max_dist, int nq, const float *scale_factors, int n_levels, float log_scale_factor,
+                             float th, float *d_q_xy, float *d_q_radius, int32_t *d_q_level, uint8_t *d_q_ok, int32_t *d_result,
+                             void *stream);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

@@ -186,6 +186,17 @@ def pose_edges_device(n2, nq, d_frame_mp, d_kps, d_q_points, d_edge_off, d_point
                   d_z.data_ptr(), d_w.data_ptr(), d_edge_kp.data_ptr() if d_edge_kp is not None else None, st))
 
 
+def pose_drop_outliers_device(n2, d_edge_off, d_edge_kp, d_inlier, d_frame_mp, stream=None):
+    """orbba_pose_drop_outliers_device on torch device tensors (Optimize.cpp:531-537): frame_mp[edge_kp[e]] = -1 for every edge
+    e < edge_off[1] that pose_optimize_batch_device left with inlier[e] == 0."""
+    import torch
+    L = _lib.lib()
+    fn = L.orbba_pose_drop_outliers_device
+    fn.restype, fn.argtypes = C.c_int, [C.c_int] + [C.c_void_p] * 5
+    st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(fn(n2, d_edge_off.data_ptr(), d_edge_kp.data_ptr(), d_inlier.data_ptr(), d_frame_mp.data_ptr(), st))
+
+
 def pose_optimize_batch_device(cam, d_R, d_t, d_edge_off, d_points, d_z, d_w, d_R_out, d_t_out, d_inlier, d_n_inliers, d_chi2,
                                n_frames=1, huber_delta=HUBER_MONO, stream=None):
     """orbba_pose_optimize_batch_device: every array a torch device tensor (float64 / int32 / uint8), nothing copied."""

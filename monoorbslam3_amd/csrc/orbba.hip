@@ -1341,6 +1341,28 @@ extern "C" int orbba_pose_edges_device(int n2, int nq, const int32_t *d_frame_mp
     ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
+// the outliers of poseOptimize leave the frame (Optimize.cpp:531-538): frame_mp[vecIndices[e]] = nullptr
+__global__ __launch_bounds__(256) void k_pose_drop_outliers(int n2, const int32_t *__restrict__ edge_off, const int32_t *__restrict__ edge_kp,
+                                                            const uint8_t *__restrict__ inlier, int32_t *__restrict__ frame_mp)
+{
+    const int ne = min(edge_off[1], n2); // (one edge per key point at most: the arrays hold n2 entries)
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < ne; e += gridDim.x * 256) {
+        const int i = edge_kp[e];
+        if (!inlier[e] && i >= 0 && i < n2) frame_mp[i] = -1;
+    }
+}
+extern "C" int orbba_pose_drop_outliers_device(int n2, const int32_t *d_edge_off, const int32_t *d_edge_kp, const uint8_t *d_inlier,
+                                               int32_t *d_frame_mp, void *stream)
+{
+    if (n2 < 0 || !d_edge_off || !d_edge_kp || !d_inlier || !d_frame_mp) return orbx_set_error(ORBX_E_ARG, "bad argument");
+    if (int rc = orb_need_device()) return rc;
+    if (n2 == 0) return ORBX_OK;
+    // the edge count is on the device: a grid for n2 edges, at most 16 workgroups (the stride loop serves the rest)
+    hipLaunchKernelGGL(k_pose_drop_outliers, dim3(std::min((n2 + 255) / 256, 16)), dim3(256), 0, (hipStream_t)stream, n2, d_edge_off,
+                       d_edge_kp, d_inlier, d_frame_mp);
+    ORB_TRY(hipGetLastError());
+    return ORBX_OK;
+}
 extern "C" int orbba_pose_optimize_batch_device(const orbba_pose_problem *p, orbba_pose_result *r, void *stream)
 {
     if (!p || !r) return orbx_set_error(ORBX_E_ARG, "null argument");

@@ -21,6 +21,7 @@
 #include "../../include/orbx.h"
 #include "orb_host.h"
 #include "orb_math.h"
+#include "orbm_internal.h"
 
 typedef unsigned long long u64;
 
@@ -1450,6 +1451,8 @@ extern "C" void orbm_destroy(orbm_t *c)
     c->hs.destroy();
     delete c;
 }
+
+hipError_t orbm_device_call(orbm_t *c, hipStream_t s) { return c->hs.device_call(s); } // orbm_internal.h
 
 extern "C" int orbm_hamming_matrix_device(orbm_t *c, const uint8_t *d_a, int na, const uint8_t *d_b, int nb,
                                           uint16_t *d_out, void *stream)

@@ -22,6 +22,20 @@ class _Fv(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("node_ids", C.c_void_p), ("offsets", C.c_void_p), ("indices", C.c_void_p)]
 
 
+class ProjCamera(C.Structure):
+    """orbm_proj_camera (include/orbm.h): the camera of the query builders, every field a float as in the reference's Camera."""
+    _fields_ = [("model", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("k", C.c_float * 4), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float)]
+
+    @classmethod
+    def make(cls, cam, bounds):
+        """cam = (fx, fy, cx, cy) -> Pinhole, (fx, fy, cx, cy, k1, k2, k3, k4) -> Fisheye (as ba._cam_tail); bounds = (min_x, max_x,
+        min_y, max_y) of isInImage -- for Fisheye (0, width, 0, height)."""
+        assert len(cam) in (4, 8) and len(bounds) == 4
+        k = tuple(cam[4:]) if len(cam) == 8 else (0.0, 0.0, 0.0, 0.0)
+        return cls(1 if len(cam) == 8 else 0, cam[0], cam[1], cam[2], cam[3], (C.c_float * 4)(*k), *bounds)
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -65,6 +79,11 @@ def _mlib():
             "orbm_search_for_triangulation_device": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
                                                            vp, vp]),
             "orbm_window_lists_device": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+            "orbm_project_frame_device": (i32, [vp, C.POINTER(ProjCamera), vp, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
+            "orbm_project_frustum_device": (i32, [vp, C.POINTER(ProjCamera), vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, f32, f32,
+                                                  f32, vp, vp, vp, vp, vp, vp, vp]),
+            "orbm_project_fuse_device": (i32, [vp, C.POINTER(ProjCamera), vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, vp, vp, vp,
+                                               vp, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -297,6 +316,38 @@ class ORBMatcher:
             _lib.check(self._L.orbm_search_by_projection_points_device(
                 self._hd._h, self.nn_ratio, p("q_desc"), p("q_xy"), p("q_radius"), p("q_level"), p("q_ok"), nq, p("kps2"),
                 p("desc2"), p("cell_start"), p("cell_items"), grid_cols, grid_rows, n2, list_cap, p("frame_mp"), p("result"), st))
+
+    # -- the queries of those searches built on the device from a map-point table and a pose (orbm_project_*_device) ----------
+    def ProjectFrameDevice(self, cam, d, nq, th, stream=None):
+        """orbm_project_frame_device (ORBMatcher.cpp:212-229): cam a ProjCamera.  d: dict of torch device tensors -- pose_R f64 [9],
+        pose_t f64 [3] (as pose_optimize_batch_device leaves them), points f32 [nq,3], valid u8, kps1 (the last frame's records, u8
+        [*,28]) in; q_xy, q_radius, q_level (the octave), q_angle, q_ok and result i32 [8] out: the keys SearchByProjectionDevice
+        ("frame") reads, so the same dict serves both calls.  Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_project_frame_device(
+            self._hd._h, C.byref(cam), p("pose_R"), p("pose_t"), p("points"), p("valid"), p("kps1"), nq, th, p("q_xy"), p("q_radius"),
+            p("q_level"), p("q_angle"), p("q_ok"), p("result"), _lib.stream_arg(stream)))
+
+    def ProjectFrustumDevice(self, cam, d, nq, n2, scale_factors, log_scale_factor, th, view_cos_limit=0.5, stream=None):
+        """orbm_project_frustum_device (Tracking.cpp:403-412, Frame.cpp:129-166, ORBMatcher.cpp:360-365).  d as for
+        ProjectFrameDevice without kps1 / q_angle, plus normals f32 [nq,3], min_dist, max_dist f32 and frame_mp i32 [n2] in (points
+        whose index it holds are off) and, optionally, view_cos f32 [nq] out.  scale_factors: host floats, at most 16."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+        _lib.check(self._L.orbm_project_frustum_device(
+            self._hd._h, C.byref(cam), p("pose_R"), p("pose_t"), p("points"), p("valid"), p("normals"), p("min_dist"), p("max_dist"), nq,
+            p("frame_mp"), n2, _vp(sf), len(sf), log_scale_factor, th, view_cos_limit, p("q_xy"), p("q_radius"), p("q_level"), p("q_ok"),
+            p("view_cos") if d.get("view_cos") is not None else None, p("result"), _lib.stream_arg(stream)))
+
+    def ProjectFuseDevice(self, cam, d, nq, scale_factors, log_scale_factor, th, stream=None):
+        """orbm_project_fuse_device (ORBMatcher.cpp:534-553): d as for ProjectFrustumDevice without frame_mp / view_cos; `valid`
+        carries the caller's three live tests (null, bad, already observed by the key frame).  The outputs are SearchFuseDevice's."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        sf = np.ascontiguousarray(scale_factors, dtype=np.float32)
+        _lib.check(self._L.orbm_project_fuse_device(
+            self._hd._h, C.byref(cam), p("pose_R"), p("pose_t"), p("points"), p("valid"), p("normals"), p("min_dist"), p("max_dist"), nq,
+            _vp(sf), len(sf), log_scale_factor, th, p("q_xy"), p("q_radius"), p("q_level"), p("q_ok"), p("result"),
+            _lib.stream_arg(stream)))
 
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
