@@ -348,6 +348,69 @@ int orbm_project_fuse_device(orbm_t *h, const orbm_proj_camera *cam, const doubl
                              float th, float *d_q_xy, float *d_q_radius, int32_t *d_q_level, uint8_t *d_q_ok, int32_t *d_result,
                              void *stream);
 
+/* ---- New map points triangulated on the device -------------------------------------------------------------------------------
+ * LocalMapping::createNewMapPoints (modules/Frontend/LocalMapping.cpp:146-259) between SearchForTriangulation and the fuse: for
+ * every feature i of key frame 1 (the older one) with d_matches12[i] = m in [0, n2) -- anything else is "no match" --
+ * TwoViewReconstruction::Triangulate (TwoViewReconstruction.cpp:689-705), the gates of LocalMapping.cpp:187-241 in their order and,
+ * for a match that passes, what the MapPoint constructor and MapPoint::update() leave (MapPoint.cpp:16-30, :43-76), appended to a
+ * map-point table in the layout the builders above read.  Key frame 2 is current_kf, the new point's reference key frame.
+ * orbm_search_for_triangulation_device -> this call -> orbm_project_fuse_device on one stream needs no host hop; the key frames of
+ * one mapper step are coupled through d_has_mp2 (a feature of the current key frame that received a point is skipped by the next
+ * search, ORBMatcher.cpp:452, :466), which this call sets.  The baseline / median-depth skip (:163-165) and the Map / KeyFrame
+ * bookkeeping (:243-248) stay with the caller.
+ *
+ * Inputs.  cam, poses (9 + 3 doubles each, rounded to float first), orbx_kp records as for the builders above; key frame 1's pose
+ * is (d_pose_R1, d_pose_t1).  d_fisheye_scale: the reference's scale_mat (Fisheye.cpp:21-30), scale_h rows of scale_w floats in
+ * device memory, read at [(int) y][(int) x] with the index kept inside the table; NULL (and the sizes ignored) for Pinhole only.
+ * d_desc2 [n2][32].  sigma2: host, n_levels <= 16 floats, ORBExtractor::getSquareSigmas(), indexed by the key point's octave
+ * (kept inside the table); max_scale_factor = getMaxScaleFactor().  The three thresholds of the reference: cos_parallax = 0.99998
+ * and chi2 = 5.991 (double literals there, hence doubles here), ratio_factor = 1.5f * getScaleFactor(1).
+ *
+ * Arithmetic (float, no fused multiply-add; `/` and sqrtf correctly rounded; project() as documented above):
+ *   back-projection  xn = (x - cx) * inv_fx, yn = (y - cy) * inv_fy, inv_fx = 1.f / fx; Fisheye: xn * s, yn * s   Pinhole.cpp:40-42, Fisheye.cpp:68-73
+ *   A row 0 / 1 = xn1 * P1.row(2) - P1.row(0) / yn1 * P1.row(2) - P1.row(1), rows 2 / 3 the same of key frame 2, P = [R | t]
+ *   Ph = the right singular vector of A's smallest singular value (a one-sided Jacobi in float: not bit-reproducible by another
+ *        SVD; see csrc/orbm_triangulate.hip); Ph.w == 0: triangulate fail; Pw = Ph.xyz / Ph.w
+ *   O_w as above;  n_v = Pw - O_v, dist_v = sqrtf((x * x + y * y) + z * z), n_v = n_v / dist_v
+ *   cosParallax = (n1x * n2x + n1y * n2y) + n1z * n2z, rejected when (double) cosParallax > cos_parallax
+ *   Pc = R Pw + t as above, rejected when Pc.z <= 0;  e = (u - x) * (u - x) + (v - y) * (v - y), rejected when
+ *        (double) e > (double) sigma2[octave] * chi2
+ *   distRatio = dist1 / dist2, levelRatio = sqrtf(sigma2[octave2]) / sqrtf(sigma2[octave1]), rejected when
+ *        distRatio * ratio_factor < levelRatio || distRatio > levelRatio * ratio_factor
+ *   normal = (n1 + n2) / 2.f;  span = dist2 * kp2.size;  max_dist = 1.2f * span;  min_dist = 0.8f * (span / max_scale_factor)
+ *
+ * Outputs.  The accepted matches in ascending i -- the reference's creation order -- become the rows *d_n_points, *d_n_points + 1,
+ * ... of the table: d_points [cap_points][3], d_valid = 1, d_normals [..][3], d_min_dist / d_max_dist (the ...Invariance values,
+ * MapPoint.cpp:83-91), d_desc [..][32] = key frame 2's descriptor row (:28), d_obs [..][2] = (i, m); the row index goes to
+ * d_mp1[i] and d_mp2[m] (the key frames' map-point slots, LocalMapping.cpp:245-246; other entries untouched), d_has_mp1[i] =
+ * d_has_mp2[m] = 1, and *d_n_points advances.  Rows below the old *d_n_points are not touched.  d_code [n1] (may be NULL)
+ * receives the gate code of every feature: -1 no match, 0 accepted, else the index of the counter below.
+ * d_result (int32 x 8, written, not accumulated): [0] accepted (numGood), [1] = 1 when the accepted matches do not fit behind
+ * *d_n_points in cap_points rows -- found before anything is written: the table, the slots, the flags and the counter are then as
+ * passed, [0] is 0, and only d_code and d_result were written --, [2] triangulate fail, [3] illegal (non-finite), [4] small
+ * parallax, [5] negative depth (either key frame), [6] re-projection error (either), [7] scale inconsistent.
+ * One launch of one workgroup; no handle scratch, allocation or host wait.  d_desc2 and d_desc must be 4-byte aligned.
+ * Arguments are checked first (ORBX_E_ARG); without a HIP device the call fails with ORBX_E_NO_DEVICE.  n1 = 0 and a call without
+ * any match are allowed.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+int orbm_triangulate_matches_device(orbm_t *h, const orbm_proj_camera *cam, const float *d_fisheye_scale, int scale_w, int scale_h,
+                                    const double *d_pose_R1, const double *d_pose_t1, const double *d_pose_R2, const double *d_pose_t2,
+                                    const void *d_kps1, int n1, const void *d_kps2, const uint8_t *d_desc2, int n2,
+                                    const int32_t *d_matches12, const float *sigma2, int n_levels, float max_scale_factor,
+                                    double cos_parallax, double chi2, float ratio_factor, int32_t *d_n_points, int cap_points,
+                                    float *d_points, uint8_t *d_valid, float *d_normals, float *d_min_dist, float *d_max_dist,
+                                    uint8_t *d_desc, int32_t *d_obs, int32_t *d_mp1, int32_t *d_mp2, uint8_t *d_has_mp1,
+                                    uint8_t *d_has_mp2, int32_t *d_code, int32_t *d_result, void *stream);
+/* The same with host pointers throughout (fisheye_scale included), for a caller built on the reference's host objects: synchronous
+ * on the handle's stream, one pinned copy each way (the key points' scale entries are gathered on the host, the new rows only
+ * come back).  Same bytes as the device entry point. */
+int orbm_triangulate_matches(orbm_t *h, const orbm_proj_camera *cam, const float *fisheye_scale, int scale_w, int scale_h,
+                             const double *pose_R1, const double *pose_t1, const double *pose_R2, const double *pose_t2,
+                             const void *kps1, int n1, const void *kps2, const uint8_t *desc2, int n2, const int32_t *matches12,
+                             const float *sigma2, int n_levels, float max_scale_factor, double cos_parallax, double chi2,
+                             float ratio_factor, int32_t *n_points, int cap_points, float *points, uint8_t *valid, float *normals,
+                             float *min_dist, float *max_dist, uint8_t *desc, int32_t *obs, int32_t *mp1, int32_t *mp2,
+                             uint8_t *has_mp1, uint8_t *has_mp2, int32_t *code, int32_t *result);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

@@ -1454,6 +1454,15 @@ extern "C" void orbm_destroy(orbm_t *c)
 
 hipError_t orbm_device_call(orbm_t *c, hipStream_t s) { return c->hs.device_call(s); } // orbm_internal.h
 
+hipError_t orbm_host_stage(orbm_t *c, size_t bytes, void **dev, void **pinned, hipStream_t *s) // orbm_internal.h
+{
+    hipError_t e = c->hs.host_call();
+    if (e == hipSuccess) e = need(c->w_in, bytes);
+    if (e == hipSuccess) e = need(c->h_in, bytes);
+    *dev = c->w_in.p, *pinned = c->h_in.p, *s = c->hs.stream;
+    return e;
+}
+
 extern "C" int orbm_hamming_matrix_device(orbm_t *c, const uint8_t *d_a, int na, const uint8_t *d_b, int nb,
                                           uint16_t *d_out, void *stream)
 {

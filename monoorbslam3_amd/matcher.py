@@ -84,6 +84,10 @@ def _mlib():
                                                   f32, vp, vp, vp, vp, vp, vp, vp]),
             "orbm_project_fuse_device": (i32, [vp, C.POINTER(ProjCamera), vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, f32, f32, vp, vp, vp,
                                                vp, vp, vp]),
+            "orbm_triangulate_matches_device": (i32, [vp, C.POINTER(ProjCamera), vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp,
+                                                      i32, f32, C.c_double, C.c_double, f32, vp, i32] + [vp] * 14),
+            "orbm_triangulate_matches": (i32, [vp, C.POINTER(ProjCamera), vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32,
+                                               f32, C.c_double, C.c_double, f32, vp, i32] + [vp] * 13),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -348,6 +352,50 @@ class ORBMatcher:
             self._hd._h, C.byref(cam), p("pose_R"), p("pose_t"), p("points"), p("valid"), p("normals"), p("min_dist"), p("max_dist"), nq,
             _vp(sf), len(sf), log_scale_factor, th, p("q_xy"), p("q_radius"), p("q_level"), p("q_ok"), p("result"),
             _lib.stream_arg(stream)))
+
+    # -- createNewMapPoints between SearchForTriangulation and the fuse (LocalMapping.cpp:171-253) ----------------------------
+    def TriangulateMatchesDevice(self, cam, d, n1, n2, cap_points, sigma2, max_scale_factor, ratio_factor, cos_parallax=0.99998,
+                                 chi2=5.991, stream=None):
+        """orbm_triangulate_matches_device: cam a ProjCamera.  d: dict of torch device tensors -- pose_R1, pose_t1 (key frame 1, the
+        older one), pose_R2, pose_t2 f64; kps1, kps2 (orbx_kp records), desc2 u8 [n2,32], matches12 i32 [n1] (as
+        SearchForTriangulationDevice leaves it); fisheye_scale f32 [h,w] (Fisheye only); in / out: n_points i32 [1], the table
+        points f32 [cap,3], valid u8, normals f32 [cap,3], min_dist, max_dist f32, desc u8 [cap,32], obs i32 [cap,2], the slots mp1
+        i32 [n1], mp2 i32 [n2], the flags has_mp1, has_mp2 u8 (the keys SearchForTriangulationDevice reads); out: code i32 [n1]
+        (optional), result i32 [8].  sigma2: host floats, at most 16.  Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        s2 = np.ascontiguousarray(sigma2, dtype=np.float32)
+        sc = d.get("fisheye_scale")
+        _lib.check(self._L.orbm_triangulate_matches_device(
+            self._hd._h, C.byref(cam), sc.data_ptr() if sc is not None else None, sc.shape[1] if sc is not None else 0,
+            sc.shape[0] if sc is not None else 0, p("pose_R1"), p("pose_t1"), p("pose_R2"), p("pose_t2"), p("kps1"), n1, p("kps2"), p("desc2"),
+            n2, p("matches12"), _vp(s2), len(s2), max_scale_factor, cos_parallax, chi2, ratio_factor, p("n_points"), cap_points, p("points"),
+            p("valid"), p("normals"), p("min_dist"), p("max_dist"), p("desc"), p("obs"), p("mp1"), p("mp2"), p("has_mp1"), p("has_mp2"),
+            p("code") if d.get("code") is not None else None, p("result"), _lib.stream_arg(stream)))
+
+    def TriangulateMatches(self, cam, t, kps1, kps2, desc2, matches12, pose1, pose2, sigma2, max_scale_factor, ratio_factor,
+                           cos_parallax=0.99998, chi2=5.991, fisheye_scale=None):
+        """orbm_triangulate_matches on numpy arrays.  t: the table and the key frames' state, a dict of C-contiguous numpy arrays
+        changed IN PLACE -- n_points i32 [1], points, valid, normals, min_dist, max_dist, desc, obs, mp1, mp2, has_mp1, has_mp2 (types
+        as for TriangulateMatchesDevice).  pose1 / pose2 = (R, t).  Returns (code i32 [n1], result i32 [8])."""
+        k1 = np.ascontiguousarray(kps1, dtype=KP_DTYPE)
+        k2 = np.ascontiguousarray(kps2, dtype=KP_DTYPE)
+        d2 = np.ascontiguousarray(desc2, dtype=np.uint8)
+        m12 = np.ascontiguousarray(matches12, dtype=np.int32)
+        pose = [np.ascontiguousarray(a, dtype=np.float64) for a in (pose1[0], pose1[1], pose2[0], pose2[1])]
+        s2 = np.ascontiguousarray(sigma2, dtype=np.float32)
+        sc = None if fisheye_scale is None else np.ascontiguousarray(fisheye_scale, dtype=np.float32)
+        types = dict(n_points=np.int32, points=np.float32, valid=np.uint8, normals=np.float32, min_dist=np.float32, max_dist=np.float32,
+                     desc=np.uint8, obs=np.int32, mp1=np.int32, mp2=np.int32, has_mp1=np.uint8, has_mp2=np.uint8)
+        for k, dt in types.items():
+            assert t[k].dtype == dt and t[k].flags["C_CONTIGUOUS"], k
+        code, result = np.zeros(len(k1), np.int32), np.zeros(8, np.int32)
+        _lib.check(self._L.orbm_triangulate_matches(
+            self._hd._h, C.byref(cam), None if sc is None else _vp(sc), 0 if sc is None else sc.shape[1], 0 if sc is None else sc.shape[0],
+            _vp(pose[0]), _vp(pose[1]), _vp(pose[2]), _vp(pose[3]), _vp(k1), len(k1), _vp(k2), _vp(d2), len(k2), _vp(m12), _vp(s2), len(s2),
+            max_scale_factor, cos_parallax, chi2, ratio_factor, _vp(t["n_points"]), len(t["valid"]), _vp(t["points"]), _vp(t["valid"]),
+            _vp(t["normals"]), _vp(t["min_dist"]), _vp(t["max_dist"]), _vp(t["desc"]), _vp(t["obs"]), _vp(t["mp1"]), _vp(t["mp2"]),
+            _vp(t["has_mp1"]), _vp(t["has_mp2"]), _vp(code), _vp(result)))
+        return code, result
 
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
