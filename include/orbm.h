@@ -411,6 +411,84 @@ int orbm_triangulate_matches(orbm_t *h, const orbm_proj_camera *cam, const float
                              float *min_dist, float *max_dist, uint8_t *desc, int32_t *obs, int32_t *mp1, int32_t *mp2,
                              uint8_t *has_mp1, uint8_t *has_mp2, int32_t *code, int32_t *result);
 
+/* ---- Map points refreshed on the device ----------------------------------------------------------------------------------------
+ * The writer of the map-point table the builders and the triangulation above read (d_points, d_valid, d_normals, d_min_dist,
+ * d_max_dist, d_desc; cap_points rows, rows at or above cap_points do not exist): what the reference does with
+ * `mp->computeDescriptor(); mp->update();` (MapPoint.cpp:103-152, :43-76) for every point of a new key frame (LocalMapping.cpp:93-105),
+ * of the current key frame after the fuse (:304-315) and of every bundle adjustment (Optimize.cpp:89, :440, :948, :1305), plus the
+ * counting loop of the KeyFrame::updateConnections that follows it (KeyFrame.cpp:233-242) and KeyFrame::computeSceneMedianDepth
+ * (KeyFrame.cpp:159-179) for the baseline test ahead of the triangulation (LocalMapping.cpp:163-165).  A caller that keeps the table
+ * on the device no longer reads it back after a fuse or a BA.  There is deliberately NO host-pointer twin: the reference-signature
+ * shims (compat/) keep their host objects, and orbm_distinctive_descriptors below stays for them.
+ *
+ * Key frames: a host struct of device pointers, copied into the launch's arguments like orbm_proj_camera.  Poses are rounded to
+ * float first, as everywhere in this header.  d_kps[k] / d_desc[k] are key frame k's records as orbx_extract_batch_device /
+ * orbf_frame_post_device leave them (descriptor rows 4-byte aligned), d_n[k] their number, d_bad[k] != 0 <=> KeyFrame::isBad().
+ *
+ * Observations of the table's rows in CSR form: row p's are d_obs_kf / d_obs_kp [d_obs_off[p] .. d_obs_off[p + 1]) (d_obs_off has
+ * cap_points + 1 entries, the two arrays n_obs), a (key-frame slot, feature index) pair each; d_ref_kf[p] is the slot of
+ * reference_kf.  The reference's std::map<shared_ptr<KeyFrame>, size_t> iterates in heap-address order, which no restatement can
+ * reproduce: THE CSR ORDER IS THE ORDER, for the normal's sum and for the descriptor's first-on-ties rule.
+ * Nothing of this is trusted.  An observation whose key-frame slot is outside [0, n_kf) or whose feature is outside [0, d_n[kf])
+ * is dropped -- it takes part in nothing below -- and counted, never dereferenced; offsets that do not describe a list inside
+ * [0, n_obs] (negative, descending, past the end) give an empty list.
+ *
+ * d_sel [n_sel] lists the rows to refresh: a key frame's slot array as d_mp2 of the triangulation leaves it, or the point list of
+ * a BA.  Entries outside [0, cap_points) (the -1s) are skipped, rows with d_valid == 0 are skipped and counted (MapPoint.cpp:50,
+ * :108), duplicates are allowed (the row is written twice with the same bytes).  For a selected row with n remaining observations
+ * (float, no fused multiply-add; `/` and sqrtf correctly rounded):
+ *   O_k      = the camera centre of key frame k, O_w_k = -((R_0k * t_0 + R_1k * t_1) + R_2k * t_2) as above
+ *   d_j      : v = Pw - O;  len = sqrtf((vx * vx + vy * vy) + vz * vz);  d_j = len > 0 ? v / len : v            Eigen's normalized()
+ *   normal   = s / (float) n,  s = ((0 + d_0) + d_1) + ... per component in CSR order; bad key frames take part   MapPoint.cpp:57-63, :73
+ *   dist     = sqrtf(...) of Pw - O_ref;  kp = the feature of the first observation with kf == d_ref_kf[p], or feature 0 of the
+ *              reference key frame when there is none (obs[refKeyFrame] through map::operator[]);  span = dist * kp.size;
+ *   d_max_dist = 1.2f * span;  d_min_dist = 0.8f * (span / max_scale_factor)        :66-72, :83-91 -- the triangulation's expressions
+ *   d_desc[p] = the descriptor row, gathered through kf->d_desc, of the observation of least median Hamming distance to the rows
+ *              of all observations whose key frame is not bad: median = sorted[(N - 1) / 2] with the self distance included, strict
+ *              `<` from 256, first in CSR order on ties (:103-152, the rule of orbm_distinctive_descriptors); left as it was when
+ *              every observer is bad (:122).
+ * Left ENTIRELY untouched and counted: a row with n == 0 (the reference would divide by zero), a row with more than 1024
+ * observations, and a row whose d_ref_kf is outside [0, n_kf) or names an unobserved key frame without a feature 0.
+ *
+ * d_covis (may be NULL) [n_kf], written, not accumulated: for every selected valid row -- per entry of d_sel, so a duplicate
+ * counts twice, as the reference's loop over a key frame's slots does, and whether or not the row was left untouched -- and each
+ * remaining observation with kf != kf_self, d_covis[kf]++.  CONNECT_TH, the sort and the graph edits stay with the caller.
+ * d_result (int32 x 8, written): [0] rows refreshed, [1] skipped invalid, [2] untouched: no usable observation, [3] untouched: over
+ * 1024 observations, [4] observations dropped for an index out of range (of every selected valid row), [5] refreshed rows whose
+ * descriptor was left as it was: every observer bad, [6] refreshed rows whose reference key frame was not among their observations,
+ * [7] untouched: no reference key frame feature to read.
+ * Cost: one wave per selected row, four to a workgroup, 8 KB of LDS per workgroup, so the common list of 2-15 observations does not
+ * pay for the longest: a list of more than 64 observations re-gathers its descriptors in tiles of 64 (9 * (n / 64)^2 tile loads).
+ * Every path gives the same bytes.  No scratch memory, handle scratch, allocation or host wait.  d_desc must be 4-byte aligned.
+ * Arguments are checked first (ORBX_E_ARG); without a HIP device the call fails with ORBX_E_NO_DEVICE.  n_sel = 0 is allowed (d_covis
+ * and d_result are zeroed).  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+typedef struct orbm_kf_table {
+    int32_t n_kf;
+    const double *d_pose_R, *d_pose_t;   /* [n_kf][9] / [n_kf][3] */
+    const uint8_t *d_bad;                /* [n_kf] KeyFrame::isBad() */
+    const void *const *d_kps;            /* [n_kf] device pointers to orbx_kp records */
+    const uint8_t *const *d_desc;        /* [n_kf] device pointers to [n][32] descriptors, 4-byte aligned */
+    const int32_t *d_n;                  /* [n_kf] features per key frame */
+} orbm_kf_table;
+int orbm_refresh_points_device(orbm_t *h, const orbm_kf_table *kf, const int32_t *d_sel, int n_sel, const float *d_points,
+                               const uint8_t *d_valid, int cap_points, float *d_normals, float *d_min_dist, float *d_max_dist,
+                               uint8_t *d_desc, const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs,
+                               const int32_t *d_ref_kf, float max_scale_factor, int kf_self, int32_t *d_covis, int32_t *d_result,
+                               void *stream);
+
+/* KeyFrame::computeSceneMedianDepth (KeyFrame.cpp:159-179) for n_kf key frames in one launch, a workgroup each.  Key frame k's
+ * map-point slots are d_slots[k * stride ..], min(d_n[k], stride) of them; every slot in [0, cap_points) contributes (the reference
+ * tests non-null only, not bad) z = ((R_20 * x + R_21 * y) + R_22 * z) + t_2.  d_count[k] = their number, d_median[k] = the element
+ * d_count[k] / 2 of the ascending order -- an exact selection on order-preserving keys, the value a sort returns (-0 orders below
+ * +0) -- and NaN when the count is 0 (the reference reads past an empty vector).  With cur >= 0 and d_baseline != NULL also
+ * d_baseline[k] = sqrtf(...) of O_cur - O_k (LocalMapping.cpp:163); the test baseline / median < 0.01 stays with the caller, who
+ * reads n_kf pairs back once.  stride <= ORBM_MEDIAN_MAX_STRIDE (ORBX_E_UNSUPPORTED above: the keys live in LDS); cur < n_kf.
+ * Arguments are checked first; no device: ORBX_E_NO_DEVICE; n_kf = 0 is allowed.  Enqueued on `stream`; no scratch, no host wait. */
+#define ORBM_MEDIAN_MAX_STRIDE 8192   /* ORBV_MAX_FEATURES */
+int orbm_scene_median_depth_device(orbm_t *h, int n_kf, const double *d_pose_R, const double *d_pose_t, const int32_t *d_slots,
+                                   const int32_t *d_n, int stride, const float *d_points, int cap_points, int cur, float *d_median,
+                                   int32_t *d_count, float *d_baseline, void *stream);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

@@ -36,6 +36,32 @@ class ProjCamera(C.Structure):
         return cls(1 if len(cam) == 8 else 0, cam[0], cam[1], cam[2], cam[3], (C.c_float * 4)(*k), *bounds)
 
 
+class KfTable(C.Structure):
+    """orbm_kf_table (include/orbm.h): a host struct of device pointers to the key frames the refresh reads."""
+    _fields_ = [("n_kf", C.c_int32), ("d_pose_R", C.c_void_p), ("d_pose_t", C.c_void_p), ("d_bad", C.c_void_p), ("d_kps", C.c_void_p),
+                ("d_desc", C.c_void_p), ("d_n", C.c_void_p)]
+
+    @classmethod
+    def make(cls, pose_R, pose_t, bad, kps, desc, n):
+        """torch device tensors: pose_R f64 [n_kf,9], pose_t f64 [n_kf,3], bad u8 [n_kf], n i32 [n_kf]; kps / desc either int64
+        [n_kf] tensors of device addresses or lists of per-key-frame tensors (their addresses are uploaded)."""
+        import torch
+        n_kf = int(n.shape[0])
+
+        def pointers(x):
+            if isinstance(x, (list, tuple)):
+                assert len(x) == n_kf
+                return torch.tensor([t.data_ptr() for t in x], dtype=torch.int64).to(n.device), x
+            assert x.dtype == torch.int64 and x.shape[0] == n_kf
+            return x, None
+
+        pk, keep_k = pointers(kps)
+        pd, keep_d = pointers(desc)
+        t = cls(n_kf, pose_R.data_ptr(), pose_t.data_ptr(), bad.data_ptr(), pk.data_ptr(), pd.data_ptr(), n.data_ptr())
+        t._keep = (pose_R, pose_t, bad, pk, pd, n, keep_k, keep_d)
+        return t
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -88,6 +114,9 @@ def _mlib():
                                                       i32, f32, C.c_double, C.c_double, f32, vp, i32] + [vp] * 14),
             "orbm_triangulate_matches": (i32, [vp, C.POINTER(ProjCamera), vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32,
                                                f32, C.c_double, C.c_double, f32, vp, i32] + [vp] * 13),
+            "orbm_refresh_points_device": (i32, [vp, C.POINTER(KfTable), vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, i32,
+                                                 vp, vp, vp]),
+            "orbm_scene_median_depth_device": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -396,6 +425,28 @@ class ORBMatcher:
             _vp(t["normals"]), _vp(t["min_dist"]), _vp(t["max_dist"]), _vp(t["desc"]), _vp(t["obs"]), _vp(t["mp1"]), _vp(t["mp2"]),
             _vp(t["has_mp1"]), _vp(t["has_mp2"]), _vp(code), _vp(result)))
         return code, result
+
+    # -- mp->computeDescriptor(); mp->update(); updateConnections' counts; computeSceneMedianDepth, on the device table ----------
+    def RefreshPointsDevice(self, kf, d, n_sel, cap_points, n_obs, max_scale_factor, kf_self=-1, stream=None):
+        """orbm_refresh_points_device: kf a KfTable.  d: dict of torch device tensors -- sel i32 [n_sel] (table rows; -1 = none), the
+        table points f32 [cap,3], valid u8 in, normals f32 [cap,3], min_dist, max_dist f32, desc u8 [cap,32] in / out (the keys of
+        TriangulateMatchesDevice and the builders); obs_off i32 [cap + 1], obs_kf, obs_kp i32 [n_obs] (CSR: its order is the order),
+        ref_kf i32 [cap]; out: covis i32 [n_kf] (optional: updateConnections' counts, kf_self left out), result i32 [8].
+        Enqueues on `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_refresh_points_device(
+            self._hd._h, C.byref(kf), p("sel"), n_sel, p("points"), p("valid"), cap_points, p("normals"), p("min_dist"), p("max_dist"),
+            p("desc"), p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, p("ref_kf"), max_scale_factor, kf_self,
+            p("covis") if d.get("covis") is not None else None, p("result"), _lib.stream_arg(stream)))
+
+    def SceneMedianDepthDevice(self, d, n_kf, stride, cap_points, cur=-1, stream=None):
+        """orbm_scene_median_depth_device: d = dict(pose_R f64 [n_kf,9], pose_t f64 [n_kf,3], slots i32 [n_kf,stride] (map-point rows,
+        -1 = none), n i32 [n_kf], points f32 [cap,3]; out: median f32 [n_kf], count i32 [n_kf] and, optionally with cur >= 0, baseline
+        f32 [n_kf] = |O_cur - O_k|).  stride <= 8192.  Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_scene_median_depth_device(
+            self._hd._h, n_kf, p("pose_R"), p("pose_t"), p("slots"), p("n"), stride, p("points"), cap_points, cur, p("median"), p("count"),
+            p("baseline") if d.get("baseline") is not None else None, _lib.stream_arg(stream)))
 
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
