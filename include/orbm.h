@@ -489,6 +489,97 @@ int orbm_scene_median_depth_device(orbm_t *h, int n_kf, const double *d_pose_R, 
                                    const int32_t *d_n, int stride, const float *d_points, int cap_points, int cur, float *d_median,
                                    int32_t *d_count, float *d_baseline, void *stream);
 
+/* ---- Observations built and key frames culled on the device -------------------------------------------------------------------
+ * The one link of the mapper step that the three sections above left on the host: the CSR the refresh reads, rebuilt from the key
+ * frames' slot arrays, and LocalMapping::KeyFrameCulling (modules/Frontend/LocalMapping.cpp:318-372) with the cascade of
+ * KeyFrame::setBad -> MapPoint::eraseObservation -> MapPoint::setBad (KeyFrame.cpp:402-418, MapPoint.cpp:190-226).  With them
+ * triangulate -> build -> fuse -> build -> refresh -> (BA on the host) -> cull runs on one stream without a read-back.  Both are
+ * integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature shims
+ * (compat/) keep their host objects.
+ *
+ * THE SLOT ARRAYS ARE THE TRUTH.  Key frame k's map-point slots are d_slots[k * stride ..], min(d_n[k], stride) of them (the layout
+ * of orbm_scene_median_depth_device; d_mp1 / d_mp2 of the triangulation are such rows), and row p's observations are exactly the
+ * pairs (k, i) with d_slots[k * stride + i] == p.  The CSR (d_obs_off / d_obs_kf / d_obs_kp, as the refresh takes it) is their
+ * inverse, an index that can be rebuilt at any time.  A CSR entry (k, i) of row p is LIVE iff d_slots[k * stride + i] == p and
+ * d_bad[k] == 0.  The refresh's "THE CSR ORDER IS THE ORDER" is hereby ascending (k, i): the reference's std::map iterates in
+ * heap-address order, which nothing reproduces.
+ *
+ * orbm_build_observations_device.  Slot i of key frame k holding p:
+ *   p outside [0, cap_points) (the -1s included)   no map point; not counted
+ *   d_valid[p] == 0                                 skipped, d_result[2]++: a bad point has no observations (MapPoint.cpp:217)
+ *   else d_bad[k] != 0                              skipped, d_result[3]++: KeyFrame::setBad erased them (KeyFrame.cpp:410)
+ *   else                                            the observation (k, i) of row p
+ * (a d_n[k] <= 0 gives key frame k no slot).  d_obs_off receives cap_points + 1 offsets, d_obs_kf / d_obs_kp the n_obs =
+ * d_obs_off[cap_points] entries, every row's list in ascending (k, i); entries at and past n_obs are not written.  The bytes are
+ * the same on every run: count into d_obs_off, scan, scatter the keys k * ORBM_MEDIAN_MAX_STRIDE + i behind the rows' cursors --
+ * the cursor of row p is d_obs_off[p + 1] itself, which the scatter advances from the row's start to its end, the final value --
+ * and then SORT every list on its key, one wave per row, four to a workgroup, by rank (the number of smaller keys of the list, read
+ * in tiles of 64), so the order the atomics came in never reaches the output.  A sort was chosen over a stable placement because
+ * the latter needs a count per (block of slots, row), which is scratch of the order of the table.  NO scratch memory and no handle
+ * scratch: d_obs_kp holds the unsorted keys, d_obs_kf receives the sorted ones, and the wave splits them in place.
+ * Two slots (k, i), (k, i') of one key frame naming the same row cannot occur in the reference (addObservation refuses the second,
+ * MapPoint.cpp:184); here both entries are emitted and the row is counted in d_result[5].
+ * Overflow: n_obs > cap_obs is found after the count and before anything is scattered; d_obs_kf / d_obs_kp are then untouched and
+ * d_obs_off is ALL ZEROS -- every list is empty, so a refresh enqueued behind it changes nothing -- and d_result[1] = 1.
+ * d_result (int32 x 8, written, not accumulated): [0] n_obs (the full count, also on overflow), [1] overflow, [2] slots skipped: row
+ * invalid, [3] slots skipped: key frame bad, [4] the longest list, [5] rows in which a key frame occurs more than once (0 on
+ * overflow: it is found by the sort), [6] rows with more than 1024 observations (the refresh leaves those untouched), [7] 0.
+ * Limits (ORBX_E_UNSUPPORTED above): stride <= ORBM_MEDIAN_MAX_STRIDE; n_kf <= 262143 (n_kf * ORBM_MEDIAN_MAX_STRIDE fits in int32);
+ * cap_points <= 524288, the builders' limit.  n_kf = 0 is allowed and gives all-zero offsets.
+ * Cost: five launches (clear, count, a one-workgroup scan over cap_points + 1 offsets, scatter, sort); a list of n entries costs
+ * n * ceil(n / 64) lane reads in the sort, so the common list of 2-15 is one pass of one wave.  Kernels: no scratch memory; static
+ * LDS 72 B (the scan) and none elsewhere; at most 32 VGPRs.
+ * Arguments are checked first (ORBX_E_ARG); without a HIP device the call fails with ORBX_E_NO_DEVICE.  Enqueued on `stream` (NULL:
+ * orbx.h, "Streams"); no allocation, no host wait. */
+int orbm_build_observations_device(orbm_t *h, int n_kf, const int32_t *d_n, const uint8_t *d_bad, const int32_t *d_slots, int stride,
+                                   const uint8_t *d_valid, int cap_points, int cap_obs, int32_t *d_obs_off, int32_t *d_obs_kf,
+                                   int32_t *d_obs_kp, int32_t *d_result, void *stream);
+
+/* LocalMapping::KeyFrameCulling with its cascade.  recent / timestamps: HOST arrays, copied into the launch's arguments as
+ * orbm_proj_camera is: the key-frame slots of Map::getRecentKeyFrames(25) in that order and their timestamps, n_recent <= 32
+ * (ORBX_E_UNSUPPORTED above); an entry outside [0, kf->n_kf) is an argument error.  first_kf: the slot of the key frame with id 0,
+ * or -1.  The reference's constants: th_obs = 3, redundant_ratio = 0.9, max_gap = 1.5 (double literals there, hence doubles here).
+ * Of kf the kernel uses d_kps and d_n only; d_bad is in / out and may be the array kf->d_bad points to.  d_slots, d_valid as above,
+ * in / out; d_ref_kf [cap_points] (the refresh's) in / out.  The CSR is the one orbm_build_observations_device left from these slots;
+ * it is never rewritten and read with the refresh's distrust: offsets that do not describe a list inside [0, n_obs] give an empty
+ * list; an entry whose key frame is outside [0, n_kf) or whose feature is outside [0, min(d_n[k], stride)) is dropped, never
+ * dereferenced (d_result[6] counts such entries once each, over all of [0, n_obs)).  Liveness is evaluated against d_slots and d_bad
+ * as they are NOW, so a stale CSR entry is harmless.
+ *
+ * Candidates idx = 1 .. n_recent - 2 strictly in order, last = 0 (n_recent < 3: no candidate -- not the reference's size_t
+ * underflow).  For c = recent[idx]:
+ *   c == first_kf                                              skipped, d_code 1                                     :329
+ *   else timestamps[idx + 1] - timestamps[last] > max_gap      skipped, d_code 2                                     :330
+ *   numMP        = slots i of c with p = d_slots[..] in [0, cap_points) and d_valid[p] != 0                          :341
+ *   numRedundant = those of them whose row has more than th_obs live entries (getNumObs()) and at least th_obs live entries
+ *                  (k2, i2) with k2 != c and octave(k2, i2) <= octave(c, i) + 1, octaves from the orbx_kp records; the `break` of
+ *                  :355 only caps the count, so no order enters                                                      :344-359
+ *   (double) numRedundant > redundant_ratio * (double) numMP false: kept, d_code 0, last = idx                       :364
+ *   else culled, d_code 3, last unchanged: d_bad[c] = 1; then for every row p named by a slot of c with p in range and d_valid[p]
+ *        != 0 -- ONCE per row, should two slots of c name it -- the observation (c, .) is erased (MapPoint.cpp:190-208): with
+ *        L = the live entries of p of key frames other than c, in CSR order,
+ *          d_ref_kf[p] == c and L not empty: d_ref_kf[p] = the key frame of L's first entry (observations.begin(), :198-199);
+ *          |L| <= 2: the point goes bad (:202, :210-226): d_valid[p] = 0 and d_slots[k2 * stride + i2] = -1 for every entry of L;
+ *        finally every slot of c, whatever it holds, becomes -1 (map_points.clear(), KeyFrame.cpp:418).
+ * Each candidate sees what the ones before it wrote.  The covisibility-graph and spanning-tree edits of KeyFrame::setBad and
+ * Map::eraseMapPoint stay with the caller, who reads d_code.
+ * d_code [n_recent]: -1 at positions 0 and n_recent - 1, else as above; d_num_mp / d_num_redundant [n_recent]: 0 where not evaluated.
+ * d_result (int32 x 8, written): [0] culled, [1] kept, [2] skipped, [3] points set bad, [4] slots cleared in key frames other than
+ * the culled one, [5] d_ref_kf entries reassigned, [6] CSR entries dropped for an index out of range, [7] 0.
+ * Shape: ONE launch of ONE workgroup of 1024 threads, a thread per slot of the candidate, workgroup barriers between the phases --
+ * the candidates are sequential and the work (<= 23 candidates x <= 8192 slots x short lists) is latency, as in k_project /
+ * k_triangulate; inside a candidate the slots are independent, because a point's cascade touches only that point's slots.  The
+ * once-per-row rule is a claim mask of one bit per table row in dynamic LDS (cap_points / 8 bytes, hence cap_points <= 524288,
+ * ORBX_E_UNSUPPORTED above; stride <= ORBM_MEDIAN_MAX_STRIDE likewise).  No scratch memory, handle scratch, allocation or host wait;
+ * static LDS 40 B; at most 64 VGPRs.
+ * Arguments are checked first (ORBX_E_ARG; th_obs >= 0, first_kf in [-1, n_kf)); without a HIP device the call fails with
+ * ORBX_E_NO_DEVICE.  n_recent = 0 is allowed.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, uint8_t *d_bad, int32_t *d_slots, int stride, uint8_t *d_valid,
+                               int cap_points, const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs,
+                               int32_t *d_ref_kf, const int32_t *recent, const double *timestamps, int n_recent, int first_kf,
+                               int th_obs, double redundant_ratio, double max_gap, int32_t *d_code, int32_t *d_num_mp,
+                               int32_t *d_num_redundant, int32_t *d_result, void *stream);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

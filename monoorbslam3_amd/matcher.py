@@ -117,6 +117,9 @@ def _mlib():
             "orbm_refresh_points_device": (i32, [vp, C.POINTER(KfTable), vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32, i32,
                                                  vp, vp, vp]),
             "orbm_scene_median_depth_device": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+            "orbm_build_observations_device": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
+            "orbm_cull_keyframes_device": (i32, [vp, C.POINTER(KfTable), vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32,
+                                                 C.c_double, C.c_double, vp, vp, vp, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -447,6 +450,33 @@ class ORBMatcher:
         _lib.check(self._L.orbm_scene_median_depth_device(
             self._hd._h, n_kf, p("pose_R"), p("pose_t"), p("slots"), p("n"), stride, p("points"), cap_points, cur, p("median"), p("count"),
             p("baseline") if d.get("baseline") is not None else None, _lib.stream_arg(stream)))
+
+    # -- the observation lists behind the refresh, and KeyFrameCulling with its cascade (LocalMapping.cpp:318-372) --------------
+    def BuildObservationsDevice(self, d, n_kf, stride, cap_points, cap_obs, stream=None):
+        """orbm_build_observations_device: d = dict of torch device tensors -- n i32 [n_kf] (slots per key frame), bad u8 [n_kf], slots
+        i32 [n_kf,stride] (map-point rows, -1 = none), valid u8 [cap]; out: obs_off i32 [cap + 1], obs_kf, obs_kp i32 [cap_obs] (the
+        refresh's CSR, every list in ascending (key frame, slot)), result i32 [8] ([0] n_obs, [1] overflow: all offsets zero).
+        Enqueues on `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_build_observations_device(
+            self._hd._h, n_kf, p("n"), p("bad"), p("slots"), stride, p("valid"), cap_points, cap_obs, p("obs_off"), p("obs_kf"),
+            p("obs_kp"), p("result"), _lib.stream_arg(stream)))
+
+    def CullKeyFramesDevice(self, kf, d, stride, cap_points, n_obs, recent, timestamps, first_kf=-1, th_obs=3, redundant_ratio=0.9,
+                            max_gap=1.5, stream=None):
+        """orbm_cull_keyframes_device: kf a KfTable (its d_kps and d_n are read).  d: dict of torch device tensors -- in / out: bad u8
+        [n_kf] (may be the table's), slots i32 [n_kf,stride], valid u8 [cap], ref_kf i32 [cap]; in: obs_off, obs_kf, obs_kp (the CSR
+        BuildObservationsDevice left from these slots); out: code, num_mp, num_redundant i32 [n_recent], result i32 [8].  recent /
+        timestamps: host sequences, the key-frame slots of Map::getRecentKeyFrames(25) and their timestamps (at most 32).
+        Enqueues on `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        rec = np.ascontiguousarray(recent, dtype=np.int32)
+        ts = np.ascontiguousarray(timestamps, dtype=np.float64)
+        assert rec.ndim == 1 and rec.shape == ts.shape
+        _lib.check(self._L.orbm_cull_keyframes_device(
+            self._hd._h, C.byref(kf), p("bad"), p("slots"), stride, p("valid"), cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs,
+            p("ref_kf"), _vp(rec), _vp(ts), len(rec), first_kf, th_obs, redundant_ratio, max_gap, p("code"), p("num_mp"),
+            p("num_redundant"), p("result"), _lib.stream_arg(stream)))
 
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
