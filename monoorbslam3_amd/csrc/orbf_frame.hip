@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/orbf.h"
+#include "orb_device.h"
 #include "orb_host.h"
 #include "orb_math.h"
 
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(256) void k_frame_post(OrbfCam cam, orbx_kp *__rest
                                                     int32_t *__restrict__ tmp)
 {
     extern __shared__ int32_t lds[]; // start[nc + 1], cursor[nc]
-    __shared__ int32_t wave_sum[4];
+    __shared__ int32_t s_wave[4];
     const int f = blockIdx.x, tid = threadIdx.x, nc = cam.cols * cam.rows;
     int32_t *start = lds, *cursor = lds + nc + 1;
     const int n = min(n_kp[f], cap);
@@ -110,16 +111,11 @@ __global__ __launch_bounds__(256) void k_frame_post(OrbfCam cam, orbx_kp *__rest
     const int per = (nc + 255) / 256, c0 = min(tid * per, nc), c1 = min(c0 + per, nc);
     int local = 0;
     for (int c = c0; c < c1; ++c) local += cursor[c];
-    int incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if ((tid & 63) >= o) incl += t;
-    }
-    if ((tid & 63) == 63) wave_sum[tid >> 6] = incl;
+    const int incl = wave_scan(local);
+    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
     __syncthreads();
     int base = incl - local;
-    for (int w = 0; w < (tid >> 6); ++w) base += wave_sum[w];
+    for (int w = 0; w < (tid >> 6); ++w) base += s_wave[w];
     for (int c = c0; c < c1; ++c) {
         const int cnt = cursor[c];
         start[c] = base;

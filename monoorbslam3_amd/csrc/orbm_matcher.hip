@@ -19,6 +19,7 @@
 
 #include "../../include/orbm.h"
 #include "../../include/orbx.h"
+#include "orb_device.h"
 #include "orb_host.h"
 #include "orb_math.h"
 #include "orbm_internal.h"
@@ -644,8 +645,7 @@ __global__ __launch_bounds__(64) void k_medoid(const uint8_t *__restrict__ desc,
         }
         bestkey = min(bestkey, ((uint32_t)lo << 16) | (uint32_t)i);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) bestkey = min(bestkey, (uint32_t)__shfl_xor((int)bestkey, o));
+    bestkey = wave_min(bestkey);
     // bestMedian starts at 256 with a strict '<': a median of 256 never replaces index 0 (:138-146)
     if (lane == 0) best_idx[g] = (bestkey >> 16) >= 256 ? 0 : (int32_t)(bestkey & 0xFFFF);
 }
@@ -666,7 +666,7 @@ __global__ __launch_bounds__(GB_T) void k_grid_build(const orbx_kp *__restrict__
                                                     int32_t *__restrict__ tmp, int32_t *__restrict__ zero_me)
 {
     extern __shared__ int32_t g_lds[]; // start[nc + 1], cursor[nc]
-    __shared__ int32_t wave_sum[GB_T / 64];
+    __shared__ int32_t s_wave[GB_T / 64];
     const int tid = threadIdx.x, nc = cols * rows;
     if (tid == 0 && zero_me) *zero_me = 0; // the next kernel's pool counter
     int32_t *start = g_lds, *cursor = g_lds + nc + 1;
@@ -685,16 +685,11 @@ __global__ __launch_bounds__(GB_T) void k_grid_build(const orbx_kp *__restrict__
     const int per = (nc + GB_T - 1) / GB_T, c0 = min(tid * per, nc), c1 = min(c0 + per, nc);
     int local = 0;
     for (int c = c0; c < c1; ++c) local += cursor[c];
-    int incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if ((tid & 63) >= o) incl += t;
-    }
-    if ((tid & 63) == 63) wave_sum[tid >> 6] = incl;
+    const int incl = wave_scan(local);
+    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
     __syncthreads();
     int base = incl - local;
-    for (int w = 0; w < (tid >> 6); ++w) base += wave_sum[w];
+    for (int w = 0; w < (tid >> 6); ++w) base += s_wave[w];
     for (int c = c0; c < c1; ++c) {
         const int cnt = cursor[c];
         start[c] = base; cell_start[c] = base; cursor[c] = 0;

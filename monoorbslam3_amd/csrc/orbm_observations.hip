@@ -35,6 +35,7 @@
 
 #include "../../include/orbm.h"
 #include "../../include/orbx.h"
+#include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
 
@@ -48,8 +49,6 @@ constexpr int OB_SCAN_T = 1024;         // the scan's one workgroup
 constexpr int OB_WAVES = 4;             // rows in flight per workgroup of the sort
 constexpr int OB_KEY_SHIFT = 13;        // key = k << 13 | i
 constexpr int OB_MAX_KF = 262143;       // (n_kf << 13) fits in int32
-constexpr int OB_MAX_POINTS = 1 << 19;  // the builders' limit (one bit per point in 64 KB)
-constexpr int OB_LONG = 1024;           // the refresh leaves longer lists untouched
 constexpr int CL_T = 1024;              // the culling's one workgroup
 constexpr int CL_MAX_RECENT = 32;
 static_assert(ORBM_MEDIAN_MAX_STRIDE == 1 << OB_KEY_SHIFT, "the sort key packs the slot index into 13 bits");
@@ -57,13 +56,6 @@ static_assert(ORBM_MEDIAN_MAX_STRIDE == 1 << OB_KEY_SHIFT, "the sort key packs t
 // result slots of the build and of the culling
 enum { B_NOBS = 0, B_OVERFLOW = 1, B_INVALID = 2, B_BAD_KF = 3, B_LONGEST = 4, B_TWICE = 5, B_LONG = 6 };
 enum { C_CULLED = 0, C_KEPT = 1, C_SKIPPED = 2, C_POINTS_BAD = 3, C_CLEARED = 4, C_REASSIGNED = 5, C_DROPPED = 6 };
-
-__device__ __forceinline__ int wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ void k_obs_clear(int32_t *__restrict__ off, int n, int32_t *__restrict__ result)
 {
@@ -119,18 +111,12 @@ __global__ __launch_bounds__(OB_SCAN_T) void k_obs_scan(int32_t *__restrict__ of
         const int c = off[j];
         sum += c;
         longest = max(longest, c);
-        n_long += c > OB_LONG;
+        n_long += c > ORBM_MAX_LIST;
     }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if ((tid & 63) >= o) incl += t;
-    }
+    const int incl = wave_scan(sum);
     if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
     n_long = wave_sum(n_long);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o));
+    longest = wave_max(longest);
     if ((tid & 63) == 0) {
         atomicMax(&s_longest, longest);
         if (n_long) atomicAdd(&s_long, n_long);
@@ -370,13 +356,11 @@ extern "C" int orbm_build_observations_device(orbm_t *h, int n_kf, const int32_t
     if (n_kf > 0 && stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
     if (cap_points > 0 && !d_valid) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
     if (cap_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
-    if (stride > ORBM_MEDIAN_MAX_STRIDE) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBM_MEDIAN_MAX_STRIDE (8192) slots per key frame");
+    if (int rc = orbm_check_stride(stride)) return rc;
     if (n_kf > OB_MAX_KF) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 262143 key frames in one call");
-    if (cap_points > OB_MAX_POINTS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 524288 map points in one call");
-    if (int rc = orb_need_device()) return rc;
-    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    if (int rc = orbm_check_points(cap_points)) return rc;
+    hipStream_t s;
+    if (int rc = orbm_begin_device(h, stream, &s)) return rc;
     const int n_off = cap_points + 1;
     hipLaunchKernelGGL(k_obs_clear, dim3(std::min((n_off + 255) / 256, OB_MAX_GRID)), dim3(256), 0, s, d_obs_off, n_off, d_result);
     ORB_TRY(hipGetLastError());
@@ -414,18 +398,15 @@ extern "C" int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, ui
     if (n_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
     if (n_recent > 0 && (!recent || !timestamps || !d_code || !d_num_mp || !d_num_redundant))
         return orbx_set_error(ORBX_E_ARG, "null candidate array");
-    if (((uintptr_t)kf->d_kps) & (sizeof(void *) - 1))
-        return orbx_set_error(ORBX_E_ARG, "the key-frame table's pointer arrays must be pointer aligned");
+    if (int rc = orbm_check_kf_rows(kf->d_kps)) return rc;
     if (first_kf < -1 || first_kf >= kf->n_kf) return orbx_set_error(ORBX_E_ARG, "first_kf is neither -1 nor a key frame of the table");
     if (n_recent > CL_MAX_RECENT) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 32 recent key frames in one call");
-    if (stride > ORBM_MEDIAN_MAX_STRIDE) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBM_MEDIAN_MAX_STRIDE (8192) slots per key frame");
-    if (cap_points > OB_MAX_POINTS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 524288 map points in one call");
+    if (int rc = orbm_check_stride(stride)) return rc;
+    if (int rc = orbm_check_points(cap_points)) return rc;
     for (int i = 0; i < n_recent; ++i)
         if (recent[i] < 0 || recent[i] >= kf->n_kf) return orbx_set_error(ORBX_E_ARG, "an entry of recent is not a key frame of the table");
-    if (int rc = orb_need_device()) return rc;
-    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    hipStream_t s;
+    if (int rc = orbm_begin_device(h, stream, &s)) return rc;
     CullArgs a = {};
     for (int i = 0; i < n_recent; ++i) a.recent[i] = recent[i], a.timestamps[i] = timestamps[i];
     a.n_recent = n_recent, a.first_kf = first_kf, a.th_obs = th_obs, a.redundant_ratio = redundant_ratio, a.max_gap = max_gap;

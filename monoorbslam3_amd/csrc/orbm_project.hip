@@ -34,7 +34,6 @@
 namespace {
 
 constexpr int PJ_T = 1024;              // threads of the one workgroup
-constexpr int PJ_MAX_POINTS = 1 << 19;  // the frustum form's mask: one bit per point in 64 KB of LDS
 
 struct ProjArgs {                       // by value in the launch's arguments
     orbm_proj_camera cam;
@@ -158,17 +157,14 @@ __global__ __launch_bounds__(PJ_T) void k_project(const ProjArgs a, const double
     }
 }
 
-int check_common(const orbm_t *h, const orbm_proj_camera *cam, const void *R, const void *t, const void *points, const void *valid, int nq,
-                 const void *xy, const void *radius, const void *level, const void *ok, const void *result)
+int check_common(orbm_t *h, const orbm_proj_camera *cam, const void *R, const void *t, const void *points, const void *valid, int nq,
+                 const void *xy, const void *radius, const void *level, const void *ok, const void *result, void *stream, hipStream_t *s)
 {
     if (!cam || !R || !t || !points || !valid || !xy || !radius || !level || !ok || !result)
         return orbx_set_error(ORBX_E_ARG, "null argument");
     if (nq < 0) return orbx_set_error(ORBX_E_ARG, "nq is negative");
-    if (cam->model != 0 && cam->model != 1) return orbx_set_error(ORBX_E_ARG, "camera model must be 0 (Pinhole) or 1 (Fisheye)");
-    if (int rc = orb_need_device()) return rc;
-    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
-    if (nq > PJ_MAX_POINTS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 524288 map points in one call");
-    return ORBX_OK;
+    if (int rc = orbm_check_camera(cam)) return rc;
+    return orbm_begin_device(h, stream, s, nq);
 }
 
 int check_levels(const float *scale_factors, int n_levels)
@@ -198,9 +194,8 @@ extern "C" int orbm_project_frame_device(orbm_t *h, const orbm_proj_camera *cam,
                                          int32_t *d_result, void *stream)
 {
     if (!d_kps1 || !d_q_angle) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (int rc = check_common(h, cam, d_pose_R, d_pose_t, d_points, d_valid, nq, d_q_xy, d_q_radius, d_q_octave, d_q_ok, d_result)) return rc;
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    hipStream_t s;
+    if (int rc = check_common(h, cam, d_pose_R, d_pose_t, d_points, d_valid, nq, d_q_xy, d_q_radius, d_q_octave, d_q_ok, d_result, stream, &s)) return rc;
     hipLaunchKernelGGL(k_project<FORM_FRAME>, dim3(1), dim3(PJ_T), 0, s, make_args(cam, nullptr, 1, 1.f, th, 0.f), d_pose_R, d_pose_t,
                        d_points, d_valid, nullptr, nullptr, nullptr, (const orbx_kp *)d_kps1, nullptr, 0, nq, d_q_xy, d_q_radius,
                        d_q_octave, d_q_angle, d_q_ok, nullptr, d_result);
@@ -217,9 +212,8 @@ extern "C" int orbm_project_frustum_device(orbm_t *h, const orbm_proj_camera *ca
 {
     if (!d_normals || !d_min_dist || !d_max_dist || n2 < 0 || (n2 > 0 && !d_frame_mp)) return orbx_set_error(ORBX_E_ARG, "bad argument");
     if (int rc = check_levels(scale_factors, n_levels)) return rc;
-    if (int rc = check_common(h, cam, d_pose_R, d_pose_t, d_points, d_valid, nq, d_q_xy, d_q_radius, d_q_level, d_q_ok, d_result)) return rc;
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    hipStream_t s;
+    if (int rc = check_common(h, cam, d_pose_R, d_pose_t, d_points, d_valid, nq, d_q_xy, d_q_radius, d_q_level, d_q_ok, d_result, stream, &s)) return rc;
     const size_t mask_bytes = (size_t)((nq + 31) >> 5) * 4; // <= 64 KB: no opt-in needed
     hipLaunchKernelGGL(k_project<FORM_FRUSTUM>, dim3(1), dim3(PJ_T), mask_bytes, s,
                        make_args(cam, scale_factors, n_levels, log_scale_factor, th, view_cos_limit), d_pose_R, d_pose_t, d_points, d_valid,
@@ -237,9 +231,8 @@ extern "C" int orbm_project_fuse_device(orbm_t *h, const orbm_proj_camera *cam, 
 {
     if (!d_normals || !d_min_dist || !d_max_dist) return orbx_set_error(ORBX_E_ARG, "null argument");
     if (int rc = check_levels(scale_factors, n_levels)) return rc;
-    if (int rc = check_common(h, cam, d_pose_R, d_pose_t, d_points, d_valid, nq, d_q_xy, d_q_radius, d_q_level, d_q_ok, d_result)) return rc;
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    hipStream_t s;
+    if (int rc = check_common(h, cam, d_pose_R, d_pose_t, d_points, d_valid, nq, d_q_xy, d_q_radius, d_q_level, d_q_ok, d_result, stream, &s)) return rc;
     hipLaunchKernelGGL(k_project<FORM_FUSE>, dim3(1), dim3(PJ_T), 0, s, make_args(cam, scale_factors, n_levels, log_scale_factor, th, 0.f),
                        d_pose_R, d_pose_t, d_points, d_valid, d_normals, d_min_dist, d_max_dist, nullptr, nullptr, 0, nq, d_q_xy,
                        d_q_radius, d_q_level, nullptr, d_q_ok, nullptr, d_result);

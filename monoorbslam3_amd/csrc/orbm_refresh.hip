@@ -28,6 +28,7 @@
 
 #include "../../include/orbm.h"
 #include "../../include/orbx.h"
+#include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
 
@@ -39,7 +40,6 @@ typedef unsigned long long u64;
 
 constexpr int RF_WAVES = 4;           // waves (= selected rows in flight) per workgroup
 constexpr int RF_T = RF_WAVES * 64;
-constexpr int RF_MAX_OBS = 1024;      // MEDOID_MAX of k_medoid
 constexpr int RF_MAX_GRID = 2048;     // workgroups; the waves stride over the selection beyond that
 constexpr int MD_T = 512;             // threads of a key frame's workgroup
 constexpr int MD_MAX = ORBM_MEDIAN_MAX_STRIDE;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(RF_T) void k_refresh(const orbm_kf_table kf, const 
         }
         // ---- what the reference cannot do is found before anything is written
         if (n == 0) { ++count[R_NONE]; continue; }
-        if (n > RF_MAX_OBS) { ++count[R_LONG]; continue; }
+        if (n > ORBM_MAX_LIST) { ++count[R_LONG]; continue; }
         if (rk < 0 || rk >= kf.n_kf) { ++count[R_REF_MISSING]; continue; }
         if (ref_kp < 0) {                                          // obs[refKeyFrame] through map::operator[]: feature 0
             if (kf.d_n[rk] < 1) { ++count[R_REF_MISSING]; continue; }
@@ -211,12 +211,8 @@ __global__ __launch_bounds__(RF_T) void k_refresh(const orbm_kf_table kf, const 
                 }
                 if (row && lo < my_median) my_median = lo, my_row = r0 + lane;   // rows ascend per lane: strict '<' keeps the first
             }
-            int median = my_median;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) median = min(median, __shfl_xor(median, o));
-            int at = my_median == median ? my_row : 0x7fffffff;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) at = min(at, __shfl_xor(at, o));
+            const int median = wave_min(my_median);
+            const int at = wave_min(my_median == median ? my_row : 0x7fffffff);
             if (median < 256) best = __builtin_amdgcn_readfirstlane(at);   // bestMedian starts at 256 with a strict '<' (:138-146)
         }
         if (lane < 8) {
@@ -318,12 +314,9 @@ extern "C" int orbm_refresh_points_device(orbm_t *h, const orbm_kf_table *kf, co
         return orbx_set_error(ORBX_E_ARG, "null map-point table array");
     if (n_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
     if (((uintptr_t)d_desc) & 3) return orbx_set_error(ORBX_E_ARG, "descriptor arrays must be 4-byte aligned");
-    if ((((uintptr_t)kf->d_kps) | ((uintptr_t)kf->d_desc)) & (sizeof(void *) - 1))
-        return orbx_set_error(ORBX_E_ARG, "the key-frame table's pointer arrays must be pointer aligned");
-    if (int rc = orb_need_device()) return rc;
-    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    if (int rc = orbm_check_kf_rows(kf->d_kps, kf->d_desc)) return rc;
+    hipStream_t s;
+    if (int rc = orbm_begin_device(h, stream, &s)) return rc;
     const int n_clear = std::max(d_covis ? kf->n_kf : 0, 8);
     hipLaunchKernelGGL(k_refresh_clear, dim3((n_clear + 255) / 256), dim3(256), 0, s, d_covis, kf->n_kf, d_result);
     ORB_TRY(hipGetLastError());
@@ -345,11 +338,9 @@ extern "C" int orbm_scene_median_depth_device(orbm_t *h, int n_kf, const double 
     if (n_kf > 0 && stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
     if (cap_points > 0 && !d_points) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
     if (cur >= n_kf && d_baseline) return orbx_set_error(ORBX_E_ARG, "cur is not a key frame of the call");
-    if (stride > MD_MAX) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBM_MEDIAN_MAX_STRIDE (8192) slots per key frame");
-    if (int rc = orb_need_device()) return rc;
-    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    if (int rc = orbm_check_stride(stride)) return rc;
+    hipStream_t s;
+    if (int rc = orbm_begin_device(h, stream, &s)) return rc;
     if (n_kf == 0) return ORBX_OK;
     hipLaunchKernelGGL(k_median_depth, dim3(n_kf), dim3(MD_T), 0, s, d_pose_R, d_pose_t, d_slots, d_n, stride, d_points, cap_points, cur,
                        d_median, d_count, d_baseline);

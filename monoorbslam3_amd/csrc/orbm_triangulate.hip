@@ -281,7 +281,7 @@ struct TriCall {   // the arguments both entry points share, checked by check()
     float ratio_factor;
 };
 
-int check(const orbm_t *h, const TriCall &c, const void *scale, int scale_w, int scale_h, const void *R1, const void *t1, const void *R2,
+int check(const TriCall &c, const void *scale, int scale_w, int scale_h, const void *R1, const void *t1, const void *R2,
           const void *t2, const void *kps1, int n1, const void *kps2, const void *desc2, int n2, const void *matches12, const void *n_points,
           int cap_points, const void *points, const void *valid, const void *normals, const void *min_dist, const void *max_dist,
           const void *desc, const void *obs, const void *mp1, const void *mp2, const void *has1, const void *has2, const void *result)
@@ -292,12 +292,10 @@ int check(const orbm_t *h, const TriCall &c, const void *scale, int scale_w, int
     if (n2 > 0 && (!kps2 || !desc2 || !mp2 || !has2)) return orbx_set_error(ORBX_E_ARG, "null key-frame 2 array");
     if (cap_points > 0 && (!points || !valid || !normals || !min_dist || !max_dist || !desc || !obs))
         return orbx_set_error(ORBX_E_ARG, "null map-point table array");
-    if (c.cam->model != 0 && c.cam->model != 1) return orbx_set_error(ORBX_E_ARG, "camera model must be 0 (Pinhole) or 1 (Fisheye)");
+    if (int rc = orbm_check_camera(c.cam)) return rc;
     if (c.cam->model == 1 && (!scale || scale_w < 1 || scale_h < 1)) return orbx_set_error(ORBX_E_ARG, "Fisheye needs its scale table");
     if (c.n_levels < 1 || c.n_levels > ORBX_MAX_LEVELS) return orbx_set_error(ORBX_E_ARG, "n_levels must be 1 .. 16");
     if ((((uintptr_t)desc2) | ((uintptr_t)desc)) & 3) return orbx_set_error(ORBX_E_ARG, "descriptor arrays must be 4-byte aligned");
-    if (int rc = orb_need_device()) return rc;
-    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
     return ORBX_OK;
 }
 
@@ -369,12 +367,12 @@ extern "C" int orbm_triangulate_matches_device(orbm_t *h, const orbm_proj_camera
                                                void *stream)
 {
     const TriCall c = {cam, sigma2, n_levels, max_scale_factor, cos_parallax, chi2, ratio_factor};
-    if (int rc = check(h, c, d_fisheye_scale, scale_w, scale_h, d_pose_R1, d_pose_t1, d_pose_R2, d_pose_t2, d_kps1, n1, d_kps2, d_desc2, n2,
+    if (int rc = check(c, d_fisheye_scale, scale_w, scale_h, d_pose_R1, d_pose_t1, d_pose_R2, d_pose_t2, d_kps1, n1, d_kps2, d_desc2, n2,
                        d_matches12, d_n_points, cap_points, d_points, d_valid, d_normals, d_min_dist, d_max_dist, d_desc, d_obs, d_mp1, d_mp2,
                        d_has_mp1, d_has_mp2, d_result))
         return rc;
-    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
-    ORB_TRY(orbm_device_call(h, s));
+    hipStream_t s;
+    if (int rc = orbm_begin_device(h, stream, &s)) return rc;
     hipLaunchKernelGGL(k_triangulate, dim3(1), dim3(TR_T), 0, s, make_args(c, cam->model == 1 ? scale_w : 0, scale_h, 0), d_pose_R1, d_pose_t1,
                        d_pose_R2, d_pose_t2, (const orbx_kp *)d_kps1, n1, (const orbx_kp *)d_kps2, (const uint32_t *)d_desc2, n2, d_matches12,
                        d_fisheye_scale, d_n_points, cap_points, d_points, d_valid, d_normals, d_min_dist, d_max_dist, (uint32_t *)d_desc, d_obs,
@@ -392,9 +390,11 @@ extern "C" int orbm_triangulate_matches(orbm_t *h, const orbm_proj_camera *cam, 
                                         uint8_t *has_mp1, uint8_t *has_mp2, int32_t *code, int32_t *result)
 {
     const TriCall c = {cam, sigma2, n_levels, max_scale_factor, cos_parallax, chi2, ratio_factor};
-    if (int rc = check(h, c, fisheye_scale, scale_w, scale_h, pose_R1, pose_t1, pose_R2, pose_t2, kps1, n1, kps2, desc2, n2, matches12, n_points,
+    if (int rc = check(c, fisheye_scale, scale_w, scale_h, pose_R1, pose_t1, pose_R2, pose_t2, kps1, n1, kps2, desc2, n2, matches12, n_points,
                        cap_points, points, valid, normals, min_dist, max_dist, desc, obs, mp1, mp2, has_mp1, has_mp2, result))
         return rc;
+    if (int rc = orb_need_device()) return rc;
+    if (!h) return orbx_set_error(ORBX_E_ARG, "null handle");
     const bool fisheye = cam->model == 1;
     const int old_n = *n_points;
     // the rows this call can append: one per match, and no more than the table has left
