@@ -258,7 +258,8 @@ int orbm_search_for_initialization_device(orbm_t *h, float nn_ratio, int check_o
  * device-resident key-frame record (key points, descriptors, CSR grid): KeyFrame::getFeaturesInArea(p, radius, predictLevel - 1,
  * predictLevel) with its strict window test, the chi-square gate of :566-567 (d_sigma2 = the level table of square sigmas, indexed
  * by the key point's octave) and the closest descriptor below TH_LOW + 1.  d_best_idx [nq] (-1 = none) / d_best_dist [nq]; what
- * the reference does with a hit (:577-589) mutates its objects and stays with the caller (compat/ORBMatcher.h).
+ * the reference does with a hit (:577-589) mutates its objects and stays with the caller (compat/ORBMatcher.h), or with
+ * orbm_fuse_apply_device below for a caller that keeps the slot arrays on the device.
  * d_result (int32 x 8): [0] points with a hit, [1] = 1 if a window held more than list_cap hits (that point's answer is then
  * taken from the first list_cap: repeat with a larger list_cap).  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
 int orbm_search_fuse_device(orbm_t *h, const uint8_t *d_q_desc, const float *d_q_xy, const float *d_q_radius, const int32_t *d_q_level,
@@ -492,7 +493,8 @@ int orbm_scene_median_depth_device(orbm_t *h, int n_kf, const double *d_pose_R, 
 /* ---- Observations built and key frames culled on the device -------------------------------------------------------------------
  * The one link of the mapper step that the three sections above left on the host: the CSR the refresh reads, rebuilt from the key
  * frames' slot arrays, and LocalMapping::KeyFrameCulling (modules/Frontend/LocalMapping.cpp:318-372) with the cascade of
- * KeyFrame::setBad -> MapPoint::eraseObservation -> MapPoint::setBad (KeyFrame.cpp:402-418, MapPoint.cpp:190-226).  With them
+ * KeyFrame::setBad -> MapPoint::eraseObservation -> MapPoint::setBad (KeyFrame.cpp:402-418, MapPoint.cpp:190-226).  With them and
+ * orbm_fuse_apply_device (the next section: the searches alone find the fuse's hits, they do not apply them)
  * triangulate -> build -> fuse -> build -> refresh -> (BA on the host) -> cull runs on one stream without a read-back.  Both are
  * integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature shims
  * (compat/) keep their host objects.
@@ -579,6 +581,78 @@ int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, uint8_t *d_ba
                                int32_t *d_ref_kf, const int32_t *recent, const double *timestamps, int n_recent, int first_kf,
                                int th_obs, double redundant_ratio, double max_gap, int32_t *d_code, int32_t *d_num_mp,
                                int32_t *d_num_redundant, int32_t *d_result, void *stream);
+
+/* ---- The fuse's hits applied on the device --------------------------------------------------------------------------------------
+ * What the static fuse SearchByProjection(keyFrame, mapPoints, Map*, th) does with a hit (modules/ORB/ORBMatcher.cpp:574-589):
+ * MapPoint::addObservation + KeyFrame::addMapPoint, or MapPoint::replace (MapPoint.cpp:233-264), on the slot arrays of the section
+ * above.  With it orbm_project_fuse_device -> orbm_search_fuse_device -> this call runs per target key frame of
+ * LocalMapping::searchInNeighbors (LocalMapping.cpp:261-316) without a wait, a read-back, a host loop and an upload, and the chain
+ * triangulate -> build -> fuse -> build -> refresh -> (BA on the host) -> cull exists as that section states it.  THE SLOT ARRAYS ARE
+ * THE TRUTH: an observation is a slot, so addObservation and addMapPoint are ONE store, and replace rewrites the slots that name the
+ * loser.  Integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature
+ * shims (compat/) keep their host objects.
+ * Out of scope, the caller's: the list of fuseMapPoints itself -- the de-duplicated union of the target key frames' slots
+ * (LocalMapping.cpp:287-300) --, Map::eraseMapPoint and the covisibility graph, and MapPointCulling.
+ *
+ * Entries: d_best_idx [nq] as orbm_search_fuse_device leaves it; entry j is table row d_rows[j], or row j when d_rows is NULL (the
+ * builders index the table by query).  kf_target = K, the key frame searched.  d_n, d_bad, d_slots (in / out), stride: the layout of
+ * orbm_build_observations_device.  d_valid (in / out), cap_points: the table.  obs(p) = the pairs (k, i) with d_slots[k * stride + i]
+ * == p, i < min(d_n[k], stride) and d_bad[k] == 0, in ascending (k, i); getNumObs() is its size.
+ *
+ * For j = 0 .. nq - 1 IN ORDER, p = the entry's row, s = d_best_idx[j], n_K = min(max(d_n[K], 0), stride); the first rule that
+ * applies decides (d_code[j]):
+ *   0 none       s < 0
+ *   1 dropped    s >= n_K, or p outside [0, cap_points): counted, nothing is read through it
+ *   2 gated      d_valid[p] == 0, or p is named by one of the n_K slots of K: isObserveKeyFrame, on the slots as they are when entry j
+ *                is reached (:534; orbm_project_fuse_device left these tests to its caller's d_valid)
+ *   3 added      o = d_slots[K * stride + s] is outside [0, cap_points): d_slots[K * stride + s] = p (:576-578)
+ *   4 bad occupant   d_valid[o] == 0: nothing is written (:579 is false), the entry counts as a match (:587)
+ *   5 / 6 replace    otherwise.  The loser L is p when getNumObs(o) > getNumObs(p), strictly (:580; code 5: the list point replaced by
+ *                the occupant), else o (code 6; a tie replaces the occupant); the winner W is the other row.  For every (k, i) of
+ *                obs(L) in order: d_slots[k * stride + i] = W if W has no observation in key frame k at that moment, else -1
+ *                (MapPoint.cpp:249-257; should L hold two slots of one key frame, the first moves and the second is cleared; a slot
+ *                of L in a bad key frame is no observation and stays).  Then d_valid[L] = 0.  Then, with d_found / d_visible
+ *                [cap_points] (int32; both or neither may be NULL), d_found[W] += d_found[L] + d_visible[L]: the reference calls
+ *                increaseFound(numFound) and increaseFound(numVisible) (:259-260), and this is the reference's text, not a
+ *                correction; d_visible is only read.  d_ref_kf is not an argument: replace does not touch reference_kf.
+ *   7 undone     a replace in which the CSR list of p or of o is longer than ORBM_MAX_LIST (1024) entries: left undone and counted,
+ *                as the refresh leaves such rows; the entry counts as a match.
+ * d_refresh_sel [nq]: W for codes 5 / 6 (computeDescriptor on the winner, MapPoint.cpp:261), p for code 3, else -1: behind a rebuilt
+ * CSR it is orbm_refresh_points_device's d_sel with n_sel = nq (the refresh skips -1 and allows duplicates).
+ * d_result (int32 x 8, written, not accumulated): [0] the reference's return value, the entries with a code of 3 or more, [1] the
+ * refusal (below), [2] observations added, [3] list points replaced by the occupant, [4] occupants replaced by the list point, [5]
+ * slots cleared because the winner already observed the key frame, [6] gated, [7] everything dropped or left undone: entries of code
+ * 1 and 7 plus the CSR entries dropped for an index out of range (once each, over all of [0, n_obs), as the culling counts them).
+ *
+ * The observation index: d_obs_off / d_obs_kf / d_obs_kp / n_obs as orbm_build_observations_device left it from THESE slots with no
+ * edit in between.  It only tells where the slots naming a row are; it is never rewritten, and read with the refresh's distrust:
+ * offsets that do not describe a list inside [0, n_obs] give an empty list, an entry whose key frame is outside [0, n_kf) or whose
+ * feature is outside [0, min(d_n[k], stride)) is dropped and counted, never dereferenced, and an entry counts only if its slot
+ * names the row NOW.  A CSR that is not fresh may therefore give a different answer -- observations it does not list are neither
+ * counted nor moved -- but never an access out of bounds.
+ *
+ * Parallelism and the refusal.  Entries that hit different slots of K do not interact if (1) no row occurs in two LIVE entries (an
+ * entry that is not none, dropped or gated on the arrays as passed), (2) no hit slot's valid occupant is named by a second slot of K,
+ * and (3) no live row is an occupant, which the gate ensures.  Then every row belongs to at most one CHAIN, the live entries of one
+ * hit slot in list order, and the gate of an entry is the same on the arrays as passed as when it is reached.  The reference's
+ * callers satisfy both: fuseMapPoints is a set, and addObservation refuses a second slot.  (1) and (2) are checked before anything
+ * is written: on a violation d_result = {0, 1 (a row twice) or 2 (an occupant in two slots; 1 wins), 0 ...} and d_slots, d_valid,
+ * d_found, d_code and d_refresh_sel are EXACTLY as passed (d_work is not).
+ * Shape: ONE launch of ONE workgroup of 1024 threads, as the culling; a mask of one bit per table row in dynamic LDS (cap_points / 8
+ * bytes, hence cap_points <= 524288) for "named by a slot of K" and then for the two premises, plus one int per slot of K (the first
+ * live entry of each hit slot: 4 * stride bytes, stride <= ORBM_MEDIAN_MAX_STRIDE); then a wave per chain, lanes across the lists: the
+ * winner's observations are the live entries of the lists of every row merged into it plus the chain's own slot of K.  d_work [nq]
+ * (int32) is the caller's work array: the entries' classes and the chains' links.  The bytes are the same on every run: counts are
+ * sums, and no stored value depends on the order atomics arrive in.  No scratch memory, handle scratch, allocation or host wait;
+ * static LDS 1064 B; at most 64 VGPRs (sixteen waves in one workgroup: 128 is all a thread could have).
+ * Arguments are checked first (ORBX_E_ARG; kf_target in [0, n_kf)); limits (ORBX_E_UNSUPPORTED): cap_points <= 524288, stride <=
+ * ORBM_MEDIAN_MAX_STRIDE, nq <= 2^30; without a HIP device the call fails with ORBX_E_NO_DEVICE.  nq = 0 is allowed.  Enqueued on
+ * `stream` (NULL: orbx.h, "Streams"). */
+int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, const int32_t *d_rows, int nq, int n_kf, int kf_target,
+                           const int32_t *d_n, const uint8_t *d_bad, int32_t *d_slots, int stride, uint8_t *d_valid, int cap_points,
+                           const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs, int32_t *d_found,
+                           const int32_t *d_visible, int32_t *d_work, int32_t *d_code, int32_t *d_refresh_sel, int32_t *d_result,
+                           void *stream);
 
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,

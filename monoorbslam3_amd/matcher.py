@@ -120,6 +120,7 @@ def _mlib():
             "orbm_build_observations_device": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]),
             "orbm_cull_keyframes_device": (i32, [vp, C.POINTER(KfTable), vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32,
                                                  C.c_double, C.c_double, vp, vp, vp, vp, vp]),
+            "orbm_fuse_apply_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -477,6 +478,21 @@ class ORBMatcher:
             self._hd._h, C.byref(kf), p("bad"), p("slots"), stride, p("valid"), cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs,
             p("ref_kf"), _vp(rec), _vp(ts), len(rec), first_kf, th_obs, redundant_ratio, max_gap, p("code"), p("num_mp"),
             p("num_redundant"), p("result"), _lib.stream_arg(stream)))
+
+    # -- what the fuse does with its hits: addObservation / replace on the slot arrays (ORBMatcher.cpp:574-589) ------------------
+    def FuseApplyDevice(self, d, nq, n_kf, kf_target, stride, cap_points, n_obs, stream=None):
+        """orbm_fuse_apply_device: d = dict of torch device tensors -- in: best_idx i32 [nq] (as SearchFuseDevice leaves it), rows i32
+        [nq] (optional: the table row of every entry; entry j is row j without it), n i32 [n_kf], bad u8 [n_kf], obs_off, obs_kf, obs_kp
+        (the CSR BuildObservationsDevice left from these slots), visible i32 [cap] (optional, with found); in / out: slots i32
+        [n_kf,stride], valid u8 [cap], found i32 [cap] (optional); work i32 [nq] (the call's work array); out: code, refresh_sel i32
+        [nq] (refresh_sel is RefreshPointsDevice's sel behind a rebuilt CSR), result i32 [8] ([0] matches, [1] refusal: nothing
+        written).  Enqueues on `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        opt = lambda k: d[k].data_ptr() if d.get(k) is not None else None  # noqa: E731
+        _lib.check(self._L.orbm_fuse_apply_device(
+            self._hd._h, p("best_idx"), opt("rows"), nq, n_kf, kf_target, p("n"), p("bad"), p("slots"), stride, p("valid"), cap_points,
+            p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, opt("found"), opt("visible"), p("work"), p("code"), p("refresh_sel"),
+            p("result"), _lib.stream_arg(stream)))
 
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
