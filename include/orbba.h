@@ -13,11 +13,14 @@
  * points, dense Cholesky of the reduced pose system, back-substitution, VertexSE3 / Vertex3D updates -- the algorithm
  * of g2o 20201223's OptimizationAlgorithmLevenberg + BlockSolver_6_3 (not vendored in the reference; restated from
  * its published sources, checked against the numpy restatement in oracle/ba_ref.py to a stated tolerance).
- * Everything is IEEE double.  Host pointers in and out.
+ * Everything is IEEE double.  Host pointers in and out, except where an entry point's name ends in _device.
  * Threads (orbx.h, "Streams and threads"): the entry points take no handle and are re-entrant.  The reference runs poseOptimize
  * on the Tracking thread (Tracking.cpp:273-358) while localBundleAdjustment runs on LocalMapping's (LocalMapping.cpp:45-52): every
  * host-pointer call leases a non-blocking stream, a device arena and a page-locked staging block from a per-device pool for its
  * duration -- one copy up, one copy down, one small read-back per LM trial; no stream-0 operation, no allocation in steady state.
+ * The _device entry points take device pointers and enqueue on the caller's stream without a copy or a wait -- with ONE stated
+ * exception, orbba_local_bundle_adjustment_device: the LM loop's accept / reject decision is the host's, so that call waits on the
+ * caller's stream for one small read-back per trial (and leases the pool's arena and staging block, not its stream).
  */
 #ifndef ORBBA_H
 #define ORBBA_H
@@ -96,6 +99,27 @@ int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o, orbba_lm_r
  * orbba_lm_result.chi2) and for every still-active edge whose chi2 at the final estimate exceeds 5.991 -- the
  * observations the reference then erases (:917-935).  outlier may be NULL. */
 int orbba_local_bundle_adjustment(const orbba_problem *p, orbba_lm_result *r, uint8_t *outlier, int device);
+
+/* The same for a caller whose problem lies in DEVICE memory -- orbm_local_ba_problem_device (orbm.h) assembles one from the
+ * device-resident map, and orbm_local_ba_apply_device consumes the outputs: every array pointer of *p, and r->pose_R, r->pose_t,
+ * r->points, r->chi2 and d_outlier (all five required), are DEVICE pointers; the three sizes of *p are HOST ints -- the caller reads
+ * the first 32 bytes of the assembly's d_result back once for them (n_poses, n_points, n_edges; a refusal there means: do not call) --
+ * and the scalar results (iterations, trials, lambda, chi2_initial, chi2_final, device_ms) come back in *r on the host, since the
+ * call waits anyway.  No array travels: the inputs are copied device to device into the leased arena, the index structures the
+ * host form builds on the host (edges per pose in edge order, the points' edge ranges, the free poses and their slots, the free pose
+ * x point table) are built there by kernels, and the demotion mask !(chi2 > 5.991), the stale first-round chi2 of the demoted edges
+ * and the outlier rule are kernels as well.  The LM loop is the host form's, literally: one function runs the same kernels in the
+ * same order on the same index arrays, so poses, points, chi2, outlier, iterations, trials and lambda equal
+ * orbba_local_bundle_adjustment's bit for bit (tests/test_local_ba_gpu.py).
+ * Checks: the host form's -- an edge index out of range, edges not grouped by point, a point observed twice by a key frame, every
+ * pose fixed -- run on the device and arrive with the FIRST read-back (the verdict and the number of free poses, which sizes the
+ * reduced system; one wait more than the host form has): the call then returns ORBX_E_ARG and the outputs are untouched.
+ * ORBX_E_UNSUPPORTED when n_poses * n_points exceeds 2^28 (the host form's limit with every pose taken as free).
+ * THE EXCEPTION to "device entry points do not wait": this call is enqueued on `stream` (hipStream_t; NULL: stream 0 itself) and
+ * WAITS on that stream -- once for the checks, once per LM trial, once at the end -- so work the caller enqueued on the stream before
+ * it has finished when it returns, and so have the outputs.  It runs on the current device and leases the arena and the staging
+ * block of the host-pointer entry points' pool for its duration (no allocation in steady state); re-entrant. */
+int orbba_local_bundle_adjustment_device(const orbba_problem *p, orbba_lm_result *r, uint8_t *d_outlier, void *stream);
 
 /* Optimize::poseOptimize (modules/Backend/Optimize.cpp:444-545) for a batch of frames at once: per frame one
  * VertexSE3 and one EdgeSE3Project3DOnlyPose (G2oTypes.h:209-236, G2oTypes.cpp:27-34) per matched map point; four rounds

@@ -495,7 +495,8 @@ int orbm_scene_median_depth_device(orbm_t *h, int n_kf, const double *d_pose_R, 
  * frames' slot arrays, and LocalMapping::KeyFrameCulling (modules/Frontend/LocalMapping.cpp:318-372) with the cascade of
  * KeyFrame::setBad -> MapPoint::eraseObservation -> MapPoint::setBad (KeyFrame.cpp:402-418, MapPoint.cpp:190-226).  With them and
  * orbm_fuse_apply_device (the next section: the searches alone find the fuse's hits, they do not apply them)
- * triangulate -> build -> fuse -> build -> refresh -> (BA on the host) -> cull runs on one stream without a read-back.  Both are
+ * triangulate -> build -> fuse -> build -> refresh -> local BA -> cull runs on one stream; the local BA ("Local bundle adjustment on the
+ * device-resident map" below) is the one link that waits, for its small read-backs -- nothing else returns to the host.  Both are
  * integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature shims
  * (compat/) keep their host objects.
  *
@@ -587,7 +588,7 @@ int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, uint8_t *d_ba
  * MapPoint::addObservation + KeyFrame::addMapPoint, or MapPoint::replace (MapPoint.cpp:233-264), on the slot arrays of the section
  * above.  With it orbm_project_fuse_device -> orbm_search_fuse_device -> this call runs per target key frame of
  * LocalMapping::searchInNeighbors (LocalMapping.cpp:261-316) without a wait, a read-back, a host loop and an upload, and the chain
- * triangulate -> build -> fuse -> build -> refresh -> (BA on the host) -> cull exists as that section states it.  THE SLOT ARRAYS ARE
+ * triangulate -> build -> fuse -> build -> refresh -> local BA -> cull exists as that section states it.  THE SLOT ARRAYS ARE
  * THE TRUTH: an observation is a slot, so addObservation and addMapPoint are ONE store, and replace rewrites the slots that name the
  * loser.  Integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature
  * shims (compat/) keep their host objects.
@@ -653,6 +654,98 @@ int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, const int32_t *
                            const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs, int32_t *d_found,
                            const int32_t *d_visible, int32_t *d_work, int32_t *d_code, int32_t *d_refresh_sel, int32_t *d_result,
                            void *stream);
+
+/* ---- Local bundle adjustment on the device-resident map --------------------------------------------------------------------------
+ * Optimize::localBundleAdjustment (modules/Backend/Optimize.cpp:766-951) for a caller whose slot arrays, map-point table and key-frame
+ * poses live in device memory, in three calls on one stream:
+ *   orbm_local_ba_problem_device                  :766-889  the local map gathered, vertices and edges built: an orbba_problem in device memory
+ *   orbba_local_bundle_adjustment_device (orbba.h) :892-922  the two rounds of Levenberg-Marquardt on those arrays
+ *   orbm_local_ba_apply_device                    :914-950  outlier observations erased with their cascade, poses and positions written back
+ * Between the first and the second the caller reads the first 32 bytes of the assembly's d_result back ONCE (the three sizes are host
+ * ints of the LM call) and the LM call waits for one small block per trial; no table, slot array or index returns to the host, and
+ * no host loop runs over points or observations.  mp->update() (:948) is orbm_refresh_points_device with d_sel = d_point_row behind a
+ * rebuilt CSR; it is not repeated here.  MapPointCulling and the covisibility graph (getConnectedKFs: d_local) stay with the caller.
+ * The two calls below follow this header's rules for the map side: device pointers only and deliberately NO host-pointer twin; no
+ * allocation, handle scratch or host wait; results written, not accumulated; the same bytes on every run; every index that comes
+ * from device memory is distrusted -- dropped and counted, never dereferenced out of range.  THE SLOT ARRAYS ARE THE TRUTH and the CSR
+ * (as orbm_build_observations_device left it from these slots) only tells where the slots naming a row are: offsets that do not
+ * describe a list inside [0, n_obs] give an empty list, an entry whose key frame is outside [0, n_kf) or whose feature is outside
+ * [0, min(d_n[k], stride)) is dropped (counted once each over all of [0, n_obs)), and an entry is LIVE iff its slot names the row NOW
+ * and its key frame is not bad.
+ *
+ * orbm_local_ba_problem_device.  d_local [n_local] (device): d_local[0] is the current key frame, the rest getConnectedKFs() in the
+ * caller's order.  first_kf: the slot of the key frame with id 0, or -1, as in the culling.
+ *   Local key frames: the entries of d_local in order.  An entry outside [0, n_kf) is dropped (d_result[6]); a later entry whose key
+ *     frame is bad is skipped (:777, d_result[7]); an entry naming a key frame an earlier entry named is dropped (d_result[6]).  Entry 0
+ *     is taken whether or not it is bad.
+ *   Local points (:783-792): the rows p in [0, cap_points) with d_valid[p] != 0 named by one of the min(max(d_n[k], 0), stride) slots
+ *     of a local key frame, each numbered at its FIRST occurrence in (position among the kept local key frames, slot) order -- the
+ *     reference's BA_local_for_kf marking.  A row that ends up without an edge is dropped before numbering (d_result[8]).
+ *   Edges (:860-889): per local point in that order, its LIVE CSR entries in CSR order.  A key frame that occurs a second time in one
+ *     row's list gives no second edge (d_result[9]; the LM refuses a point observed twice by a key frame).  For edge e of point x:
+ *     d_edge_point[e] = x (non-decreasing), d_edge_pose[e] = the pose of the key frame, d_edge_z[2e..] = the orbx_kp record's (x, y)
+ *     widened to double, d_edge_inv_sigma2[e] = (double)((1.f / size) / size) (:877), d_edge_kf / d_edge_kp[e] = (key-frame slot,
+ *     feature); d_edge_off[x] = the point's first edge, d_edge_off[n_points] = n_edges.
+ *   Poses: the kept local key frames in list order, then the fixed ones (:795-806) -- every key frame of an edge that is not local --
+ *     in ASCENDING SLOT ORDER.  That is a stated canonicalisation: the reference's order comes from std::map's heap addresses, and a
+ *     fixed pose has no block in the system, so its position reaches no number.  d_pose_fixed = 1 for those and for a local key frame
+ *     equal to first_kf (:830); d_pose_R / d_pose_t = (double)(float) of the table's values (the reference's Pose is float);
+ *     d_ba_points [x][3] = (double) of d_points[d_point_row[x]]; d_pose_kf [pose] / d_point_row [x] map back to slots and rows.
+ * The output arrays are an orbba_problem (orbba.h) in device memory: d_pose_R [cap_poses][9], d_pose_t [..][3], d_pose_fixed, d_pose_kf
+ * [cap_poses]; d_ba_points [cap_local_points][3], d_point_row [cap_local_points], d_edge_off [cap_local_points + 1]; d_edge_pose,
+ * d_edge_point, d_edge_inv_sigma2, d_edge_kf, d_edge_kp [cap_edges], d_edge_z [cap_edges][2].  d_work: the caller's work array of
+ * cap_points + n_kf int32 (the rows' first occurrences and the key frames' poses; its contents afterwards are unspecified).
+ * d_result (int32 x 16, written; the first eight -- 32 bytes -- are what the caller reads back): [0] n_poses, [1] n_points, [2]
+ * n_edges, [3] local key frames kept (the poses apply writes), [4] fixed key frames, [5] the refusal, a bit mask: 1 more poses than
+ * cap_poses, 2 more points than cap_local_points, 4 more edges than cap_edges, 8 no free pose (no local key frame besides first_kf),
+ * 16 no edge; [6] entries of d_local dropped, [7] skipped for a bad key frame; [8] rows dropped for having no edge, [9] second edges
+ * of a key frame in one row, [10] CSR entries dropped for an index out of range; the rest 0.  On a refusal the counts are still the
+ * FULL counts, no array is written at or past its capacity, and what lies below is unspecified: do not run the LM on it.
+ * Shape: ONE launch of ONE workgroup of 1024 threads with barriers between the phases, as the culling -- 20 key frames x 2000 slots x
+ * short lists are latency: first occurrences by atomicMin (the least key wins whatever the order), then the slots in order, a tile of
+ * 1024 at a time, with a block scan of (has an edge, edges) numbering points and edges.  A row's list is walked twice (count, write)
+ * and a key frame's second entry is found by re-reading the list's start, so a list of n entries costs n^2 / 2 reads by one thread:
+ * nothing for the 2-30 of a map, slow for a forged CSR.  No scratch memory; static LDS 4288 B; at most 64 VGPRs.
+ * Limits (ORBX_E_UNSUPPORTED above): n_local <= ORBM_LOCAL_BA_MAX_LOCAL, stride <= ORBM_MEDIAN_MAX_STRIDE, cap_points <= 524288.
+ * Arguments are checked first (ORBX_E_ARG: n_local and the capacities >= 1, first_kf in [-1, n_kf)); without a HIP device the call fails
+ * with ORBX_E_NO_DEVICE.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+#define ORBM_LOCAL_BA_MAX_LOCAL 1024
+int orbm_local_ba_problem_device(orbm_t *h, const orbm_kf_table *kf, const int32_t *d_slots, int stride, const uint8_t *d_valid,
+                                 const float *d_points, int cap_points, const int32_t *d_obs_off, const int32_t *d_obs_kf,
+                                 const int32_t *d_obs_kp, int n_obs, const int32_t *d_local, int n_local, int first_kf, int cap_poses,
+                                 int cap_local_points, int cap_edges, int32_t *d_work, double *d_pose_R, double *d_pose_t,
+                                 uint8_t *d_pose_fixed, double *d_ba_points, int32_t *d_edge_pose, int32_t *d_edge_point,
+                                 double *d_edge_z, double *d_edge_inv_sigma2, int32_t *d_edge_kf, int32_t *d_edge_kp, int32_t *d_edge_off,
+                                 int32_t *d_point_row, int32_t *d_pose_kf, int32_t *d_result, void *stream);
+
+/* orbm_local_ba_apply_device.  n_local, n_points, n_edges: d_result[3], [1], [2] of the assembly, which the caller read back for the
+ * LM; d_pose_kf, d_point_row, d_edge_off, d_edge_kf, d_edge_kp: the assembly's maps; d_est_pose_R / d_est_pose_t / d_est_points /
+ * d_outlier: the outputs of orbba_local_bundle_adjustment_device.  In / out: d_slots, d_valid, d_ref_kf [cap_points] (the refresh's),
+ * d_points, and d_kf_pose_R / d_kf_pose_t, the key-frame table's pose arrays.  The CSR is the one the assembly read.
+ *   Erase (:927-934).  For each local point x, row p = d_point_row[x], its edges e in [d_edge_off[x], d_edge_off[x + 1]) with
+ *     d_outlier[e] != 0 in edge order, (k, i) = (d_edge_kf[e], d_edge_kp[e]); nothing more once the point is bad (:931).  If the slot
+ *     (k, i) still names p and k is not bad: d_slots[k * stride + i] = -1 (KeyFrame::eraseMapPoint), then MapPoint::eraseObservation
+ *     (MapPoint.cpp:190-208) as orbm_cull_keyframes_device states it: with L = the live entries of p of key frames other than k, in CSR
+ *     order, d_ref_kf[p] == k and L not empty: d_ref_kf[p] = the key frame of L's first entry; |L| <= 2: the point goes bad, d_valid[p]
+ *     = 0 and the slot of every entry of L becomes -1.  (Should a second slot of k name p, which the reference cannot have, it stays.)
+ *     Points are independent -- a point's cascade touches only its own slots --, the edges of one point sequential.
+ *   Poses (:937-941).  For q < n_local, key frame k = d_pose_kf[q]: d_kf_pose_R / d_kf_pose_t[k] = (double)(float) of the estimate.
+ *     The fixed key frames behind them are not written.
+ *   Points (:944-950).  Every local row still valid after the erasures: d_points[p] = (float) of the estimate.
+ * An entry of d_point_row outside [0, cap_points), offsets of d_edge_off that do not describe a list inside [0, n_edges], an edge
+ * whose (k, i) is unusable and an entry of d_pose_kf outside [0, n_kf) are dropped and counted, never dereferenced.
+ * d_result (int32 x 8, written): [0] observations erased, [1] points set bad, [2] slots cleared by the cascade, [3] reference key
+ * frames moved, [4] rows whose position was written, [5] CSR entries dropped for an index out of range, [6] entries of the assembly's
+ * maps dropped, [7] poses written.
+ * Shape: ONE launch of ONE workgroup of 1024 threads, a thread per local point, then per local key frame.  No scratch memory, handle
+ * scratch, allocation or host wait; static LDS 32 B; at most 64 VGPRs.  Limits and errors as above.  Enqueued on `stream`. */
+int orbm_local_ba_apply_device(orbm_t *h, int n_kf, const int32_t *d_n, const uint8_t *d_bad, int32_t *d_slots, int stride,
+                               uint8_t *d_valid, int32_t *d_ref_kf, float *d_points, int cap_points, double *d_kf_pose_R,
+                               double *d_kf_pose_t, const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs,
+                               int n_local, int n_points, int n_edges, const int32_t *d_pose_kf, const int32_t *d_point_row,
+                               const int32_t *d_edge_off, const int32_t *d_edge_kf, const int32_t *d_edge_kp, const double *d_est_pose_R,
+                               const double *d_est_pose_t, const double *d_est_points, const uint8_t *d_outlier, int32_t *d_result,
+                               void *stream);
 
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,

@@ -139,6 +139,25 @@ def local_bundle_adjustment(cam, pose_R, pose_t, pose_fixed, points, edge_pose, 
     return _lm_finish(out, res)
 
 
+def local_bundle_adjustment_device(cam, d, n_poses, n_points, n_edges, huber_delta=HUBER_MONO, stream=None):
+    """orbba_local_bundle_adjustment_device: the same on a problem in DEVICE memory, as matcher.local_ba_problem_device leaves it.  d:
+    dict of torch device tensors -- in: pose_R, pose_t f64, pose_fixed u8, ba_points f64, edge_pose, edge_point i32, edge_z,
+    edge_inv_sigma2 f64; out: est_pose_R f64 [n_poses,9], est_pose_t f64 [n_poses,3], est_points f64 [n_points,3], chi2 f64 [n_edges],
+    outlier u8 [n_edges].  The three sizes are host ints (the assembly's result[0:3], read back once).  Runs on `stream` (torch's
+    current stream when None) and WAITS on it, once per LM trial.  Returns dict(iterations, trials, lam, chi2_initial, chi2_final,
+    device_ms); an argument error found on the device raises and leaves the outputs as passed."""
+    L = _lib.lib()
+    fn = L.orbba_local_bundle_adjustment_device
+    fn.restype = C.c_int
+    fn.argtypes = [C.POINTER(_Problem), C.POINTER(_LmResult), C.c_void_p, C.c_void_p]
+    p = lambda k: d[k].data_ptr()  # noqa: E731
+    prob = _Problem(cam[0], cam[1], cam[2], cam[3], huber_delta, n_poses, n_points, n_edges, p("pose_R"), p("pose_t"), p("pose_fixed"),
+                    p("ba_points"), p("edge_pose"), p("edge_point"), p("edge_z"), p("edge_inv_sigma2"), *_cam_tail(cam))
+    res = _LmResult(p("est_pose_R"), p("est_pose_t"), p("est_points"), p("chi2"))
+    _lib.check(fn(C.byref(prob), C.byref(res), p("outlier"), _lib.stream_arg(stream)))
+    return _lm_finish({}, res)
+
+
 class _PoseProblem(C.Structure):
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("huber_delta", C.c_double),
                 ("n_frames", C.c_int32), ("rounds", C.c_int32), ("iterations", C.c_int32), ("edge_off", C.c_void_p),

@@ -19,6 +19,7 @@
 
 #include "../../include/orbba.h"
 #include "../../include/orbx.h"
+#include "orb_device.h"
 #include "orb_host.h"
 
 // kernel-choice switches of the BA entry points (include/orbba.h: orbba_set_variant); the entry points take no handle, so the
@@ -698,89 +699,70 @@ __global__ __launch_bounds__(256) void k_lm_diag_max(int n_free, const int *__re
     if (threadIdx.x == 0) *out = fmax(fmax(red4[0], red4[1]), fmax(red4[2], red4[3]));
 }
 
-extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o, orbba_lm_result *r, int device)
-{
-    if (!p || !o || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (p->n_poses < 1 || p->n_points < 1 || p->n_edges < 1) return orbx_set_error(ORBX_E_ARG, "bad sizes");
-    if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || !p->edge_pose || !p->edge_point || !p->edge_z ||
-        !p->edge_inv_sigma2)
-        return orbx_set_error(ORBX_E_ARG, "null input array");
-    if (o->max_iterations < 0) return orbx_set_error(ORBX_E_ARG, "negative iteration count");
-    if (int rc = orb_need_device(&device)) return rc;
-    ORB_TRY(hipSetDevice(device));
-    const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
-    const double tau = o->tau > 0 ? o->tau : 1e-5, lower = o->good_step_lower > 0 ? o->good_step_lower : 1.0 / 3.0,
-                 upper = o->good_step_upper > 0 ? o->good_step_upper : 2.0 / 3.0;
-    const int max_trials = o->max_trials > 0 ? o->max_trials : 10;
-    // ---- index structures
-    std::vector<int> pose_off(NP + 1, 0), pose_edges(NE), point_off(NL + 1, 0), free_pose, pose_slot(NP, -1);
-    for (int i = 0; i < NP; ++i)
-        if (!p->pose_fixed[i]) { pose_slot[i] = (int)free_pose.size(); free_pose.push_back(i); }
-    const int NF = (int)free_pose.size(), N = 6 * NF;
-    if (NF < 1) return orbx_set_error(ORBX_E_ARG, "every pose is fixed: nothing to optimise");
-    if ((size_t)NF * NL > (size_t)1 << 28) return orbx_set_error(ORBX_E_UNSUPPORTED, "free poses x points table too large");
-    std::vector<int> edge_of((size_t)NF * NL, -1);
-    for (int e = 0; e < NE; ++e) {
-        const int ip = p->edge_pose[e], il = p->edge_point[e];
-        if (ip < 0 || ip >= NP || il < 0 || il >= NL) return orbx_set_error(ORBX_E_ARG, "edge index out of range");
-        if (e && il < p->edge_point[e - 1]) return orbx_set_error(ORBX_E_ARG, "edges must be grouped by point");
-        pose_off[ip + 1]++;
-        point_off[il + 1]++;
-        if (pose_slot[ip] >= 0) {
-            int &slot = edge_of[(size_t)pose_slot[ip] * NL + il];
-            if (slot >= 0) return orbx_set_error(ORBX_E_ARG, "a point is observed twice by the same key frame");
-            slot = e;
-        }
-    }
-    for (int i = 0; i < NP; ++i) pose_off[i + 1] += pose_off[i];
-    for (int i = 0; i < NL; ++i) point_off[i + 1] += point_off[i];
-    {
-        std::vector<int> fill(pose_off.begin(), pose_off.end() - 1);
-        for (int e = 0; e < NE; ++e) pose_edges[fill[p->edge_pose[e]]++] = e;
-    }
-    const int EB = (NE + 255) / 256, LB = (NL + 255) / 256;
-    // arena: [estimates R t P -- in and out][other inputs][scratch][chi2 out][read-back block]
-    Layout L;
-    const size_t oR = L.add(72 * (size_t)NP), ot = L.add(24 * (size_t)NP), oP = L.add(24 * (size_t)NL);
-    const size_t est_bytes = L.n;
-    const size_t ofix = L.add(NP), oep = L.add(4 * (size_t)NE), oel = L.add(4 * (size_t)NE), oz = L.add(16 * (size_t)NE),
-                 ow = L.add(8 * (size_t)NE), oact = L.add(NE), opo = L.add(4 * (size_t)(NP + 1)), ope = L.add(4 * (size_t)NE),
-                 olo = L.add(4 * (size_t)(NL + 1)), ofree = L.add(4 * (size_t)NF), oslot = L.add(4 * (size_t)NP),
-                 oeo = L.add((size_t)4 * NF * NL);
-    const size_t in_bytes = L.n;
-    const size_t oRb = L.add(est_bytes), // push() / pop(): R, t, P kept in the same relative layout
-                 oHlp = L.add(144 * (size_t)NE), oCpp = L.add(216 * (size_t)NE), oCll = L.add(72 * (size_t)NE),
-                 oHpp = L.add(288 * (size_t)NP), obp = L.add(48 * (size_t)NP), oHll = L.add(72 * (size_t)NL), obl = L.add(24 * (size_t)NL),
-                 oinv = L.add(72 * (size_t)NL), otl = L.add(24 * (size_t)NL), oS = L.add((size_t)8 * N * N), orhs = L.add(8 * (size_t)N),
-                 oxp = L.add(8 * (size_t)N), oxl = L.add(24 * (size_t)NL);
-    const size_t ochi = L.add(8 * (size_t)NE);
+namespace {
+// One LM problem in the arena: its sizes and the offsets of its arrays.  The host form fills [0, in_bytes) in one copy; the device form
+// copies the caller's arrays in and builds the index structures there (below), before it knows the number of free poses: everything up
+// to and including o_edge_of's START does not depend on it.
+struct LmPlan {
+    int NP, NL, NE, NF, N, EB, LB;
+    size_t oR, ot, oP, est_bytes;                                  // the estimates, in and out
+    size_t ofix, oep, oel, oz, ow, oact, opo, ope, olo, oslot, ofree, oix, oeo, in_bytes;
+    size_t oRb, oHlp, oCpp, oCll, oHpp, obp, oHll, obl, oinv, otl, oS, orhs, oxp, oxl, ochi, ochi1, orb, bytes;
     // what the host reads per trial, ONE copy: [chi2 partials at the iteration's estimate: EB][at the trial's: EB]
     // [computeScale partials of the points: LB][of the poses: 1][max |H_jj|: 1][Cholesky flag: int in 8 bytes]
-    const int RB_CUR = 0, RB_TRY = EB, RB_SCL = 2 * EB, RB_POSE = 2 * EB + LB, RB_MAX = RB_POSE + 1, RB_FLAG = RB_POSE + 2, RB_N = RB_POSE + 3;
-    const size_t orb = L.add(8 * (size_t)RB_N);
-    // page-locked block: [read-back][inputs up / results down]
-    Layout HL;
-    const size_t hrb = HL.add(8 * (size_t)RB_N), hio = HL.add(std::max(in_bytes, est_bytes + 8 * (size_t)NE + 256));
-    Lease<BaWork> lease(g_work);
-    ORB_TRY(lease.acquire(device));
-    BaWork *w = lease.w;
-    ORB_TRY(w->need(L.n, HL.n));
-    hipStream_t s = w->stream;
-    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>() + hio;
-    double *const rb = reinterpret_cast<double *>(w->h.as<uint8_t>() + hrb);
-    put(h, oR, p->pose_R, 72 * (size_t)NP); put(h, ot, p->pose_t, 24 * (size_t)NP); put(h, oP, p->points, 24 * (size_t)NL);
-    put(h, ofix, p->pose_fixed, NP); put(h, oep, p->edge_pose, 4 * (size_t)NE); put(h, oel, p->edge_point, 4 * (size_t)NE);
-    put(h, oz, p->edge_z, 16 * (size_t)NE); put(h, ow, p->edge_inv_sigma2, 8 * (size_t)NE);
-    if (o->edge_active) put(h, oact, o->edge_active, NE);
-    put(h, opo, pose_off.data(), 4 * (size_t)(NP + 1)); put(h, ope, pose_edges.data(), 4 * (size_t)NE);
-    put(h, olo, point_off.data(), 4 * (size_t)(NL + 1)); put(h, ofree, free_pose.data(), 4 * (size_t)NF);
-    put(h, oslot, pose_slot.data(), 4 * (size_t)NP); put(h, oeo, edge_of.data(), (size_t)4 * NF * NL);
-    ORB_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
+    int RB_CUR, RB_TRY, RB_SCL, RB_POSE, RB_MAX, RB_FLAG, RB_N;
+};
+LmPlan lm_plan(int NP, int NL, int NE, int NF)
+{
+    LmPlan q = {};
+    q.NP = NP, q.NL = NL, q.NE = NE, q.NF = NF, q.N = 6 * NF, q.EB = (NE + 255) / 256, q.LB = (NL + 255) / 256;
+    const int N = q.N;
+    // arena: [estimates R t P -- in and out][other inputs][scratch][chi2 out][read-back block]
+    Layout L;
+    q.oR = L.add(72 * (size_t)NP), q.ot = L.add(24 * (size_t)NP), q.oP = L.add(24 * (size_t)NL);
+    q.est_bytes = L.n;
+    q.ofix = L.add(NP), q.oep = L.add(4 * (size_t)NE), q.oel = L.add(4 * (size_t)NE), q.oz = L.add(16 * (size_t)NE);
+    q.ow = L.add(8 * (size_t)NE), q.oact = L.add(NE), q.opo = L.add(4 * (size_t)(NP + 1)), q.ope = L.add(4 * (size_t)NE);
+    q.olo = L.add(4 * (size_t)(NL + 1)), q.oslot = L.add(4 * (size_t)NP), q.ofree = L.add(4 * (size_t)NP), q.oix = L.add(64);
+    q.oeo = L.add((size_t)4 * NF * NL);
+    q.in_bytes = L.n;
+    q.oRb = L.add(q.est_bytes); // push() / pop(): R, t, P kept in the same relative layout
+    q.oHlp = L.add(144 * (size_t)NE), q.oCpp = L.add(216 * (size_t)NE), q.oCll = L.add(72 * (size_t)NE);
+    q.oHpp = L.add(288 * (size_t)NP), q.obp = L.add(48 * (size_t)NP), q.oHll = L.add(72 * (size_t)NL), q.obl = L.add(24 * (size_t)NL);
+    q.oinv = L.add(72 * (size_t)NL), q.otl = L.add(24 * (size_t)NL), q.oS = L.add((size_t)8 * N * N), q.orhs = L.add(8 * (size_t)N);
+    q.oxp = L.add(8 * (size_t)N), q.oxl = L.add(24 * (size_t)NL);
+    q.ochi = L.add(8 * (size_t)NE), q.ochi1 = L.add(8 * (size_t)NE);
+    q.RB_CUR = 0, q.RB_TRY = q.EB, q.RB_SCL = 2 * q.EB, q.RB_POSE = 2 * q.EB + q.LB, q.RB_MAX = q.RB_POSE + 1, q.RB_FLAG = q.RB_POSE + 2;
+    q.RB_N = q.RB_POSE + 3;
+    q.orb = L.add(8 * (size_t)q.RB_N);
+    q.bytes = L.n;
+    return q;
+}
+
+struct LmKnobs { int max_iterations, max_trials; double tau, lower, upper, user_lambda_init; };
+struct LmOutcome { int iterations, trials; double lambda, chi_initial; };
+LmKnobs lm_knobs(const orbba_lm_options *o)
+{
+    return {o->max_iterations, o->max_trials > 0 ? o->max_trials : 10, o->tau > 0 ? o->tau : 1e-5,
+            o->good_step_lower > 0 ? o->good_step_lower : 1.0 / 3.0, o->good_step_upper > 0 ? o->good_step_upper : 2.0 / 3.0, o->user_lambda_init};
+}
+inline double lm_sum(const double *rb, int from, int n) { double v = 0.0; for (int b = 0; b < n; ++b) v += rb[from + b]; return v; }
+
+// optimizer.optimize(max_iterations) on a problem that lies in the arena `d` as `q` describes it, index structures included, enqueued on
+// `s`; `rb` is the page-locked read-back block.  THE loop: the host-pointer and the device-pointer entry points both run it.  It waits
+// on `s` once per trial and returns behind the last evaluation, whose chi2 partials (q.RB_TRY) the caller reads back with its results.
+int lm_loop(const LmPlan &q, uint8_t *d, double *rb, hipStream_t s, const BaCam &cam, const uint8_t *d_active, const LmKnobs &o, LmOutcome *out)
+{
+    const int NP = q.NP, NL = q.NL, NE = q.NE, NF = q.NF, N = q.N, EB = q.EB, LB = q.LB;
+    const int RB_CUR = q.RB_CUR, RB_TRY = q.RB_TRY, RB_SCL = q.RB_SCL, RB_POSE = q.RB_POSE, RB_MAX = q.RB_MAX, RB_FLAG = q.RB_FLAG, RB_N = q.RB_N;
+    const size_t oR = q.oR, ot = q.ot, oP = q.oP, est_bytes = q.est_bytes, ofix = q.ofix, oep = q.oep, oel = q.oel, oz = q.oz, ow = q.ow, opo = q.opo,
+                 ope = q.ope, olo = q.olo, ofree = q.ofree, oslot = q.oslot, oeo = q.oeo, oRb = q.oRb, oHlp = q.oHlp, oCpp = q.oCpp, oCll = q.oCll,
+                 oHpp = q.oHpp, obp = q.obp, oHll = q.oHll, obl = q.obl, oinv = q.oinv, otl = q.otl, oS = q.oS, orhs = q.orhs, oxp = q.oxp,
+                 oxl = q.oxl, ochi = q.ochi, orb = q.orb;
+    const double tau = o.tau, lower = o.lower, upper = o.upper;
+    const int max_trials = o.max_trials;
     auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
     auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
-    const uint8_t *d_active = o->edge_active ? d + oact : nullptr;
-    const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
-    ORB_TRY(hipEventRecord(w->e0, s));
 
     // errors at the current estimate (+ the whole linearisation when `full`); activeRobustChi2 as partial sums into the
     // read-back block's slot `slot`
@@ -801,15 +783,15 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
         ORB_TRY(hipStreamSynchronize(s));
         return ORBX_OK;
     };
-    auto sum = [&](int from, int n) { double v = 0.0; for (int b = 0; b < n; ++b) v += rb[from + b]; return v; };
+    auto sum = [&](int from, int n) { return lm_sum(rb, from, n); };
 
     double lam = 0.0, ni = 2.0, chi_initial = 0.0, current = 0.0;
     int its = 0, trials_total = 0, rc = ORBX_OK;
-    for (int it = 0; it < o->max_iterations; ++it) {
+    for (int it = 0; it < o.max_iterations; ++it) {
         evaluate(true, RB_CUR);
         bool have_current = false;
         if (it == 0) {
-            if (o->user_lambda_init > 0) lam = o->user_lambda_init;
+            if (o.user_lambda_init > 0) lam = o.user_lambda_init;
             else { // computeLambdaInit: tau * max |H_jj| over the free vertices
                 hipLaunchKernelGGL(k_lm_diag_max, dim3(1), dim3(256), 0, s, NF, I(ofree), D(oHpp), NL, D(oHll), D(orb) + RB_MAX);
                 if ((rc = read_back())) return rc;
@@ -880,25 +862,91 @@ extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o,
         if (qmax == max_trials || rho == 0 || !std::isfinite(lam)) break; // Terminate
     }
     evaluate(false, RB_TRY);
-    ORB_TRY(hipEventRecord(w->e1, s));
     ORB_TRY(hipGetLastError());
-    ORB_TRY(hipMemcpyAsync(rb, d + orb, 8 * (size_t)RB_N, hipMemcpyDeviceToHost, s));
-    ORB_TRY(hipMemcpyAsync(h, d, est_bytes, hipMemcpyDeviceToHost, s));
-    if (r->chi2) ORB_TRY(hipMemcpyAsync(h + est_bytes, d + ochi, 8 * (size_t)NE, hipMemcpyDeviceToHost, s));
+    out->iterations = its, out->trials = trials_total, out->lambda = lam, out->chi_initial = chi_initial;
+    return ORBX_OK;
+}
+} // namespace
+
+extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o, orbba_lm_result *r, int device)
+{
+    if (!p || !o || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (p->n_poses < 1 || p->n_points < 1 || p->n_edges < 1) return orbx_set_error(ORBX_E_ARG, "bad sizes");
+    if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || !p->edge_pose || !p->edge_point || !p->edge_z ||
+        !p->edge_inv_sigma2)
+        return orbx_set_error(ORBX_E_ARG, "null input array");
+    if (o->max_iterations < 0) return orbx_set_error(ORBX_E_ARG, "negative iteration count");
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
+    const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
+    // ---- index structures (the device form builds the same ones with k_lmi_*, below)
+    std::vector<int> pose_off(NP + 1, 0), pose_edges(NE), point_off(NL + 1, 0), free_pose, pose_slot(NP, -1);
+    for (int i = 0; i < NP; ++i)
+        if (!p->pose_fixed[i]) { pose_slot[i] = (int)free_pose.size(); free_pose.push_back(i); }
+    const int NF = (int)free_pose.size();
+    if (NF < 1) return orbx_set_error(ORBX_E_ARG, "every pose is fixed: nothing to optimise");
+    if ((size_t)NF * NL > (size_t)1 << 28) return orbx_set_error(ORBX_E_UNSUPPORTED, "free poses x points table too large");
+    std::vector<int> edge_of((size_t)NF * NL, -1);
+    for (int e = 0; e < NE; ++e) {
+        const int ip = p->edge_pose[e], il = p->edge_point[e];
+        if (ip < 0 || ip >= NP || il < 0 || il >= NL) return orbx_set_error(ORBX_E_ARG, "edge index out of range");
+        if (e && il < p->edge_point[e - 1]) return orbx_set_error(ORBX_E_ARG, "edges must be grouped by point");
+        pose_off[ip + 1]++;
+        point_off[il + 1]++;
+        if (pose_slot[ip] >= 0) {
+            int &slot = edge_of[(size_t)pose_slot[ip] * NL + il];
+            if (slot >= 0) return orbx_set_error(ORBX_E_ARG, "a point is observed twice by the same key frame");
+            slot = e;
+        }
+    }
+    for (int i = 0; i < NP; ++i) pose_off[i + 1] += pose_off[i];
+    for (int i = 0; i < NL; ++i) point_off[i + 1] += point_off[i];
+    {
+        std::vector<int> fill(pose_off.begin(), pose_off.end() - 1);
+        for (int e = 0; e < NE; ++e) pose_edges[fill[p->edge_pose[e]]++] = e;
+    }
+    const LmPlan q = lm_plan(NP, NL, NE, NF);
+    // page-locked block: [read-back][inputs up / results down]
+    Layout HL;
+    const size_t hrb = HL.add(8 * (size_t)q.RB_N), hio = HL.add(std::max(q.in_bytes, q.est_bytes + 8 * (size_t)NE + 256));
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
+    BaWork *w = lease.w;
+    ORB_TRY(w->need(q.bytes, HL.n));
+    hipStream_t s = w->stream;
+    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>() + hio;
+    double *const rb = reinterpret_cast<double *>(w->h.as<uint8_t>() + hrb);
+    put(h, q.oR, p->pose_R, 72 * (size_t)NP); put(h, q.ot, p->pose_t, 24 * (size_t)NP); put(h, q.oP, p->points, 24 * (size_t)NL);
+    put(h, q.ofix, p->pose_fixed, NP); put(h, q.oep, p->edge_pose, 4 * (size_t)NE); put(h, q.oel, p->edge_point, 4 * (size_t)NE);
+    put(h, q.oz, p->edge_z, 16 * (size_t)NE); put(h, q.ow, p->edge_inv_sigma2, 8 * (size_t)NE);
+    if (o->edge_active) put(h, q.oact, o->edge_active, NE);
+    put(h, q.opo, pose_off.data(), 4 * (size_t)(NP + 1)); put(h, q.ope, pose_edges.data(), 4 * (size_t)NE);
+    put(h, q.olo, point_off.data(), 4 * (size_t)(NL + 1)); put(h, q.ofree, free_pose.data(), 4 * (size_t)NF);
+    put(h, q.oslot, pose_slot.data(), 4 * (size_t)NP); put(h, q.oeo, edge_of.data(), (size_t)4 * NF * NL);
+    ORB_TRY(hipMemcpyAsync(d, h, q.in_bytes, hipMemcpyHostToDevice, s));
+    const uint8_t *d_active = o->edge_active ? d + q.oact : nullptr;
+    const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
+    ORB_TRY(hipEventRecord(w->e0, s));
+    LmOutcome out = {};
+    if (int rc = lm_loop(q, d, rb, s, cam, d_active, lm_knobs(o), &out)) return rc;
+    ORB_TRY(hipEventRecord(w->e1, s));
+    ORB_TRY(hipMemcpyAsync(rb, d + q.orb, 8 * (size_t)q.RB_N, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(h, d, q.est_bytes, hipMemcpyDeviceToHost, s));
+    if (r->chi2) ORB_TRY(hipMemcpyAsync(h + q.est_bytes, d + q.ochi, 8 * (size_t)NE, hipMemcpyDeviceToHost, s));
     ORB_TRY(hipStreamSynchronize(s));
-    const double final_chi = sum(RB_TRY, EB);
+    const double final_chi = lm_sum(rb, q.RB_TRY, q.EB);
     float ms = 0;
     ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
-    r->iterations = its;
-    r->trials = trials_total;
-    r->lambda = lam;
-    r->chi2_initial = o->max_iterations > 0 ? chi_initial : final_chi;
+    r->iterations = out.iterations;
+    r->trials = out.trials;
+    r->lambda = out.lambda;
+    r->chi2_initial = o->max_iterations > 0 ? out.chi_initial : final_chi;
     r->chi2_final = final_chi;
     r->device_ms = ms;
-    if (r->pose_R) memcpy(r->pose_R, h + oR, 72 * (size_t)NP);
-    if (r->pose_t) memcpy(r->pose_t, h + ot, 24 * (size_t)NP);
-    if (r->points) memcpy(r->points, h + oP, 24 * (size_t)NL);
-    if (r->chi2) memcpy(r->chi2, h + est_bytes, 8 * (size_t)NE);
+    if (r->pose_R) memcpy(r->pose_R, h + q.oR, 72 * (size_t)NP);
+    if (r->pose_t) memcpy(r->pose_t, h + q.ot, 24 * (size_t)NP);
+    if (r->points) memcpy(r->points, h + q.oP, 24 * (size_t)NL);
+    if (r->chi2) memcpy(r->chi2, h + q.est_bytes, 8 * (size_t)NE);
     return ORBX_OK;
 }
 
@@ -942,6 +990,218 @@ extern "C" int orbba_local_bundle_adjustment(const orbba_problem *p, orbba_lm_re
     if (user_chi) std::copy(chi2v.begin(), chi2v.end(), user_chi);
     if (outlier)
         for (int e = 0; e < NE; ++e) outlier[e] = !active[e] || chi2v[e] > 5.991; // :917-921
+    return ORBX_OK;
+}
+
+// =====================================================================================================================
+// The same on a problem that lies in DEVICE memory (include/orbba.h: orbba_local_bundle_adjustment_device), as
+// orbm_local_ba_problem_device leaves it.  The index structures orbba_optimize builds on the host are built here by the k_lmi_*
+// kernels, with its checks; both rounds then run lm_loop on them, and the demotion between the rounds and the outlier rule behind
+// them are two small kernels.  Every structure is a function of the edge arrays alone -- counts are sums, a cell of edge_of has one
+// writer in a problem that passes the checks, pose_edges is placed in edge order by a block scan -- so the bytes equal the host's.
+//   k_lmi_count   thread = edge: index ranges, edges grouped by point; edges per pose into pose_off[pose + 1]
+//   k_lmi_poses   one workgroup: pose_off scanned in place; free_pose / pose_slot / the number of free poses by a scan of the flags
+//   k_lmi_place   workgroup = pose: its edges in edge order -> pose_edges (reads every edge once per pose: n_poses * n_edges reads)
+//   k_lmi_fill    edge_of = -1, free poses x points (the number of free poses is read from device memory)
+//   k_lmi_cells   thread = edge: edge_of[slot of its pose][point] = edge; a cell taken twice = a point observed twice by a key frame
+//   k_lmi_points  thread = point: point_off = the first edge whose point is not below it (the edges are sorted by point)
+// =====================================================================================================================
+enum { LMI_FLAG = 0, LMI_NF = 1 };                                  // the index block (q.oix): error bits, free poses
+enum { LMI_E_RANGE = 1, LMI_E_ORDER = 2, LMI_E_TWICE = 4, LMI_E_ALL_FIXED = 8 };
+
+__global__ __launch_bounds__(256) void k_lmi_count(int NP, int NL, int NE, const int *__restrict__ ep, const int *__restrict__ el,
+                                                   int *__restrict__ pose_off, int *__restrict__ ix)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const int ip = ep[e], il = el[e];
+    int err = 0;
+    if (ip < 0 || ip >= NP || il < 0 || il >= NL) err |= LMI_E_RANGE;
+    else atomicAdd(&pose_off[ip + 1], 1);
+    if (e && il < el[e - 1]) err |= LMI_E_ORDER;
+    if (err) atomicOr(&ix[LMI_FLAG], err);
+}
+
+__global__ __launch_bounds__(1024) void k_lmi_poses(int NP, const uint8_t *__restrict__ fixed, int *__restrict__ pose_off,
+                                                    int *__restrict__ free_pose, int *__restrict__ pose_slot, int *__restrict__ ix)
+{
+    __shared__ int s_wave[2][16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = (NP + 1023) / 1024;
+    const int j0 = min(tid * chunk, NP), j1 = min(j0 + chunk, NP);
+    int edges = 0, n_free = 0;
+    for (int j = j0; j < j1; ++j) edges += pose_off[j + 1], n_free += !fixed[j];
+    const int ie = wave_scan(edges), in = wave_scan(n_free);
+    if (lane == 63) s_wave[0][wave] = ie, s_wave[1][wave] = in;
+    __syncthreads();
+    int before_e = ie - edges, before_f = in - n_free, total_f = 0;
+    for (int w = 0; w < 16; ++w) {
+        if (w < wave) before_e += s_wave[0][w], before_f += s_wave[1][w];
+        total_f += s_wave[1][w];
+    }
+    for (int j = j0; j < j1; ++j) {
+        before_e += pose_off[j + 1];
+        pose_off[j + 1] = before_e;
+        if (fixed[j]) pose_slot[j] = -1;
+        else pose_slot[j] = before_f, free_pose[before_f++] = j;
+    }
+    if (tid == 0) {
+        pose_off[0] = 0;
+        ix[LMI_NF] = total_f;
+        if (total_f < 1) atomicOr(&ix[LMI_FLAG], LMI_E_ALL_FIXED);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lmi_place(int NE, const int *__restrict__ ep, const int *__restrict__ pose_off,
+                                                   int *__restrict__ pose_edges)
+{
+    __shared__ int s_wave[4];
+    const int ip = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int at = pose_off[ip];
+    const int end = pose_off[ip + 1];
+    for (int e0 = 0; e0 < NE && at < end; e0 += 256) {
+        const int e = e0 + tid;
+        const int is_mine = e < NE && ep[e] == ip;
+        const int incl = wave_scan(is_mine);
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int before = incl - is_mine, total = 0;
+        for (int w = 0; w < 4; ++w) {
+            if (w < wave) before += s_wave[w];
+            total += s_wave[w];
+        }
+        if (is_mine && at + before < min(end, NE)) pose_edges[at + before] = e;
+        at += total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lmi_fill(int NL, const int *__restrict__ ix, int cap, int *__restrict__ edge_of)
+{
+    const long long all = (long long)ix[LMI_NF] * NL, n = all < cap ? all : cap;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) edge_of[i] = -1;
+}
+
+__global__ __launch_bounds__(256) void k_lmi_cells(int NP, int NL, int NE, const int *__restrict__ ep, const int *__restrict__ el,
+                                                   const int *__restrict__ pose_slot, int *__restrict__ edge_of, int *__restrict__ ix)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const int ip = ep[e], il = el[e];
+    if (ip < 0 || ip >= NP || il < 0 || il >= NL) return;
+    const int slot = pose_slot[ip];
+    if (slot < 0) return;
+    if (atomicCAS(&edge_of[(size_t)slot * NL + il], -1, e) != -1) atomicOr(&ix[LMI_FLAG], LMI_E_TWICE);
+}
+
+__global__ __launch_bounds__(256) void k_lmi_points(int NL, int NE, const int *__restrict__ el, int *__restrict__ point_off)
+{
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l > NL) return;
+    int lo = 0, hi = NE;                                           // the first edge whose point is >= l
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (el[mid] < l) lo = mid + 1;
+        else hi = mid;
+    }
+    point_off[l] = lo;
+}
+
+// Optimize.cpp:899-902 between the rounds: the demotion mask, and the first round's chi2 kept for the demoted edges
+__global__ __launch_bounds__(256) void k_lba_demote(int NE, const double *__restrict__ chi, uint8_t *__restrict__ active, double *__restrict__ chi1)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const double c = chi[e];
+    active[e] = !(c > 5.991);
+    chi1[e] = c;
+}
+
+// :917-921 behind the second round: a demoted edge keeps its stale first-round chi2 (see orbba_local_bundle_adjustment), the outliers
+__global__ __launch_bounds__(256) void k_lba_outliers(int NE, const double *__restrict__ chi, const uint8_t *__restrict__ active,
+                                                      const double *__restrict__ chi1, double *__restrict__ chi_out, uint8_t *__restrict__ outlier)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= NE) return;
+    const double c = active[e] ? chi[e] : chi1[e];
+    chi_out[e] = c;
+    outlier[e] = !active[e] || c > 5.991;
+}
+
+extern "C" int orbba_local_bundle_adjustment_device(const orbba_problem *p, orbba_lm_result *r, uint8_t *d_outlier, void *stream)
+{
+    if (!p || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
+    const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
+    if (NP < 1 || NL < 1 || NE < 1) return orbx_set_error(ORBX_E_ARG, "bad sizes");
+    if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || !p->edge_pose || !p->edge_point || !p->edge_z || !p->edge_inv_sigma2 ||
+        !r->pose_R || !r->pose_t || !r->points || !r->chi2 || !d_outlier)
+        return orbx_set_error(ORBX_E_ARG, "null array (every pointer is device memory here, chi2 and outlier included)");
+    // the number of free poses is not known yet: the arena is sized for every pose free
+    if ((size_t)NP * NL > (size_t)1 << 28) return orbx_set_error(ORBX_E_UNSUPPORTED, "poses x points table too large");
+    int device = -1;
+    if (int rc = orb_need_device(&device)) return rc;
+    hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
+    const LmPlan q0 = lm_plan(NP, NL, NE, NP);
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
+    BaWork *w = lease.w;                 // its arena, staging block and events; the stream is the caller's
+    ORB_TRY(w->need(q0.bytes, 8 * (size_t)q0.RB_N + 256));
+    uint8_t *d = w->d.as<uint8_t>();
+    double *const rb = w->h.as<double>();
+    auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
+    auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
+    auto copy = [&](size_t off, const void *src, size_t bytes) { return hipMemcpyAsync(d + off, src, bytes, hipMemcpyDeviceToDevice, s); };
+    ORB_TRY(copy(q0.oR, p->pose_R, 72 * (size_t)NP)); ORB_TRY(copy(q0.ot, p->pose_t, 24 * (size_t)NP)); ORB_TRY(copy(q0.oP, p->points, 24 * (size_t)NL));
+    ORB_TRY(copy(q0.ofix, p->pose_fixed, NP)); ORB_TRY(copy(q0.oep, p->edge_pose, 4 * (size_t)NE)); ORB_TRY(copy(q0.oel, p->edge_point, 4 * (size_t)NE));
+    ORB_TRY(copy(q0.oz, p->edge_z, 16 * (size_t)NE)); ORB_TRY(copy(q0.ow, p->edge_inv_sigma2, 8 * (size_t)NE));
+    // ---- index structures and the host form's checks, on the device
+    ORB_TRY(hipMemsetAsync(d + q0.opo, 0, 4 * (size_t)(NP + 1), s));
+    ORB_TRY(hipMemsetAsync(d + q0.oix, 0, 64, s));
+    const int EB = q0.EB;
+    const int fill_cap = (int)std::min<size_t>((size_t)NP * NL, (size_t)1 << 28);
+    hipLaunchKernelGGL(k_lmi_count, dim3(EB), dim3(256), 0, s, NP, NL, NE, I(q0.oep), I(q0.oel), I(q0.opo), I(q0.oix));
+    hipLaunchKernelGGL(k_lmi_poses, dim3(1), dim3(1024), 0, s, NP, d + q0.ofix, I(q0.opo), I(q0.ofree), I(q0.oslot), I(q0.oix));
+    hipLaunchKernelGGL(k_lmi_place, dim3(NP), dim3(256), 0, s, NE, I(q0.oep), I(q0.opo), I(q0.ope));
+    hipLaunchKernelGGL(k_lmi_fill, dim3(std::min((fill_cap + 255) / 256, 1024)), dim3(256), 0, s, NL, I(q0.oix), fill_cap, I(q0.oeo));
+    hipLaunchKernelGGL(k_lmi_cells, dim3(EB), dim3(256), 0, s, NP, NL, NE, I(q0.oep), I(q0.oel), I(q0.oslot), I(q0.oeo), I(q0.oix));
+    hipLaunchKernelGGL(k_lmi_points, dim3((NL + 256) / 256), dim3(256), 0, s, NL, NE, I(q0.oel), I(q0.olo));
+    ORB_TRY(hipGetLastError());
+    // the first read-back: the checks' verdict and the number of free poses, which sizes the reduced system
+    int *const ix = reinterpret_cast<int *>(rb);
+    ORB_TRY(hipMemcpyAsync(ix, d + q0.oix, 64, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
+    const int flag = ix[LMI_FLAG], NF = ix[LMI_NF];
+    if (flag & LMI_E_RANGE) return orbx_set_error(ORBX_E_ARG, "edge index out of range");
+    if (flag & LMI_E_ORDER) return orbx_set_error(ORBX_E_ARG, "edges must be grouped by point");
+    if (flag & LMI_E_ALL_FIXED || NF < 1 || NF > NP) return orbx_set_error(ORBX_E_ARG, "every pose is fixed: nothing to optimise");
+    if (flag & LMI_E_TWICE) return orbx_set_error(ORBX_E_ARG, "a point is observed twice by the same key frame");
+    const LmPlan q = lm_plan(NP, NL, NE, NF);                      // the same offsets up to edge_of; the scratch behind it is smaller
+    BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
+    ORB_TRY(hipEventRecord(w->e0, s));
+    orbba_lm_options o1 = {}, o2 = {};
+    o1.max_iterations = 5;               // optimizer.optimize(5), :893
+    o2.max_iterations = 10;              // :909
+    LmOutcome out1 = {}, out2 = {};
+    if (int rc = lm_loop(q, d, rb, s, cam, nullptr, lm_knobs(&o1), &out1)) return rc;
+    hipLaunchKernelGGL(k_lba_demote, dim3(EB), dim3(256), 0, s, NE, D(q.ochi), d + q.oact, D(q.ochi1));   // :899-902
+    cam.delta = 0.0;                     // setRobustKernel(nullptr), :904
+    if (int rc = lm_loop(q, d, rb, s, cam, d + q.oact, lm_knobs(&o2), &out2)) return rc;
+    hipLaunchKernelGGL(k_lba_outliers, dim3(EB), dim3(256), 0, s, NE, D(q.ochi), d + q.oact, D(q.ochi1), r->chi2, d_outlier);
+    ORB_TRY(hipGetLastError());
+    ORB_TRY(hipMemcpyAsync(r->pose_R, d + q.oR, 72 * (size_t)NP, hipMemcpyDeviceToDevice, s));
+    ORB_TRY(hipMemcpyAsync(r->pose_t, d + q.ot, 24 * (size_t)NP, hipMemcpyDeviceToDevice, s));
+    ORB_TRY(hipMemcpyAsync(r->points, d + q.oP, 24 * (size_t)NL, hipMemcpyDeviceToDevice, s));
+    ORB_TRY(hipEventRecord(w->e1, s));
+    ORB_TRY(hipMemcpyAsync(rb, d + q.orb, 8 * (size_t)q.RB_N, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));    // the arena goes back to the pool: nothing of this call may still be running
+    float ms = 0;
+    ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
+    r->iterations = out1.iterations + out2.iterations;
+    r->trials = out1.trials + out2.trials;
+    r->lambda = out2.lambda;
+    r->chi2_initial = out1.chi_initial;
+    r->chi2_final = lm_sum(rb, q.RB_TRY, q.EB);
+    r->device_ms = ms;
     return ORBX_OK;
 }
 

@@ -121,6 +121,10 @@ def _mlib():
             "orbm_cull_keyframes_device": (i32, [vp, C.POINTER(KfTable), vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32,
                                                  C.c_double, C.c_double, vp, vp, vp, vp, vp]),
             "orbm_fuse_apply_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+            "orbm_local_ba_problem_device": (i32, [vp, C.POINTER(KfTable), vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32]
+                                             + [vp] * 16),
+            "orbm_local_ba_apply_device": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32]
+                                           + [vp] * 11),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -494,6 +498,37 @@ class ORBMatcher:
             p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, opt("found"), opt("visible"), p("work"), p("code"), p("refresh_sel"),
             p("result"), _lib.stream_arg(stream)))
 
+    # -- Optimize::localBundleAdjustment on the slot arrays: the problem assembled, the result applied (Optimize.cpp:766-889, :914-950) --
+    def LocalBaProblemDevice(self, kf, d, stride, cap_points, n_obs, n_local, first_kf, cap_poses, cap_local_points, cap_edges, stream=None):
+        """orbm_local_ba_problem_device: kf a KfTable.  d: dict of torch device tensors -- in: slots i32 [n_kf,stride], valid u8 [cap],
+        points f32 [cap,3], obs_off, obs_kf, obs_kp (the CSR BuildObservationsDevice left from these slots), local i32 [n_local] (the
+        current key frame, then its connected ones); work i32 [cap + n_kf] (the call's work array); out, an orbba problem in device
+        memory: pose_R f64 [cap_poses,9], pose_t f64 [cap_poses,3], pose_fixed u8 [cap_poses], ba_points f64 [cap_local_points,3],
+        edge_pose, edge_point i32 [cap_edges], edge_z f64 [cap_edges,2], edge_inv_sigma2 f64 [cap_edges], and the maps back: edge_kf,
+        edge_kp i32 [cap_edges], edge_off i32 [cap_local_points + 1], point_row i32 [cap_local_points], pose_kf i32 [cap_poses]; result
+        i32 [16] ([0] n_poses, [1] n_points, [2] n_edges, [3] local key frames, [5] refusal mask).  Enqueues on `stream`; nothing is
+        copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_local_ba_problem_device(
+            self._hd._h, C.byref(kf), p("slots"), stride, p("valid"), p("points"), cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs,
+            p("local"), n_local, first_kf, cap_poses, cap_local_points, cap_edges, p("work"), p("pose_R"), p("pose_t"), p("pose_fixed"),
+            p("ba_points"), p("edge_pose"), p("edge_point"), p("edge_z"), p("edge_inv_sigma2"), p("edge_kf"), p("edge_kp"), p("edge_off"),
+            p("point_row"), p("pose_kf"), p("result"), _lib.stream_arg(stream)))
+
+    def LocalBaApplyDevice(self, d, n_kf, stride, cap_points, n_obs, n_local, n_points, n_edges, stream=None):
+        """orbm_local_ba_apply_device: d = dict of torch device tensors -- in: n i32 [n_kf], bad u8 [n_kf], obs_off, obs_kf, obs_kp (the
+        CSR the assembly read), the assembly's maps pose_kf, point_row, edge_off, edge_kf, edge_kp, and the outputs of
+        ba.local_bundle_adjustment_device est_pose_R, est_pose_t, est_points f64, outlier u8; in / out: slots i32 [n_kf,stride], valid
+        u8 [cap], ref_kf i32 [cap], points f32 [cap,3], kf_pose_R f64 [n_kf,9], kf_pose_t f64 [n_kf,3] (the key-frame table's); out:
+        result i32 [8].  n_local, n_points, n_edges: result[3], [1], [2] of the assembly.  Enqueues on `stream`; nothing is copied or
+        synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_local_ba_apply_device(
+            self._hd._h, n_kf, p("n"), p("bad"), p("slots"), stride, p("valid"), p("ref_kf"), p("points"), cap_points, p("kf_pose_R"),
+            p("kf_pose_t"), p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, n_local, n_points, n_edges, p("pose_kf"), p("point_row"),
+            p("edge_off"), p("edge_kf"), p("edge_kp"), p("est_pose_R"), p("est_pose_t"), p("est_points"), p("outlier"), p("result"),
+            _lib.stream_arg(stream)))
+
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
         orbf_frame_post_device leaves it), desc2, cell_start, cell_items, pre (float32 [n1, 2], in / out), matches12 (int32 [n1], out),
@@ -549,3 +584,13 @@ class ORBMatcher:
         _lib.check(self._L.orbm_search_fuse(self._hd._h, _vp(qd), _vp(qx), _vp(qr), _vp(ql), _vp(qk), len(qd), _vp(k),
                                             _vp(d), len(k), img_w, img_h, _vp(s2), len(s2), _vp(bi), _vp(bd), C.byref(n)))
         return bi, bd, n.value
+
+
+def local_ba_problem_device(matcher, *args, **kwargs):
+    """ORBMatcher.LocalBaProblemDevice (orbm_local_ba_problem_device) under the name include/orbm.h's section uses"""
+    return matcher.LocalBaProblemDevice(*args, **kwargs)
+
+
+def local_ba_apply_device(matcher, *args, **kwargs):
+    """ORBMatcher.LocalBaApplyDevice (orbm_local_ba_apply_device)"""
+    return matcher.LocalBaApplyDevice(*args, **kwargs)
