@@ -453,7 +453,8 @@ int orbm_triangulate_matches(orbm_t *h, const orbm_proj_camera *cam, const float
  *
  * d_covis (may be NULL) [n_kf], written, not accumulated: for every selected valid row -- per entry of d_sel, so a duplicate
  * counts twice, as the reference's loop over a key frame's slots does, and whether or not the row was left untouched -- and each
- * remaining observation with kf != kf_self, d_covis[kf]++.  CONNECT_TH, the sort and the graph edits stay with the caller.
+ * remaining observation with kf != kf_self, d_covis[kf]++.  CONNECT_TH, the sort and the graph edits are
+ * orbm_update_connections_device ("The covisibility graph on the device").
  * d_result (int32 x 8, written): [0] rows refreshed, [1] skipped invalid, [2] untouched: no usable observation, [3] untouched: over
  * 1024 observations, [4] observations dropped for an index out of range (of every selected valid row), [5] refreshed rows whose
  * descriptor was left as it was: every observer bad, [6] refreshed rows whose reference key frame was not among their observations,
@@ -564,8 +565,8 @@ int orbm_build_observations_device(orbm_t *h, int n_kf, const int32_t *d_n, cons
  *          d_ref_kf[p] == c and L not empty: d_ref_kf[p] = the key frame of L's first entry (observations.begin(), :198-199);
  *          |L| <= 2: the point goes bad (:202, :210-226): d_valid[p] = 0 and d_slots[k2 * stride + i2] = -1 for every entry of L;
  *        finally every slot of c, whatever it holds, becomes -1 (map_points.clear(), KeyFrame.cpp:418).
- * Each candidate sees what the ones before it wrote.  The covisibility-graph and spanning-tree edits of KeyFrame::setBad and
- * Map::eraseMapPoint stay with the caller, who reads d_code.
+ * Each candidate sees what the ones before it wrote.  The covisibility-graph and spanning-tree edits of KeyFrame::setBad are
+ * orbm_erase_connections_device, which takes d_code as it is; Map::eraseMapPoint stays with the caller, who reads d_code.
  * d_code [n_recent]: -1 at positions 0 and n_recent - 1, else as above; d_num_mp / d_num_redundant [n_recent]: 0 where not evaluated.
  * d_result (int32 x 8, written): [0] culled, [1] kept, [2] skipped, [3] points set bad, [4] slots cleared in key frames other than
  * the culled one, [5] d_ref_kf entries reassigned, [6] CSR entries dropped for an index out of range, [7] 0.
@@ -592,8 +593,9 @@ int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, uint8_t *d_ba
  * THE TRUTH: an observation is a slot, so addObservation and addMapPoint are ONE store, and replace rewrites the slots that name the
  * loser.  Integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature
  * shims (compat/) keep their host objects.
- * Out of scope, the caller's: the list of fuseMapPoints itself -- the de-duplicated union of the target key frames' slots
- * (LocalMapping.cpp:287-300) --, Map::eraseMapPoint and the covisibility graph, and MapPointCulling.
+ * The list of fuseMapPoints itself -- the de-duplicated union of the target key frames' slots (LocalMapping.cpp:287-300) -- is
+ * orbm_fuse_targets_device's d_rows ("The covisibility graph on the device").  Out of scope, the caller's: Map::eraseMapPoint and
+ * MapPointCulling.
  *
  * Entries: d_best_idx [nq] as orbm_search_fuse_device leaves it; entry j is table row d_rows[j], or row j when d_rows is NULL (the
  * builders index the table by query).  kf_target = K, the key frame searched.  d_n, d_bad, d_slots (in / out), stride: the layout of
@@ -664,7 +666,8 @@ int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, const int32_t *
  * Between the first and the second the caller reads the first 32 bytes of the assembly's d_result back ONCE (the three sizes are host
  * ints of the LM call) and the LM call waits for one small block per trial; no table, slot array or index returns to the host, and
  * no host loop runs over points or observations.  mp->update() (:948) is orbm_refresh_points_device with d_sel = d_point_row behind a
- * rebuilt CSR; it is not repeated here.  MapPointCulling and the covisibility graph (getConnectedKFs: d_local) stay with the caller.
+ * rebuilt CSR; it is not repeated here.  d_local (getConnectedKFs) is orbm_connected_keyframes_device's d_out ("The covisibility graph on
+ * the device"); only MapPointCulling and Map::eraseMapPoint stay with the caller.
  * The two calls below follow this header's rules for the map side: device pointers only and deliberately NO host-pointer twin; no
  * allocation, handle scratch or host wait; results written, not accumulated; the same bytes on every run; every index that comes
  * from device memory is distrusted -- dropped and counted, never dereferenced out of range.  THE SLOT ARRAYS ARE THE TRUTH and the CSR
@@ -674,7 +677,8 @@ int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, const int32_t *
  * and its key frame is not bad.
  *
  * orbm_local_ba_problem_device.  d_local [n_local] (device): d_local[0] is the current key frame, the rest getConnectedKFs() in the
- * caller's order.  first_kf: the slot of the key frame with id 0, or -1, as in the culling.
+ * caller's order -- or orbm_connected_keyframes_device's d_out with n_local = its n_out: the -1 fill is dropped below, so no count is
+ * read back.  first_kf: the slot of the key frame with id 0, or -1, as in the culling.
  *   Local key frames: the entries of d_local in order.  An entry outside [0, n_kf) is dropped (d_result[6]); a later entry whose key
  *     frame is bad is skipped (:777, d_result[7]); an entry naming a key frame an earlier entry named is dropped (d_result[6]).  Entry 0
  *     is taken whether or not it is bad.
@@ -746,6 +750,115 @@ int orbm_local_ba_apply_device(orbm_t *h, int n_kf, const int32_t *d_n, const ui
                                const int32_t *d_edge_off, const int32_t *d_edge_kf, const int32_t *d_edge_kp, const double *d_est_pose_R,
                                const double *d_est_pose_t, const double *d_est_points, const uint8_t *d_outlier, int32_t *d_result,
                                void *stream);
+
+/* ---- The covisibility graph on the device ------------------------------------------------------------------------------------------
+ * What the links of the mapper step exchange: KeyFrame::connected_kf_weights / ordered_connected_kfs and the spanning tree
+ * (modules/BasicObject/KeyFrame.cpp:225-362, :402-467; CONNECT_TH = 15, KeyFrame.h:24) in device memory beside the slot arrays, with
+ * four entry points: updateConnections behind the refresh's d_covis, the graph part of setBad behind the culling's d_code, the target
+ * key frames and the fuseMapPoints list of LocalMapping::searchInNeighbors (LocalMapping.cpp:263-300), and getConnectedKFs /
+ * getBestCovisibleKFs as the d_local of orbm_local_ba_problem_device.  With them the only read-back the graph adds per key frame is
+ * the target list of at most n_first * (1 + n_second) = 120 ints, which the host needs anyway: kf_target of the fuse calls is a host
+ * int.  The map side's rules hold: device pointers only and deliberately NO host-pointer twin; no allocation, handle scratch or host
+ * wait; integer only, written not accumulated, the same bytes on every run.
+ *
+ * The state is the caller's, a host struct of device pointers copied into the launch's arguments as orbm_kf_table is:
+ *   - the caller zero-fills d_weight and d_ord_n and fills d_parent with -1 ONCE; a new key frame's row and column are then empty;
+ *   - only rows and columns below the call's n_kf (<= cap_kf) are read or written;
+ *   - entries of d_ord_kf[k] at and past the d_ord_n[k] a call leaves are never written by that call;
+ *   - ordered_connected_weights[i] is d_weight[k][d_ord_kf[k][i]] -- the reference re-sorts the list at every change of a map entry,
+ *     so the invariant holds there -- and is therefore not stored;
+ *   - the children of k are the j with d_parent[j] == k.  The reference's consumers all test isBad(), for which the set is the same;
+ *   - THE ORDER OF A LIST is descending weight and ascending key-frame slot among equal weights.  That is a stated canonicalisation:
+ *     the reference sorts pair<int, shared_ptr>, so its ties fall in heap-address order.  Likewise, where the reference takes "the
+ *     first strictly greater" over an unordered_map (the fallback maxKF, KeyFrame.cpp:254), the choice here is the LEAST SLOT among the
+ *     maxima.  Lists are compared on the full int32 weight; a row entry is an entry iff it is non-zero;
+ *   - list entries and lengths read back from device memory are distrusted: a length is kept inside [0, n_kf], an entry outside
+ *     [0, n_kf) is dropped and counted, never dereferenced.
+ * Every call checks its arguments first (ORBX_E_ARG: a null graph or graph array, n_kf outside [0, cap_kf], a key frame outside
+ * [0, n_kf)), then the limits (ORBX_E_UNSUPPORTED: cap_kf > ORBM_GRAPH_MAX_KF, stride > ORBM_MEDIAN_MAX_STRIDE, cap_points > 524288),
+ * then fails with ORBX_E_NO_DEVICE without a HIP device.  Enqueued on `stream` (NULL: orbx.h, "Streams").
+ *
+ * orbm_update_connections_device: KeyFrame::updateConnections of key frame K = kf_self behind orbm_refresh_points_device's d_covis
+ * (called with the same kf_self), which is the counting loop of :233-242.
+ *   c[j] = d_covis[j] for j != K with d_bad[j] == 0 and d_covis[j] > 0, else 0.  A positive count of a bad key frame is ignored and
+ *     counted in d_result[5]; a negative count, or d_covis[K] != 0, is ignored and counted in [6].
+ *   No c[j] > 0: d_result[1] = 1 and NOTHING of the graph is written (:244).
+ *   S = { j : c[j] >= connect_th }; if S is empty, S = { the least j with c[j] = max } and [2] = 1 (:265-268).
+ *   For every j in S (addConnection, :293-304): if d_weight[j][K] != c[j] then d_weight[j][K] = c[j] and list j is rebuilt from ALL
+ *     non-zero entries of row j; otherwise list j is left exactly as it is.  This is the reference's asymmetry, kept on purpose: a list
+ *     rebuilt by updateBestCovisibles holds the sub-threshold entries that the key frame's own updateConnections put into its map; a
+ *     list written by updateConnections does not hold them.
+ *   Row K becomes c, every column below n_kf (connected_kf_weights = kfCounter, :281: entries of K that are now zero disappear from
+ *     K's row only, the column entries d_weight[j][K] of such j survive).  List K = S in list order, d_ord_n[K] = |S|.
+ *   If d_parent[K] < 0 and K != first_kf (the slot of the key frame with id 0, or -1): d_parent[K] = the head of list K, [4] = 1
+ *     (be_first_connection, :285-289).
+ *   d_work: n_kf int32, the caller's (the marks of the lists to rebuild).  connect_th >= 1 (the reference's is CONNECT_TH = 15).
+ *   d_result (int32 x 8): [0] |S|, [1] nothing to do, [2] fallback used, [3] neighbour lists rebuilt, [4] parent assigned, [5], [6] as
+ *   above, [7] 0.
+ *
+ * orbm_erase_connections_device: the graph part of KeyFrame::setBad, chained behind orbm_cull_keyframes_device.  recent is the HOST
+ * array the culling took (n_recent <= 32, copied into the arguments; more, or an entry outside [0, n_kf), is an argument error), d_code
+ * the culling's device output; with d_code == NULL every entry is processed.  For idx in order with d_code[idx] == 3, c = recent[idx]:
+ *   for every j != c with d_weight[c][j] > 0: if d_weight[j][c] > 0 it becomes 0, list j is rebuilt from its whole row, [1]++
+ *     (eraseConnection, :403-405, :306-317);
+ *   row c becomes all zero and d_ord_n[c] = 0 (:419-420);
+ *   with P = d_parent[c]: every j with d_parent[j] == c gets d_parent[j] = P ([2]++).  This IS what :423-460 do: the loop never inserts
+ *     the chosen child into parentCandidates, so the candidate set stays { parent } and every child, linked to it or not, bad or not,
+ *     ends with changeParent(parent).  The reference's text, not a correction.  With P < 0 the tree is left alone and [3]++ (the
+ *     reference would dereference null).  d_parent[c] itself stays.
+ * Each candidate sees what the ones before it wrote (a culled child of a culled key frame moves twice).  A list's final bytes depend on
+ * its row's final values only, so the lists are rebuilt once, behind the last candidate; [1] counts erases, [4] the lists rebuilt (a
+ * key frame erased itself later in the call is among them and ends with an empty list).  d_work: n_kf int32.
+ *   d_result (int32 x 8): [0] key frames erased, [1] - [3] as above, [4] lists rebuilt, the rest 0.
+ *
+ * orbm_fuse_targets_device: LocalMapping.cpp:263-300.  d_n, d_bad, d_slots, stride, d_valid, cap_points: the layout of
+ * orbm_build_observations_device.
+ *   Targets, sequentially: for a in the first min(n_first, d_ord_n[cur]) entries of list cur: skipped if marked, else appended and
+ *     marked; then for b in the first min(n_second, d_ord_n[a]) entries of list a: skipped if marked or b == cur, else marked and
+ *     appended (a skipped a's list is not walked).  The reference's values are 20 and 5.  The marks are per call: the reference's
+ *     fuse_target_for_kf == current_kf->id stamps are unique per call, and its id-0 coincidence is not restated.  Bad key frames are
+ *     NOT filtered, because the reference does not filter them; they are counted in [3] (their slots are -1 after a cull, so they add
+ *     no row).
+ *   Rows: over the targets in order and their min(max(d_n[k], 0), stride) slots in order, every p in [0, cap_points):
+ *     d_valid[p] == 0 is skipped and counted in [4] (:292); a row is listed at its FIRST occurrence (:296-298), later ones are counted
+ *     in [6].  Rows that cur already observes stay in the list: the fuse's gate handles them, as in the reference.
+ *   d_work: cap_points int32, the caller's (the rows' first occurrences; contents afterwards unspecified).
+ *   d_result (int32 x 8): [0] n_targets and [1] n_rows, both FULL counts; [2] the refusal, a bit mask: 1 more targets than
+ *   cap_targets, 2 more rows than cap_rows -- nothing is written at or past a capacity, and what lies below d_rows' is unspecified on
+ *   a refusal --; [3] bad targets, [4] invalid, [5] list entries dropped for an index out of range, [6] duplicates, [7] 0.
+ *   The caller reads d_result and d_targets back once and runs the per-target chain: one direction orbm_project_fuse_device ->
+ *   orbm_search_fuse_device -> orbm_fuse_apply_device per target, the other with d_rows = this call's d_rows and nq = n_rows.
+ *
+ * orbm_connected_keyframes_device: d_out = [kf if include_self] + the first min(max_n, d_ord_n[kf]) entries of list kf, cut to n_out
+ * entries, then -1 up to n_out; *d_n_out = the number before the fill.  With include_self = 1 and max_n = n_kf this is d_local of
+ * orbm_local_ba_problem_device, which already drops entries outside [0, n_kf): the caller passes n_local = n_out without a read-back.
+ *
+ * Shape (latency, not throughput).  k_graph_update and k_graph_erase are ONE workgroup of 1024 threads each; they mark the rows whose
+ * list changes in d_work, and k_graph_resort, launched behind them with one workgroup per key frame, rebuilds the marked ones -- a
+ * workgroup reads its own mark and row and writes its own list, nothing another workgroup writes in that launch.  A list is sorted as
+ * 64-bit keys (weight complement above the slot: distinct, so the order is the bytes) by a bitonic network in LDS, 32 KB for 4096
+ * keys.  k_graph_fuse_targets is one workgroup: wave 0 walks the lists while the others clear d_work, then the rows' first occurrences
+ * by atomicMin (the least key wins whatever the order) and the slots in order, a tile of 1024 at a time, numbered by a block scan.
+ * As compiled for gfx950 -- VGPRs / scratch / static LDS: k_graph_update 26 / 0 / 32808 B, k_graph_erase 24 / 0 / 32 B, k_graph_resort
+ * 12 / 0 / 32776 B, k_graph_fuse_targets 52 / 0 / 16992 B, k_graph_connected 9 / 0 / 0 B: no scratch memory, at most 64 VGPRs. */
+#define ORBM_GRAPH_MAX_KF 4096
+typedef struct orbm_covis_graph {
+    int32_t cap_kf;        /* row pitch of the two matrices, <= ORBM_GRAPH_MAX_KF */
+    int32_t *d_weight;     /* [cap_kf][cap_kf]  connected_kf_weights of key frame k: d_weight[k * cap_kf + j], 0 = no entry */
+    int32_t *d_ord_kf;     /* [cap_kf][cap_kf]  ordered_connected_kfs of k: the first d_ord_n[k] entries of row k */
+    int32_t *d_ord_n;      /* [cap_kf] */
+    int32_t *d_parent;     /* [cap_kf]  spanning-tree parent, -1 = none yet (be_first_connection) */
+} orbm_covis_graph;
+int orbm_update_connections_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, const uint8_t *d_bad, const int32_t *d_covis,
+                                   int kf_self, int first_kf, int connect_th, int32_t *d_work, int32_t *d_result, void *stream);
+int orbm_erase_connections_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, const int32_t *recent, int n_recent,
+                                  const int32_t *d_code, int32_t *d_work, int32_t *d_result, void *stream);
+int orbm_fuse_targets_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, const int32_t *d_n, const uint8_t *d_bad,
+                             const int32_t *d_slots, int stride, const uint8_t *d_valid, int cap_points, int cur, int n_first,
+                             int n_second, int cap_targets, int cap_rows, int32_t *d_work, int32_t *d_targets, int32_t *d_rows,
+                             int32_t *d_result, void *stream);
+int orbm_connected_keyframes_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, int kf, int include_self, int max_n,
+                                    int32_t *d_out, int n_out, int32_t *d_n_out, void *stream);
 
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,

@@ -62,6 +62,29 @@ class KfTable(C.Structure):
         return t
 
 
+class CovisGraph(C.Structure):
+    """orbm_covis_graph (include/orbm.h): a host struct of device pointers to the covisibility graph and the spanning tree."""
+    _fields_ = [("cap_kf", C.c_int32), ("d_weight", C.c_void_p), ("d_ord_kf", C.c_void_p), ("d_ord_n", C.c_void_p), ("d_parent", C.c_void_p)]
+    CONNECT_TH = 15   # modules/BasicObject/KeyFrame.h:24
+
+    @classmethod
+    def make(cls, weight, ord_kf, ord_n, parent):
+        """torch device tensors, i32: weight, ord_kf [cap_kf, cap_kf] (weight and ord_n zero-filled once), ord_n, parent [cap_kf]
+        (parent filled with -1 once)."""
+        cap = int(ord_n.shape[0])
+        assert weight.numel() == cap * cap and ord_kf.numel() == cap * cap and parent.numel() == cap
+        g = cls(cap, weight.data_ptr(), ord_kf.data_ptr(), ord_n.data_ptr(), parent.data_ptr())
+        g._keep = (weight, ord_kf, ord_n, parent)
+        return g
+
+    @classmethod
+    def empty(cls, cap_kf, device):
+        """an empty graph of cap_kf key frames on `device`, initialised as the header asks"""
+        import torch
+        z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=device)  # noqa: E731
+        return cls.make(z(cap_kf, cap_kf), z(cap_kf, cap_kf), z(cap_kf), torch.full((cap_kf,), -1, dtype=torch.int32, device=device))
+
+
 def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -125,6 +148,11 @@ def _mlib():
                                              + [vp] * 16),
             "orbm_local_ba_apply_device": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32]
                                            + [vp] * 11),
+            "orbm_update_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, i32, i32, i32, vp, vp, vp]),
+            "orbm_erase_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, i32, vp, vp, vp, vp]),
+            "orbm_fuse_targets_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp,
+                                               vp, vp]),
+            "orbm_connected_keyframes_device": (i32, [vp, C.POINTER(CovisGraph), i32, i32, i32, i32, vp, i32, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -497,6 +525,47 @@ class ORBMatcher:
             self._hd._h, p("best_idx"), opt("rows"), nq, n_kf, kf_target, p("n"), p("bad"), p("slots"), stride, p("valid"), cap_points,
             p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, opt("found"), opt("visible"), p("work"), p("code"), p("refresh_sel"),
             p("result"), _lib.stream_arg(stream)))
+
+    # -- the covisibility graph and the spanning tree on the device (KeyFrame.cpp:225-362, :402-467; LocalMapping.cpp:263-300) ----
+    def UpdateConnectionsDevice(self, graph, d, n_kf, kf_self, first_kf=-1, connect_th=CovisGraph.CONNECT_TH, stream=None):
+        """orbm_update_connections_device: graph a CovisGraph (in / out).  d = dict of torch device tensors -- in: bad u8 [n_kf], covis
+        i32 [n_kf] (as RefreshPointsDevice leaves it for the same kf_self); work i32 [n_kf] (the call's work array); out: result i32 [8]
+        ([0] connections of kf_self, [1] nothing to do, [2] fallback, [3] neighbour lists rebuilt, [4] parent assigned).  Enqueues on
+        `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_update_connections_device(
+            self._hd._h, C.byref(graph), n_kf, p("bad"), p("covis"), kf_self, first_kf, connect_th, p("work"), p("result"),
+            _lib.stream_arg(stream)))
+
+    def EraseConnectionsDevice(self, graph, d, n_kf, recent, stream=None):
+        """orbm_erase_connections_device: the graph part of KeyFrame::setBad behind CullKeyFramesDevice.  recent: the host sequence the
+        culling took (at most 32).  d = dict of torch device tensors -- in: code i32 [n_recent] (the culling's; optional: without it
+        every entry of recent is erased); work i32 [n_kf]; out: result i32 [8] ([0] erased, [1] connections erased, [2] children moved,
+        [3] without a parent, [4] lists rebuilt).  Enqueues on `stream`; nothing is copied or synchronised."""
+        rec = np.ascontiguousarray(recent, dtype=np.int32)
+        assert rec.ndim == 1
+        code = d.get("code")
+        _lib.check(self._L.orbm_erase_connections_device(
+            self._hd._h, C.byref(graph), n_kf, _vp(rec), len(rec), code.data_ptr() if code is not None else None, d["work"].data_ptr(),
+            d["result"].data_ptr(), _lib.stream_arg(stream)))
+
+    def FuseTargetsDevice(self, graph, d, n_kf, stride, cap_points, cur, cap_targets, cap_rows, n_first=20, n_second=5, stream=None):
+        """orbm_fuse_targets_device (LocalMapping.cpp:263-300): d = dict of torch device tensors -- in: n i32 [n_kf], bad u8 [n_kf], slots
+        i32 [n_kf,stride], valid u8 [cap]; work i32 [cap] (the call's work array); out: targets i32 [cap_targets], rows i32 [cap_rows]
+        (FuseApplyDevice's rows for the direction into `cur`), result i32 [8] ([0] targets, [1] rows, full counts; [2] refusal mask).
+        Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_fuse_targets_device(
+            self._hd._h, C.byref(graph), n_kf, p("n"), p("bad"), p("slots"), stride, p("valid"), cap_points, cur, n_first, n_second,
+            cap_targets, cap_rows, p("work"), p("targets"), p("rows"), p("result"), _lib.stream_arg(stream)))
+
+    def ConnectedKeyFramesDevice(self, graph, d, n_kf, kf, include_self=True, max_n=None, stream=None):
+        """orbm_connected_keyframes_device: d = dict(out i32 [n_out], n_out i32 [1]), torch device tensors.  out = [kf if include_self] +
+        the first max_n (default: all) entries of kf's list, then -1: with include_self it is LocalBaProblemDevice's `local` with
+        n_local = len(out).  Enqueues on `stream`; nothing is copied or synchronised."""
+        _lib.check(self._L.orbm_connected_keyframes_device(
+            self._hd._h, C.byref(graph), n_kf, kf, int(bool(include_self)), n_kf if max_n is None else max_n, d["out"].data_ptr(),
+            int(d["out"].shape[0]), d["n_out"].data_ptr(), _lib.stream_arg(stream)))
 
     # -- Optimize::localBundleAdjustment on the slot arrays: the problem assembled, the result applied (Optimize.cpp:766-889, :914-950) --
     def LocalBaProblemDevice(self, kf, d, stride, cap_points, n_obs, n_local, first_kf, cap_poses, cap_local_points, cap_edges, stream=None):
