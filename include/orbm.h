@@ -860,6 +860,99 @@ int orbm_fuse_targets_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf,
 int orbm_connected_keyframes_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, int kf, int include_self, int max_n,
                                     int32_t *d_out, int n_out, int32_t *d_n_out, void *stream);
 
+/* ---- The tracker's local map on the device -----------------------------------------------------------------------------------------
+ * What Tracking::trackLocalMap (modules/Frontend/Tracking.cpp:345-373) does around its search and its pose optimisation, on the arrays
+ * the sections above own: updateLocalKeyFrames + updateLocalMapPoints (:429-537), which decide what the second SearchByProjection of
+ * every frame may see; the increaseVisible / increaseFound counters (:388-412, :362-364) that orbm_fuse_apply_device reads as
+ * d_visible / d_found; and KeyFrame::getNumTrackedMapPoint of the reference key frame (KeyFrame.cpp:146-152), which needNewKeyFrame
+ * tests (:544-545).  With them stage 1 -> orbm_local_map_device -> orbm_project_frustum_device -> orbm_track_counters_device (1 | 2) ->
+ * the points search -> orbba_pose_edges_device -> poseOptimize -> orbba_pose_drop_outliers_device -> orbm_track_counters_device (4) ->
+ * orbm_num_tracked_points_device runs on one stream without a host hop between the two stages.  The map side's rules hold: device
+ * pointers only and deliberately NO host-pointer twin; no allocation, handle scratch or host wait; integer only, written not
+ * accumulated (the two counter arrays aside: they are counters), the same bytes on every run; everything read back from device memory
+ * is distrusted: clamped, dropped and counted, never dereferenced.  Arguments are checked first (ORBX_E_ARG: a null pointer, a negative
+ * count, n_kf outside [0, cap_kf], a bad entry of recent), then the limits (ORBX_E_UNSUPPORTED: cap_kf > ORBM_GRAPH_MAX_KF, stride or n2
+ * > ORBM_MEDIAN_MAX_STRIDE, cap_points > 524288), then the call fails with ORBX_E_NO_DEVICE without a HIP device.  Enqueued on `stream`
+ * (NULL: orbx.h, "Streams").
+ * d_n, d_bad, d_slots, stride, d_valid, cap_points and the CSR (d_obs_off / d_obs_kf / d_obs_kp, n_obs): the layout of
+ * orbm_build_observations_device and what it left.  The CSR is read with the culling's distrust: offsets that do not describe a list
+ * inside [0, n_obs] give an empty list; an entry (k, i') whose key frame is outside [0, n_kf) or whose feature is outside [0,
+ * min(max(d_n[k], 0), stride)) is DROPPED; an entry of row p that is not LIVE (d_slots[k * stride + i'] == p and d_bad[k] == 0) is
+ * STALE and skipped.  Both kinds are counted.
+ *
+ * orbm_local_map_device.  d_frame_mp [n2], in / out: the slots of the frame the reference votes from -- the current frame, or the last
+ * frame once the IMU is initialised (:432-460); the caller passes whichever applies.  Values are table rows.
+ *   Votes.  For i < n2, p = d_frame_mp[i]: p outside [0, cap_points): nothing happens; d_valid[p] == 0: d_frame_mp[i] = -1, [5]++
+ *     (:441-443); otherwise every live CSR entry (k, i') of row p adds one to votes[k] (dropped entries [6]++, stale ones [7]++).  This
+ *     is per entry of d_frame_mp: a row named twice votes twice, as the reference's loop does.
+ *   The list.  First the entries of recent in order, each marked (:466-470): recent is a HOST array of key-frame slots in
+ *     Map::getRecentKeyFrames(10) order (Map.cpp:42-53: oldest first), n_recent <= 32, copied into the launch's arguments as
+ *     orbm_erase_connections_device does; more, an entry outside [0, n_kf) or a repeated entry is an argument error.  The reference does
+ *     not test them for bad, so neither does this; bad ones are counted in [9].  Then every k with votes[k] > 0 ([8] of them) in
+ *     ASCENDING SLOT ORDER, appended and marked unless already marked; maxKF is the LEAST SLOT among the maxima of the votes.  Both are
+ *     stated canonicalisations where the reference iterates an unordered_map<shared_ptr<KeyFrame>, int> (:474-487), the same two the
+ *     graph section makes.  The kf->isBad() of :476 cannot be met: a live entry has no bad key frame.
+ *   Expansion (:490-519), sequential and literal.  Positions 0 .. end0 - 1 of the list, end0 fixed at the length the two steps above
+ *     left (iterEnd is taken once).  At each position, kf = the entry there:
+ *       1. the list's length > max_kf: stop ([11] = 1);
+ *       2. the first min(n_neigh, d_ord_n[kf]) entries of list kf: each that is neither bad nor marked is appended and marked (an
+ *          entry outside [0, n_kf) is dropped, [10]++; the length is kept inside [0, n_kf]);
+ *       3. the first child not bad and not marked -- the least j < n_kf with d_parent[j] == kf, ascending slot standing in for the
+ *          reference's std::set<shared_ptr> order -- is appended and marked; at most one;
+ *       4. d_parent[kf] in [0, n_kf) and not marked: appended and marked, and THE WHOLE WALK ENDS ([11] = 2).
+ *     Step 4 is the reference's text, not a correction: the `break` of :517 sits in the outer `for`, and the parent is not tested for
+ *     bad.  The walk running out of positions gives [11] = 0.  The reference's values are n_neigh = 10 and max_kf = 80.  The marks are
+ *     per call: the track_frame_id == current_frame->id stamps are unique per frame, and their id-0 coincidence is not restated.
+ *   Points (:525-537).  Over the list in order and each key frame's min(max(d_n[k], 0), stride) slots in order, every p in [0,
+ *     cap_points) with d_valid[p] != 0 at its FIRST occurrence; later occurrences are counted in [13], invalid rows in [12].
+ *   Outputs.  d_local_kf [cap_local_kf]: the list.  d_rows [cap_rows]: local_map_points in the order above.  d_local_mask [cap_points]
+ *     uint8, EVERY entry written: 1 iff the row is in d_rows.  d_ref (device int32, in / out): maxKF when there is one, else untouched
+ *     (:522).  Nothing is written at or past a capacity; on a refusal ([2] != 0) the mask is ALL ZERO, d_ref is untouched and what lies
+ *     below the capacities is unspecified.  The clearing of d_frame_mp happens regardless: it is idempotent and the reference's first act.
+ *   d_work: cap_points + n_kf int32, the caller's, the size of orbm_local_ba_problem_device's (the rows' first occurrences in the first
+ *   cap_points; contents afterwards unspecified).
+ *   d_result (int32 x 16, written): [0] key frames and [1] rows, both FULL counts; [2] the refusal, a bit mask: 1 more key frames than
+ *   cap_local_kf, 2 more rows than cap_rows; [3] maxKF or -1, [4] its votes; [5] - [13] as above; [14], [15] 0.
+ *   WHY A MASK.  d_local_mask goes straight into orbm_project_frustum_device as d_valid with nq = the table's row count, so the
+ *   queries, and the frame_mp the search fills, stay in the one index space orbba_pose_edges_device documents.  This runs the points
+ *   search in ASCENDING ROW ORDER; the reference's order descends from unordered_map iteration, which nothing reproduces.  d_rows is
+ *   the reference-shaped list for a caller that gathers instead.
+ *
+ * orbm_track_counters_device: the counters of one tracked frame.  d_visible, d_found: int32 [cap_points], ACCUMULATED by design.  what,
+ * a bit mask (0 .. 7):
+ *   1  :388-398.  A slot of d_frame_mp [n2] (in / out) in [0, cap_points) with d_valid == 0 becomes -1 ([3]++); otherwise
+ *      d_visible[p]++ ([0]++).
+ *   2  :406-408.  d_visible[q]++ for every q < nq with d_q_ok[q] != 0 ([1]++): the frustum builder's q_ok IS that loop's isInFrustum,
+ *      and its "already in the frame" gate is :404.  Needs d_q_ok and nq <= cap_points (ORBX_E_ARG); d_q_ok may be NULL without it.
+ *   4  :362-364.  d_found[p]++ for every slot in [0, cap_points) ([2]++), with no test for bad, as there; a slot that bit 1 of the same
+ *      call cleared is not counted.
+ * A caller issues 1 | 2 behind the builder and 4 behind poseOptimize and the drop.  d_result (int32 x 8, written): [0] - [3], the rest 0.
+ *
+ * orbm_num_tracked_points_device: KeyFrame::getNumTrackedMapPoint(min_obs).  d_kf is a DEVICE int32, the d_ref orbm_local_map_device
+ * leaves, so no read-back sits in between; it is distrusted: outside [0, n_kf) gives d_count[0] = 0 and d_count[1] = 1.  d_count[0] =
+ * the slots of that key frame holding a p in [0, cap_points) whose live CSR entries number at least min_obs.  No test for bad, as in
+ * the reference: a bad row has no live entry, so it fails any min_obs >= 1.  d_count (int32 x 4, written): [0], [1], [2] CSR entries
+ * dropped for an index out of range, [3] 0.  The comparison num_inlier < numRefMatch * theRefRatio stays with the caller.
+ *
+ * Shape (latency, not throughput).  k_local_map is ONE workgroup of 1024 threads: the votes are an LDS array of n_kf ints filled by LDS
+ * atomics, a thread per frame slot walking its row's list; the marks are one bit per key frame in LDS; the voted key frames are
+ * appended behind a block scan over the slots in order; wave 0 runs the expansion, its lanes across a neighbour list and a ballot for
+ * the first child, while the other waves clear d_work; then the rows' first occurrences by atomicMin (the least key wins whatever the
+ * order) and the slots in order, a tile of 1024 at a time, numbered by a block scan.  The two small calls clear their result and run a
+ * thread per slot / per query.
+ * As compiled for gfx950 -- VGPRs / scratch / static LDS: k_local_map 60 / 0 / 33412 B, k_track_counters 14 / 0 / 0 B, k_num_tracked
+ * 20 / 0 / 0 B: no scratch memory, at most 64 VGPRs. */
+int orbm_local_map_device(orbm_t *h, int32_t *d_frame_mp, int n2, const uint8_t *d_valid, int cap_points, const int32_t *d_obs_off,
+                          const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs, int n_kf, const int32_t *d_n, const uint8_t *d_bad,
+                          const int32_t *d_slots, int stride, const orbm_covis_graph *graph, const int32_t *recent, int n_recent,
+                          int n_neigh, int max_kf, int cap_local_kf, int cap_rows, int32_t *d_work, int32_t *d_local_kf, int32_t *d_rows,
+                          uint8_t *d_local_mask, int32_t *d_ref, int32_t *d_result, void *stream);
+int orbm_track_counters_device(orbm_t *h, int32_t *d_frame_mp, int n2, const uint8_t *d_valid, int cap_points, const uint8_t *d_q_ok,
+                               int nq, int what, int32_t *d_visible, int32_t *d_found, int32_t *d_result, void *stream);
+int orbm_num_tracked_points_device(orbm_t *h, const int32_t *d_kf, int min_obs, int n_kf, const int32_t *d_n, const uint8_t *d_bad,
+                                   const int32_t *d_slots, int stride, int cap_points, const int32_t *d_obs_off, const int32_t *d_obs_kf,
+                                   const int32_t *d_obs_kp, int n_obs, int32_t *d_count, void *stream);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

@@ -153,6 +153,10 @@ def _mlib():
             "orbm_fuse_targets_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp,
                                                vp, vp]),
             "orbm_connected_keyframes_device": (i32, [vp, C.POINTER(CovisGraph), i32, i32, i32, i32, vp, i32, vp, vp]),
+            "orbm_local_map_device": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, C.POINTER(CovisGraph), vp, i32, i32, i32, i32,
+                                            i32, vp, vp, vp, vp, vp, vp, vp]),
+            "orbm_track_counters_device": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
+            "orbm_num_tracked_points_device": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -566,6 +570,45 @@ class ORBMatcher:
         _lib.check(self._L.orbm_connected_keyframes_device(
             self._hd._h, C.byref(graph), n_kf, kf, int(bool(include_self)), n_kf if max_n is None else max_n, d["out"].data_ptr(),
             int(d["out"].shape[0]), d["n_out"].data_ptr(), _lib.stream_arg(stream)))
+
+    # -- the tracker's local map, its counters and the reference key frame's tracked points (Tracking.cpp:345-537, KeyFrame.cpp:146-152) --
+    def LocalMapDevice(self, graph, d, n2, n_kf, stride, cap_points, n_obs, recent, cap_local_kf, cap_rows, n_neigh=10, max_kf=80, stream=None):
+        """orbm_local_map_device (Tracking.cpp:429-537): graph a CovisGraph (read).  recent: the host sequence of key-frame slots of
+        Map::getRecentKeyFrames(10), oldest first (at most 32).  d = dict of torch device tensors -- in / out: frame_mp i32 [n2] (slots
+        naming a bad row become -1), ref i32 [1] (the reference key frame: written when a key frame got a vote); in: valid u8 [cap],
+        obs_off, obs_kf, obs_kp (the CSR BuildObservationsDevice left), n i32 [n_kf], bad u8 [n_kf], slots i32 [n_kf,stride]; work i32
+        [cap + n_kf] (the call's work array); out: local_kf i32 [cap_local_kf], rows i32 [cap_rows], local_mask u8 [cap]
+        (ProjectFrustumDevice's `valid` with nq = cap), result i32 [16] ([0] key frames, [1] rows, full counts; [2] refusal mask).
+        Enqueues on `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        rec = np.ascontiguousarray(recent, dtype=np.int32)
+        assert rec.ndim == 1
+        _lib.check(self._L.orbm_local_map_device(
+            self._hd._h, p("frame_mp"), n2, p("valid"), cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, n_kf, p("n"), p("bad"),
+            p("slots"), stride, C.byref(graph), _vp(rec), len(rec), n_neigh, max_kf, cap_local_kf, cap_rows, p("work"), p("local_kf"), p("rows"),
+            p("local_mask"), p("ref"), p("result"), _lib.stream_arg(stream)))
+
+    def TrackCountersDevice(self, d, n2, cap_points, nq, what, stream=None):
+        """orbm_track_counters_device: what = 1 (Tracking.cpp:388-398: frame slots naming a bad row become -1, the others' rows are
+        visible) | 2 (:406-408: every query the frustum builder left on is visible) | 4 (:362-364: the frame's rows are found).  d =
+        dict of torch device tensors -- in / out: frame_mp i32 [n2], visible, found i32 [cap] (counters: accumulated); in: valid u8
+        [cap], q_ok u8 [nq] (ProjectFrustumDevice's; optional without bit 2); out: result i32 [8] ([0] - [2] the three counts, [3] slots
+        cleared).  Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        opt = lambda k: d[k].data_ptr() if d.get(k) is not None else None  # noqa: E731
+        _lib.check(self._L.orbm_track_counters_device(
+            self._hd._h, p("frame_mp"), n2, p("valid"), cap_points, opt("q_ok"), nq, what, opt("visible"), opt("found"), p("result"),
+            _lib.stream_arg(stream)))
+
+    def NumTrackedPointsDevice(self, d, n_kf, stride, cap_points, n_obs, min_obs, stream=None):
+        """orbm_num_tracked_points_device (KeyFrame.cpp:146-152): d = dict of torch device tensors -- in: ref i32 [1] (the key frame, as
+        LocalMapDevice leaves it: no read-back in between), n i32 [n_kf], bad u8 [n_kf], slots i32 [n_kf,stride], obs_off, obs_kf, obs_kp;
+        out: count i32 [4] ([0] the slots whose row has at least min_obs live observations, [1] ref is not a key frame).  Enqueues on
+        `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_num_tracked_points_device(
+            self._hd._h, p("ref"), min_obs, n_kf, p("n"), p("bad"), p("slots"), stride, cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs,
+            p("count"), _lib.stream_arg(stream)))
 
     # -- Optimize::localBundleAdjustment on the slot arrays: the problem assembled, the result applied (Optimize.cpp:766-889, :914-950) --
     def LocalBaProblemDevice(self, kf, d, stride, cap_points, n_obs, n_local, first_kf, cap_poses, cap_local_points, cap_edges, stream=None):
