@@ -594,8 +594,8 @@ int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, uint8_t *d_ba
  * loser.  Integer only.  Device pointers only, and deliberately NO host-pointer twin, for the refresh's reason: the reference-signature
  * shims (compat/) keep their host objects.
  * The list of fuseMapPoints itself -- the de-duplicated union of the target key frames' slots (LocalMapping.cpp:287-300) -- is
- * orbm_fuse_targets_device's d_rows ("The covisibility graph on the device").  Out of scope, the caller's: Map::eraseMapPoint and
- * MapPointCulling.
+ * orbm_fuse_targets_device's d_rows ("The covisibility graph on the device").  Out of scope, the caller's: Map::eraseMapPoint
+ * (MapPointCulling is orbm_cull_map_points_device, "Key frames inserted and recent map points culled on the device").
  *
  * Entries: d_best_idx [nq] as orbm_search_fuse_device leaves it; entry j is table row d_rows[j], or row j when d_rows is NULL (the
  * builders index the table by query).  kf_target = K, the key frame searched.  d_n, d_bad, d_slots (in / out), stride: the layout of
@@ -667,7 +667,7 @@ int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, const int32_t *
  * ints of the LM call) and the LM call waits for one small block per trial; no table, slot array or index returns to the host, and
  * no host loop runs over points or observations.  mp->update() (:948) is orbm_refresh_points_device with d_sel = d_point_row behind a
  * rebuilt CSR; it is not repeated here.  d_local (getConnectedKFs) is orbm_connected_keyframes_device's d_out ("The covisibility graph on
- * the device"); only MapPointCulling and Map::eraseMapPoint stay with the caller.
+ * the device"), MapPointCulling is orbm_cull_map_points_device; only Map::eraseMapPoint stays with the caller.
  * The two calls below follow this header's rules for the map side: device pointers only and deliberately NO host-pointer twin; no
  * allocation, handle scratch or host wait; results written, not accumulated; the same bytes on every run; every index that comes
  * from device memory is distrusted -- dropped and counted, never dereferenced out of range.  THE SLOT ARRAYS ARE THE TRUTH and the CSR
@@ -952,6 +952,108 @@ int orbm_track_counters_device(orbm_t *h, int32_t *d_frame_mp, int n2, const uin
 int orbm_num_tracked_points_device(orbm_t *h, const int32_t *d_kf, int min_obs, int n_kf, const int32_t *d_n, const uint8_t *d_bad,
                                    const int32_t *d_slots, int stride, int cap_points, const int32_t *d_obs_off, const int32_t *d_obs_kf,
                                    const int32_t *d_obs_kp, int n_obs, int32_t *d_count, void *stream);
+
+/* ---- Key frames inserted and recent map points culled on the device ---------------------------------------------------------------
+ * The start of every mapper step, which the sections above left on the host: Tracking::createNewKeyFrame with the KeyFrame constructor
+ * (modules/Frontend/Tracking.cpp:578-588, modules/BasicObject/KeyFrame.cpp:15-25) and the loop of LocalMapping::processNewKeyFrame
+ * (modules/Frontend/LocalMapping.cpp:93-105); the Map / KeyFrame bookkeeping of a triangulated point (:243-248) with the fields of the
+ * MapPoint constructor that orbm_triangulate_matches_device does not write (MapPoint.cpp:18, :24-25); and LocalMapping::MapPointCulling
+ * (:117-144) with the cascade of MapPoint::setBad (MapPoint.cpp:210-226).  With them the non-inertial body of LocalMapping::Run (:29-62)
+ * has a device form for every step, and a tracked frame -- d_frame_mp and the pose orbba_pose_optimize_batch_device left -- becomes a
+ * key frame without a read-back.  The map side's rules hold: device pointers only and deliberately NO host-pointer twin; no allocation,
+ * handle scratch or host wait; results written, not accumulated; the same bytes on every run (counts are sums, and no stored value
+ * depends on the order atomics arrive in); THE SLOT ARRAYS ARE THE TRUTH, the CSR only says where to look and is never rewritten;
+ * every index or count read from device memory is distrusted: clamped, or dropped and counted, never dereferenced out of range.
+ * Arguments are checked first (ORBX_E_ARG: a null pointer, a negative count, K outside [0, cap_kf), a negative id), then the limits
+ * (ORBX_E_UNSUPPORTED: stride > ORBM_MEDIAN_MAX_STRIDE, cap_points > 524288), then the call fails with ORBX_E_NO_DEVICE without a HIP
+ * device.  Enqueued on `stream` (NULL: orbx.h, "Streams").
+ *
+ * orbm_insert_keyframe_device.  K: the new key frame's slot, the caller's choice, in [0, cap_kf).  d_pose_R [cap_kf][9], d_pose_t
+ * [cap_kf][3], d_bad, d_kps, d_desc, d_n [cap_kf]: the arrays an orbm_kf_table points to, here as their owner holds them (the two
+ * pointer arrays pointer aligned).  d_slots, stride, d_valid, cap_points: the layout of orbm_build_observations_device.  The frame:
+ * d_frame_mp [n2], table rows in the convention of orbm_track_counters_device, READ ONLY (the reference erases on the KeyFrame, not
+ * on the Frame) and not overlapping d_slots; d_frame_pose_R [9] / d_frame_pose_t [3], device doubles as the pose optimisation leaves
+ * them; frame_kps / frame_desc, the HOST VALUES of the device pointers to the frame's orbx_kp records and descriptors.
+ *   Row K of the table: the pose copied bit for bit, d_bad[K] = 0, d_n[K] = n2, d_kps[K] = frame_kps, d_desc[K] = frame_desc.
+ *   EVERY one of the stride slots of row K is written, so nothing of an earlier use of the row survives.  Slot i < min(n2, stride),
+ *   p = d_frame_mp[i]:
+ *     p == -1                                the slot becomes -1
+ *     else p outside [0, cap_points)         the slot becomes -1, [3]++
+ *     else d_valid[p] == 0                   the slot becomes -1, [2]++: eraseMapPoint (:98)
+ *     else                                   the slot becomes p, [0]++: the slot IS the observation, so addObservation (:100) is this store
+ *   Slots i >= min(n2, stride) become -1.  A row that a lower slot of K already names keeps its second slot -- the reference's
+ *   map_points[i] keeps it too, only addObservation refuses (MapPoint.cpp:184) -- and is counted in [4] as (slots holding a point) -
+ *   (distinct rows), through a mask of one bit per table row, so the count does not depend on order; orbm_build_observations_device
+ *   emits both entries of such a row and counts it.
+ *   d_result (int32 x 8, written): [0] slots holding a point, [1] 0, [2] slots cleared because the row is invalid, [3] values outside
+ *   [0, cap_points) other than -1, [4] slots naming a row that a lower slot of K already names, [5] max(n2 - stride, 0), [6], [7] 0.
+ *   The chain.  `mp->computeDescriptor(); mp->update();` (:101-102) and `current_kf->updateConnections()` (:108) are the calls the
+ *   sections above have: this call -> orbm_build_observations_device -> orbm_refresh_points_device with d_sel = d_slots + K * stride,
+ *   n_sel = stride and kf_self = K -> orbm_update_connections_device with the same kf_self.
+ *
+ * orbm_register_new_points_device: what LocalMapping.cpp:243-248 and MapPoint.cpp:18, :24-25 leave for the rows that
+ * orbm_triangulate_matches_device appended.  d_n_points: the device int the triangulation advances; d_n_registered: a device int,
+ * in / out, rows below it are finished; K: the current key frame's slot; kf_id: its KeyFrame::id, by which the culling ages points --
+ * it counts culled key frames too, so a caller that never reuses a slot passes K.  d_ref_kf (the refresh's), d_first_kf, d_found,
+ * d_visible (the counters of orbm_track_counters_device): int32 [cap_points].  d_recent [cap_recent] with the device int d_n_recent,
+ * in / out: recent_map_points as table rows.
+ *   a = clamp(*d_n_registered, 0, cap_points), b = clamp(*d_n_points, 0, cap_points), r = clamp(*d_n_recent, 0, cap_recent).
+ *   Refusal 2 when a > b; refusal 1 when r + (b - a) > cap_recent; on a refusal nothing but d_result is written ([4] is then r).
+ *   Otherwise for rows a .. b - 1: d_ref_kf = K, d_first_kf = kf_id, d_found = d_visible = 1, d_recent[r + (row - a)] = row -- ascending
+ *   row order, the creation order, the reference's push_back order -- then *d_n_recent = r + (b - a) and *d_n_registered = b.
+ *   Rows are registered whether or not a fuse has set them bad meanwhile: the reference pushes at creation and the culling removes them.
+ *   One call may follow each triangulation or only the last one of a step; the bytes are the same either way.
+ *   d_result (int32 x 8, written): [0] rows registered, [1] the refusal, [2] a, [3] b, [4] the new *d_n_recent, [5] - [7] 0.
+ *
+ * orbm_cull_map_points_device.  d_recent / d_n_recent (in / out), cap_recent: the list above; cur_kf_id: current_kf->id; d_first_kf,
+ * d_found, d_visible: read only; d_valid, d_slots: in / out; n_kf, d_n, d_bad, stride, cap_points and the CSR (d_obs_off / d_obs_kf /
+ * d_obs_kp, n_obs): the layout of orbm_build_observations_device and what it left from these slots.  n = clamp(*d_n_recent, 0,
+ * cap_recent).  For entry j < n, p = d_recent[j]; the first rule that applies decides d_code[j] (d_code [cap_recent], int32; entries at
+ * and past n are not written):
+ *   -1  p outside [0, cap_points)                                                      dropped from the list, [7]++
+ *    1  d_valid[p] == 0                                                         :126   removed from the list, [2]++ (numBad)
+ *    2  (float) d_found[p] / (float) d_visible[p] < 0.25f      :129, MapPoint.cpp:278   setBad(p), removed, [3]++ (numFoundRatio)
+ *    3  (uint32_t) cur_kf_id - (uint32_t) d_first_kf[p] >= 2 and numObs(p) <= 2  :133   setBad(p), removed, [4]++
+ *    4  that difference > 2                                                     :136   removed from the list only, [5]++
+ *    0  otherwise                                                                      kept, [0]++
+ *   The float division is literal: 0 / 0 is NaN and compares false, x / 0 is +-inf, negative counts divide as they are.  The reference's
+ *   difference is unsigned 64-bit (an unsigned int less an unsigned long); for non-negative ids the 32-bit wrap gives the same two
+ *   verdicts: a first id above the current one wraps to at least 2^31 + 1 here and to nearly 2^64 there, both beyond 2.
+ *   numObs(p) = the LIVE CSR entries of p (the slot names p now and its key frame is not bad): getNumObs() as orbm_fuse_apply_device
+ *   defines it.  setBad(p): d_valid[p] = 0 and d_slots[k * stride + i] = -1 for every live entry ([6]++ each); a slot in a bad key frame
+ *   is no observation and stays, as in the fuse.  No list-length limit: nothing is staged, a list is walked as it is.  The CSR is read
+ *   with the culling's distrust: offsets that do not describe a list inside [0, n_obs] give an empty list; an entry whose key frame is
+ *   outside [0, n_kf) or whose feature is outside [0, min(max(d_n[k], 0), stride)) is dropped, never dereferenced, and counted in [7]
+ *   once each over all of [0, n_obs).
+ *   The kept entries are compacted IN PLACE in list order -- a tile's reads, a barrier, its writes behind a block scan -- and
+ *   *d_n_recent becomes their number; the entries of d_recent at and past it are as passed.
+ *   Why it is parallel: a setBad touches only slots that name its own row and numObs(q) reads only slots that name q, so entries of
+ *   different rows do not interact and a thread per entry gives the sequential loop's result.  The one premise, that no row occurs
+ *   twice in the list (the reference's list gets one push_back per constructed point), is checked over all tiles BEFORE anything is
+ *   written: on a violation d_result = {0, 1, 0 ...} and d_recent, *d_n_recent, d_valid, d_slots and d_code are exactly as passed.
+ *   d_result (int32 x 8, written): [0] kept, [1] the refusal, [2] already bad, [3] found ratio, [4] few observations, [5] aged out, [6]
+ *   slots cleared, [7] entries of code -1 plus CSR entries dropped.  Map::eraseMapPoint stays with the caller, who reads d_code; rows
+ *   are never reused.
+ *
+ * Shape (latency, not throughput: hundreds to a few thousand entries).  Each call is ONE launch of ONE workgroup of 1024 threads that
+ * walks its input in tiles of 1024 with workgroup barriers between the phases.  k_kf_insert and k_kf_cull_points keep one bit per table
+ * row in dynamic LDS (cap_points / 8 bytes, hence cap_points <= 524288): the distinct rows of K, and the premise.  k_kf_register reads
+ * its three counters in every thread ahead of a barrier, and one thread rewrites them behind the last tile.
+ * As compiled for gfx950 -- VGPRs / scratch / static LDS: k_kf_insert 16 / 0 / 32 B, k_kf_register 32 / 0 / 0 B, k_kf_cull_points
+ * 42 / 0 / 352 B: no scratch memory, at most 64 VGPRs. */
+int orbm_insert_keyframe_device(orbm_t *h, int K, int cap_kf, double *d_pose_R, double *d_pose_t, uint8_t *d_bad, const void **d_kps,
+                                const uint8_t **d_desc, int32_t *d_n, int32_t *d_slots, int stride, const uint8_t *d_valid,
+                                int cap_points, const int32_t *d_frame_mp, int n2, const double *d_frame_pose_R,
+                                const double *d_frame_pose_t, const void *frame_kps, const uint8_t *frame_desc, int32_t *d_result,
+                                void *stream);
+int orbm_register_new_points_device(orbm_t *h, const int32_t *d_n_points, int32_t *d_n_registered, int K, int kf_id, int cap_points,
+                                    int32_t *d_ref_kf, int32_t *d_first_kf, int32_t *d_found, int32_t *d_visible, int32_t *d_recent,
+                                    int cap_recent, int32_t *d_n_recent, int32_t *d_result, void *stream);
+int orbm_cull_map_points_device(orbm_t *h, int32_t *d_recent, int32_t *d_n_recent, int cap_recent, int cur_kf_id,
+                                const int32_t *d_first_kf, const int32_t *d_found, const int32_t *d_visible, uint8_t *d_valid,
+                                int cap_points, int n_kf, const int32_t *d_n, const uint8_t *d_bad, int32_t *d_slots, int stride,
+                                const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs, int32_t *d_code,
+                                int32_t *d_result, void *stream);
 
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,

@@ -157,6 +157,9 @@ def _mlib():
                                             i32, vp, vp, vp, vp, vp, vp, vp]),
             "orbm_track_counters_device": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
             "orbm_num_tracked_points_device": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]),
+            "orbm_insert_keyframe_device": (i32, [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
+            "orbm_register_new_points_device": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+            "orbm_cull_map_points_device": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]),
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
@@ -609,6 +612,44 @@ class ORBMatcher:
         _lib.check(self._L.orbm_num_tracked_points_device(
             self._hd._h, p("ref"), min_obs, n_kf, p("n"), p("bad"), p("slots"), stride, cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs,
             p("count"), _lib.stream_arg(stream)))
+
+    # -- a tracked frame becomes a key frame; new map points are registered; MapPointCulling (LocalMapping.cpp:93-105, :117-144, :243-248) --
+    def InsertKeyFrameDevice(self, d, K, stride, cap_points, n2, frame_kps, frame_desc, stream=None):
+        """orbm_insert_keyframe_device (Tracking.cpp:578-588, LocalMapping.cpp:93-105): d = dict of torch device tensors -- in / out, the
+        key-frame table's arrays: pose_R f64 [cap_kf,9], pose_t f64 [cap_kf,3], bad u8 [cap_kf], kps, desc i64 [cap_kf] (device addresses),
+        n i32 [cap_kf], slots i32 [cap_kf,stride]; in: valid u8 [cap], frame_mp i32 [n2] (table rows, -1 = none), frame_pose_R f64 [9],
+        frame_pose_t f64 [3]; out: result i32 [8] ([0] slots holding a point, [2] cleared: bad row, [3] out of range, [4] second slots of
+        a row, [5] n2 beyond stride).  K: the new key frame's slot; frame_kps / frame_desc: the frame's record tensors or their device
+        addresses.  Enqueues on `stream`; nothing is copied or synchronised.  There is no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        addr = lambda x: x if isinstance(x, int) else x.data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_insert_keyframe_device(
+            self._hd._h, K, int(d["n"].shape[0]), p("pose_R"), p("pose_t"), p("bad"), p("kps"), p("desc"), p("n"), p("slots"), stride, p("valid"),
+            cap_points, p("frame_mp"), n2, p("frame_pose_R"), p("frame_pose_t"), addr(frame_kps), addr(frame_desc), p("result"),
+            _lib.stream_arg(stream)))
+
+    def RegisterNewPointsDevice(self, d, K, kf_id, cap_points, stream=None):
+        """orbm_register_new_points_device (LocalMapping.cpp:243-248, MapPoint.cpp:18, :24-25): d = dict of torch device tensors -- in:
+        n_points i32 [1] (as TriangulateMatchesDevice leaves it); in / out: n_registered i32 [1] (rows below it are finished), recent i32
+        [cap_recent] with n_recent i32 [1] (recent_map_points as table rows); out, for the rows n_registered .. n_points - 1: ref_kf = K,
+        first_kf = kf_id, found = visible = 1 (all i32 [cap]); result i32 [8] ([0] rows registered, [1] refusal: nothing written).
+        Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_register_new_points_device(
+            self._hd._h, p("n_points"), p("n_registered"), K, kf_id, cap_points, p("ref_kf"), p("first_kf"), p("found"), p("visible"), p("recent"),
+            int(d["recent"].shape[0]), p("n_recent"), p("result"), _lib.stream_arg(stream)))
+
+    def CullMapPointsDevice(self, d, cur_kf_id, n_kf, stride, cap_points, n_obs, stream=None):
+        """orbm_cull_map_points_device (LocalMapping.cpp:117-144): d = dict of torch device tensors -- in / out: recent i32 [cap_recent]
+        with n_recent i32 [1] (the kept entries, compacted in order), valid u8 [cap], slots i32 [n_kf,stride]; in: first_kf, found,
+        visible i32 [cap], n i32 [n_kf], bad u8 [n_kf], obs_off, obs_kf, obs_kp (the CSR BuildObservationsDevice left from these slots);
+        out: code i32 [cap_recent] (0 kept, 1 already bad, 2 found ratio, 3 few observations, 4 aged out, -1 not a row), result i32 [8]
+        ([0] kept, [1] refusal: a row twice in the list, nothing written).  Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_cull_map_points_device(
+            self._hd._h, p("recent"), p("n_recent"), int(d["recent"].shape[0]), cur_kf_id, p("first_kf"), p("found"), p("visible"), p("valid"),
+            cap_points, n_kf, p("n"), p("bad"), p("slots"), stride, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs, p("code"), p("result"),
+            _lib.stream_arg(stream)))
 
     # -- Optimize::localBundleAdjustment on the slot arrays: the problem assembled, the result applied (Optimize.cpp:766-889, :914-950) --
     def LocalBaProblemDevice(self, kf, d, stride, cap_points, n_obs, n_local, first_kf, cap_poses, cap_local_points, cap_edges, stream=None):
