@@ -67,7 +67,10 @@ int orbba_linearize(const orbba_problem *p, orbba_result *r, int device);
 /* g2o::OptimizationAlgorithmLevenberg's knobs; a zero field takes g2o's default */
 typedef struct orbba_lm_options {
     int32_t max_iterations;     /* optimizer.optimize(n) */
-    int32_t max_trials;         /* _maxTrialsAfterFailure, default 10 */
+    int32_t max_trials;         /* _maxTrialsAfterFailure, default 10.  g2o counts the ACCEPTED trial too and ends the whole
+                                 * optimisation when an iteration has used max_trials trials, whatever the last one's verdict:
+                                 * an acceptance on the last allowed trial is kept and still terminates, and max_trials = 1
+                                 * therefore means one iteration (one trial, kept or not) */
     double tau;                 /* computeLambdaInit: lambda0 = tau * max |H_jj|, default 1e-5 */
     double good_step_lower;     /* default 1/3 */
     double good_step_upper;     /* default 2/3 */

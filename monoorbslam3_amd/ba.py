@@ -107,14 +107,17 @@ def _lm_finish(out, res):
 
 
 def optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2,
-             huber_delta=HUBER_MONO, iterations=5, edge_active=None, device=-1):
-    """optimizer.optimize(iterations) of Optimize::localBundleAdjustment's graph (Optimize.cpp:811-893) on the GPU."""
+             huber_delta=HUBER_MONO, iterations=5, edge_active=None, device=-1, max_trials=0, tau=0.0, good_step_lower=0.0,
+             good_step_upper=0.0, user_lambda_init=0.0):
+    """optimizer.optimize(iterations) of Optimize::localBundleAdjustment's graph (Optimize.cpp:811-893) on the GPU.  max_trials, tau,
+    good_step_lower / _upper and user_lambda_init are orbba_lm_options' fields of those names: 0 takes g2o's default."""
     L = _lib.lib()
     fn = L.orbba_optimize
     fn.restype = C.c_int
     fn.argtypes = [C.POINTER(_Problem), C.POINTER(_LmOptions), C.POINTER(_LmResult), C.c_int]
     prob, keep = _problem(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2, huber_delta)
-    opt = _LmOptions(max_iterations=iterations)
+    opt = _LmOptions(max_iterations=iterations, max_trials=max_trials, tau=tau, good_step_lower=good_step_lower,
+                     good_step_upper=good_step_upper, user_lambda_init=user_lambda_init)
     if edge_active is not None:
         act = np.ascontiguousarray(edge_active, dtype=np.uint8)
         opt.edge_active = act.ctypes.data

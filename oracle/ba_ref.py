@@ -140,12 +140,14 @@ def robust_chi2(chi2, huber_delta, active=None):
 
 
 def lm_optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2, huber_delta,
-                iterations, edge_active=None, tau=1e-5, max_trials=10, lower=1.0 / 3.0, upper=2.0 / 3.0):
+                iterations, edge_active=None, tau=1e-5, max_trials=10, lower=1.0 / 3.0, upper=2.0 / 3.0, user_lambda_init=0.0):
     """g2o's OptimizationAlgorithmLevenberg + BlockSolver_6_3 with marginalised points, restated densely
     (g2o 20201223: optimization_algorithm_levenberg.cpp solve(), block_solver.hpp buildSystem/solve, sparse_optimizer.cpp
     optimize()) for the graph Optimize::localBundleAdjustment builds (reference modules/Backend/Optimize.cpp:811-911).
-    Inactive edges (setLevel(1), Optimize.cpp:900-902) take no part.  Returns dict(pose_R, pose_t, points, chi2,
-    iterations, lam, chi2_initial, chi2_final, trials)."""
+    Inactive edges (setLevel(1), Optimize.cpp:900-902) take no part.  user_lambda_init > 0 replaces computeLambdaInit's
+    tau * max |H_jj| (g2o's _userLambdaInit).  Returns dict(pose_R, pose_t, points, chi2, iterations, lam, chi2_initial,
+    chi2_final, trials, trace); trace holds one tuple per trial: (iteration, trial within it, lambda used, current chi2, the
+    trial's chi2, computeScale() + 1e-3, rho, Cholesky succeeded)."""
     R = np.array(pose_R, np.float64).reshape(-1, 3, 3)
     t = np.array(pose_t, np.float64).reshape(-1, 3)
     P = np.array(points, np.float64).reshape(-1, 3)
@@ -170,7 +172,7 @@ def lm_optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, 
         e, _ = residual(cam, Rc[ep], tc[ep], Pc[el], np.asarray(edge_z, np.float64).reshape(-1, 2))
         return np.asarray(edge_inv_sigma2, np.float64) * (e * e).sum(1)
 
-    lam, ni, its, trials_total = 0.0, 2.0, 0, 0
+    lam, ni, its, trials_total, trace = 0.0, 2.0, 0, 0, []
     chi2_initial = robust_chi2(chi(R, t, P), huber_delta, act)
     for it in range(iterations):
         current = robust_chi2(chi(R, t, P), huber_delta, act)
@@ -178,7 +180,7 @@ def lm_optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, 
         Hpp, bp, Hll, bl = lin["H_pp"][free], lin["b_p"][free], lin["H_ll"], lin["b_l"]
         if it == 0:  # computeLambdaInit: tau * max |diagonal| over the free vertices
             diag = np.concatenate([np.abs(np.einsum("nii->ni", Hpp)).ravel(), np.abs(np.einsum("nii->ni", Hll)).ravel()])
-            lam, ni = tau * float(diag.max()), 2.0
+            lam, ni = user_lambda_init if user_lambda_init > 0 else tau * float(diag.max()), 2.0
         rho, qmax = 0.0, 0
         while True:
             Rb, tb, Pb = R.copy(), t.copy(), P.copy()  # push()
@@ -203,6 +205,7 @@ def lm_optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, 
             scale = float((xp * (lam * xp + bp.reshape(-1))).sum() + (xl * (lam * xl + bl)).sum()) + 1e-3
             rho = (current - temp) / scale
             trials_total += 1
+            trace.append((it, qmax, lam, current, temp, scale, rho, ok2))
             if rho > 0 and np.isfinite(temp):
                 alpha = min(1.0 - (2 * rho - 1) ** 3, upper)
                 lam *= max(lower, alpha)
@@ -222,7 +225,8 @@ def lm_optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, 
             break  # Terminate: optimize() leaves its loop
     final = chi(R, t, P)
     return {"pose_R": R, "pose_t": t, "points": P, "chi2": final, "iterations": its, "lam": lam,
-            "chi2_initial": chi2_initial, "chi2_final": robust_chi2(final, huber_delta, act), "trials": trials_total}
+            "chi2_initial": chi2_initial, "chi2_final": robust_chi2(final, huber_delta, act), "trials": trials_total,
+            "trace": trace}
 
 
 def local_bundle_adjustment(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2,

@@ -75,17 +75,17 @@ def test_gpu_matches_oracle(n_poses, n_points):
 
 # ---------------------------------------------------------------------------------------------------------------
 # Levenberg-Marquardt with marginalised points (g2o's OptimizationAlgorithmLevenberg + BlockSolver_6_3)
-def _perturbed(n_poses, n_points, seed, outliers=0):
+def _perturbed(n_poses, n_points, seed, outliers=0, rot=0.01, trans=0.05, pts=0.05, camera="pinhole"):
     from oracle import ba_ref
-    pr = synth.make_ba_problem(n_poses, n_points, seed=seed, n_fixed=min(2, n_poses - 1))
+    pr = synth.make_ba_problem(n_poses, n_points, seed=seed, n_fixed=min(2, n_poses - 1), camera=camera)
     rng = np.random.RandomState(seed)
     R = np.array(pr["pose_R"]).reshape(-1, 3, 3).copy()
     t = np.array(pr["pose_t"]).reshape(-1, 3).copy()
     P = np.array(pr["points"]).reshape(-1, 3).copy()
     for i in np.flatnonzero(~np.asarray(pr["pose_fixed"], bool)):
-        dR, dt = ba_ref.se3_exp(np.concatenate([rng.normal(0, 0.01, 3), rng.normal(0, 0.05, 3)]))
+        dR, dt = ba_ref.se3_exp(np.concatenate([rng.normal(0, rot, 3), rng.normal(0, trans, 3)]))
         R[i], t[i] = dR @ R[i], dR @ t[i] + dt
-    P += rng.normal(0, 0.05, P.shape)
+    P += rng.normal(0, pts, P.shape)
     z = np.array(pr["edge_z"]).reshape(-1, 2).copy()
     if outliers:
         bad = rng.choice(len(z), outliers, replace=False)

@@ -188,6 +188,36 @@ def test_the_device_lm_equals_the_host_entry_point_bit_for_bit(model, chol):
     _bits_equal(out, info, host)
 
 
+@pytest.mark.parametrize("chol", ["lds", "global"])
+def test_the_device_lm_equals_the_host_entry_point_where_trials_are_rejected(chol):
+    """the scene of tests/test_ba_lm_paths.py whose first round rejects a trial (admitted there on the CPU, and the host form held against
+    the oracle): push(), pop() and the lambda schedule on the index arrays the device built -- bit for bit again, counts and lambda included"""
+    import torch
+    from monoorbslam3_amd import ba
+    from test_ba_lm_paths import _local_ba_args, _local_ba_oracle
+    dev = torch.device("cuda", 0)
+    cam, R, t, fixed, P, ep, el, z, w = _local_ba_args()
+    prob = dict(pose_R=np.ascontiguousarray(R, np.float64).reshape(-1, 9), pose_t=np.ascontiguousarray(t, np.float64),
+                pose_fixed=np.ascontiguousarray(fixed, np.uint8), ba_points=np.ascontiguousarray(P, np.float64),
+                edge_pose=np.ascontiguousarray(ep, np.int32), edge_point=np.ascontiguousarray(el, np.int32),
+                edge_z=np.ascontiguousarray(z, np.float64), edge_inv_sigma2=np.ascontiguousarray(w, np.float64))
+    n_poses, n_points, n_edges = len(prob["pose_t"]), len(prob["ba_points"]), len(prob["edge_pose"])
+    ba.set_variant("chol", chol)
+    try:
+        host = _host_ba(cam, prob)
+        out = _lm_outputs(torch, dev, n_poses, n_points, n_edges)
+        info = ba.local_bundle_adjustment_device(cam, dict({k: _up(torch, dev, v) for k, v in prob.items()}, **out), n_poses, n_points, n_edges)
+        torch.cuda.synchronize()
+    finally:
+        ba.set_variant("chol", "lds")
+    ref = _local_ba_oracle()
+    print("iterations %d trials %d lambda %.6g chi2 %.6g -> %.6g outliers %d" % (info["iterations"], info["trials"], info["lam"],
+                                                                               info["chi2_initial"], info["chi2_final"], int(host["outlier"].sum())))
+    assert info["trials"] > info["iterations"] and info["trials"] == ref["first_round"]["trials"] + ref["trials"]
+    assert np.array_equal(host["outlier"], ref["outlier"])
+    _bits_equal(out, info, host)
+
+
 def test_the_device_lm_refuses_what_the_host_form_refuses():
     """a key frame observing a point twice, and an edge index out of range: ORBX_E_ARG, found on the device, outputs as passed"""
     import torch
