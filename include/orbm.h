@@ -941,7 +941,7 @@ int orbm_connected_keyframes_device(orbm_t *h, const orbm_covis_graph *graph, in
  * order) and the slots in order, a tile of 1024 at a time, numbered by a block scan.  The two small calls clear their result and run a
  * thread per slot / per query.
  * As compiled for gfx950 -- VGPRs / scratch / static LDS: k_local_map 60 / 0 / 33412 B, k_track_counters 14 / 0 / 0 B, k_num_tracked
- * 20 / 0 / 0 B: no scratch memory, at most 64 VGPRs. */
+ * 16 / 0 / 0 B: no scratch memory, at most 64 VGPRs. */
 int orbm_local_map_device(orbm_t *h, int32_t *d_frame_mp, int n2, const uint8_t *d_valid, int cap_points, const int32_t *d_obs_off,
                           const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs, int n_kf, const int32_t *d_n, const uint8_t *d_bad,
                           const int32_t *d_slots, int stride, const orbm_covis_graph *graph, const int32_t *recent, int n_recent,

@@ -3,7 +3,7 @@
 //                            MapPoint::addObservation / KeyFrame::addMapPoint and MapPoint::replace (MapPoint.cpp:233-264)
 //
 // THE SLOT ARRAYS ARE THE TRUTH: an observation is a slot, so an add is one store and a replace rewrites the slots that name the loser.
-// ONE launch of ONE workgroup of 1024 threads (the shape of k_cull: a few thousand hits are latency), in phases between barriers:
+// ONE launch of ONE workgroup of 1024 threads (the shape of orbm_map.h: a few thousand hits are latency), in phases between barriers:
 //   1  the mask (one bit per table row, dynamic LDS) = the rows named by a slot of K; head[] (one int per slot of K) = empty
 //   2  every entry classified on the arrays as passed -- none / dropped / gated / live -- into d_work: the hit slot of a live entry,
 //      a negative class otherwise; head[s] = the first live entry of slot s (atomicMin: the value does not depend on the order)
@@ -32,6 +32,7 @@
 #include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
+#include "orbm_map.h"
 
 namespace {
 
@@ -39,7 +40,7 @@ typedef unsigned long long u64;
 
 constexpr int FU_T = 1024;              // the one workgroup
 constexpr int FU_WAVES = FU_T / 64;
-constexpr int FU_EMPTY = 0x7fffffff;    // head[s]: no live entry hits slot s
+constexpr int FU_EMPTY = MAP_NONE;      // head[s]: no live entry hits slot s
 constexpr int FU_MAX_NQ = 1 << 30;      // a link in d_work is -8 - (the next entry)
 constexpr int FU_LINK = -8;
 
@@ -47,42 +48,28 @@ constexpr int FU_LINK = -8;
 enum { F_NONE = 0, F_DROPPED = 1, F_GATED = 2, F_ADDED = 3, F_BAD_OCCUPANT = 4, F_LIST_REPLACED = 5, F_OCCUPANT_REPLACED = 6, F_UNDONE = 7 };
 enum { R_MATCHES = 0, R_REFUSED = 1, R_ADDED = 2, R_LIST_REPLACED = 3, R_OCCUPANT_REPLACED = 4, R_CLEARED = 5, R_GATED = 6, R_DROPPED = 7 };
 
-struct FuseView {
-    int n_kf, stride, cap_points, n_obs, K;
-    const int32_t *kf_n;
-    const uint8_t *bad;
-    int32_t *slots;
-    const int32_t *obs_off, *obs_kf, *obs_kp;
+// the map (orbm_map.h), the chains' key frame and the entries
+struct FuseView : MapView {
+    int K;
     const int32_t *rows;
     int32_t *work;
 };
 
-// the slots and d_work are read while other waves write other elements of them: relaxed atomics, plain loads and stores in the ISA
-__device__ __forceinline__ int ld(const int32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-__device__ __forceinline__ void st(int32_t *p, int x) { __atomic_store_n(p, x, __ATOMIC_RELAXED); }
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
 __device__ __forceinline__ int fuse_row(const FuseView &v, int j) { return v.rows ? v.rows[j] : j; }
 
-// row p's CSR list; offsets that do not describe a list inside [0, n_obs] give an empty one
+// row p's CSR list, the same for every lane of the wave
 __device__ __forceinline__ void fuse_list(const FuseView &v, int p, int &b, int &e)
 {
-    b = uniform(v.obs_off[p]), e = uniform(v.obs_off[p + 1]);
-    if (b < 0 || e < b || e > v.n_obs) b = e = 0;
-}
-
-__device__ __forceinline__ bool fuse_usable(const FuseView &v, int k, int i)
-{
-    return k >= 0 && k < v.n_kf && i >= 0 && i < min(v.kf_n[k], v.stride);
+    map_list(v, p, b, e);
+    b = uniform(b), e = uniform(e);
 }
 
 // CSR entry j as an observation: usable, its key frame not bad, not the chain's own slot (K, own) -> what its slot holds NOW
 __device__ __forceinline__ bool fuse_entry(const FuseView &v, int j, int own, int &k, int &held)
 {
-    k = v.obs_kf[j];
-    const int i = v.obs_kp[j];
-    if (!fuse_usable(v, k, i) || v.bad[k] || (k == v.K && i == own)) return false;
-    held = ld(&v.slots[(size_t)k * v.stride + i]);
+    int i;
+    if (!map_entry(v, j, k, i) || v.bad[k] || (k == v.K && i == own)) return false;
+    held = ld(map_slot(v, k, i));
     return true;
 }
 
@@ -108,34 +95,32 @@ __device__ __forceinline__ bool chain_next(const FuseView &v, ChainRows &c, int 
     return true;
 }
 
-__global__ __launch_bounds__(FU_T) void k_fuse_apply(const int32_t *__restrict__ best_idx, const int32_t *__restrict__ rows, int nq, int n_kf, int K,
-                                                     const int32_t *__restrict__ kf_n, const uint8_t *__restrict__ bad, int32_t *slots, int stride,
-                                                     uint8_t *valid, int cap_points, const int32_t *__restrict__ obs_off,
-                                                     const int32_t *__restrict__ obs_kf, const int32_t *__restrict__ obs_kp, int n_obs, int32_t *found,
-                                                     const int32_t *visible, int32_t *work, int32_t *code, int32_t *refresh_sel, int32_t *result)
+__global__ __launch_bounds__(FU_T) void k_fuse_apply(const FuseView v, const int32_t *__restrict__ best_idx, int nq, int32_t *found, const int32_t *visible,
+                                                     int32_t *code, int32_t *refresh_sel, int32_t *result)
 {
     extern __shared__ uint32_t s_dyn[];                            // the mask, (cap_points + 31) / 32 words, then head[stride]
     __shared__ uint32_t s_multi[ORBM_MEDIAN_MAX_STRIDE / 32];      // bit s: more than one live entry hits slot s
     __shared__ int s_count[8];
     __shared__ int s_refused[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
-    const int n_words = (cap_points + 31) >> 5;
+    const int K = v.K, stride = v.stride, cap_points = v.cap_points, n_obs = v.n_obs;
+    uint8_t *const valid = v.valid;
+    int32_t *const work = v.work;
     uint32_t *s_mask = s_dyn;
-    int *s_head = (int *)(s_dyn + n_words);
-    const FuseView v = {n_kf, stride, cap_points, n_obs, K, kf_n, bad, slots, obs_off, obs_kf, obs_kp, rows, work};
-    const int nK = min(max(kf_n[K], 0), stride);
-    const bool bad_K = bad[K] != 0;
-    int32_t *mine = slots + (size_t)K * stride;
+    int *s_head = (int *)(s_dyn + ((cap_points + 31) >> 5));
+    const int nK = map_slots(v, K);
+    const bool bad_K = v.bad[K] != 0;
+    int32_t *mine = map_slot(v, K, 0);
     // ---- 1: the rows named by a slot of K
-    for (int w = tid; w < n_words; w += FU_T) s_mask[w] = 0;
+    bits_zero<FU_T>(s_mask, cap_points);
     for (int i = tid; i < stride; i += FU_T) s_head[i] = FU_EMPTY;
-    for (int i = tid; i < ORBM_MEDIAN_MAX_STRIDE / 32; i += FU_T) s_multi[i] = 0;
+    bits_zero<FU_T>(s_multi, ORBM_MEDIAN_MAX_STRIDE);
     if (tid < 8) s_count[tid] = 0;
     if (tid < 2) s_refused[tid] = 0;
     __syncthreads();
     for (int i = tid; i < nK; i += FU_T) {
         const int o = mine[i];
-        if (o >= 0 && o < cap_points) atomicOr(&s_mask[o >> 5], 1u << (o & 31));
+        if (o >= 0 && o < cap_points) bit_set(s_mask, o);
     }
     __syncthreads();
     // ---- 2: every entry on the arrays as passed (ORBMatcher.cpp:534, :574)
@@ -145,33 +130,30 @@ __global__ __launch_bounds__(FU_T) void k_fuse_apply(const int32_t *__restrict__
         int w;
         if (s < 0) w = -1 - F_NONE;
         else if (s >= nK || p < 0 || p >= cap_points) w = -1 - F_DROPPED, ++dropped;
-        else if (!valid[p] || (s_mask[p >> 5] >> (p & 31) & 1)) w = -1 - F_GATED, ++gated;
+        else if (!valid[p] || bit_test(s_mask, p)) w = -1 - F_GATED, ++gated;
         else w = s, atomicMin(&s_head[s], j);
         work[j] = w;
     }
     __syncthreads();
     // ---- 3: the premises, before anything is written
-    for (int w = tid; w < n_words; w += FU_T) s_mask[w] = 0;
+    bits_zero<FU_T>(s_mask, cap_points);
     __syncthreads();
     for (int j = tid; j < nq; j += FU_T) {
         if (work[j] < 0) continue;
-        const int p = fuse_row(v, j);
-        const uint32_t bit = 1u << (p & 31);
-        if (atomicOr(&s_mask[p >> 5], bit) & bit) s_refused[0] = 1;          // a row in two live entries
+        if (!bit_set(s_mask, fuse_row(v, j))) s_refused[0] = 1;              // a row in two live entries
     }
     for (int i = tid; i < nK; i += FU_T) {
         if (s_head[i] == FU_EMPTY) continue;
         const int o = mine[i];
         if (o < 0 || o >= cap_points || !valid[o]) continue;
-        const uint32_t bit = 1u << (o & 31);
-        if (atomicOr(&s_mask[o >> 5], bit) & bit) s_refused[1] = 1;          // the occupant of two hit slots
+        if (!bit_set(s_mask, o)) s_refused[1] = 1;                           // the occupant of two hit slots
     }
     __syncthreads();
     for (int i = tid; i < nK; i += FU_T) {
         if (s_head[i] != FU_EMPTY) continue;
         const int o = mine[i];
         if (o < 0 || o >= cap_points || !valid[o]) continue;
-        if (s_mask[o >> 5] >> (o & 31) & 1) s_refused[1] = 1;                // the occupant of a hit slot in a second slot of K
+        if (bit_test(s_mask, o)) s_refused[1] = 1;                           // the occupant of a hit slot in a second slot of K
     }
     __syncthreads();
     const int refused = s_refused[0] ? 1 : s_refused[1] ? 2 : 0;
@@ -183,9 +165,9 @@ __global__ __launch_bounds__(FU_T) void k_fuse_apply(const int32_t *__restrict__
     for (int j = tid; j < nq; j += FU_T) {
         const int w = work[j];
         if (w < 0) code[j] = -1 - w, refresh_sel[j] = -1;
-        else if (s_head[w] != j) atomicOr(&s_multi[w >> 5], 1u << (w & 31));
+        else if (s_head[w] != j) bit_set(s_multi, w);
     }
-    for (int j = tid; j < n_obs; j += FU_T) dropped += !fuse_usable(v, obs_kf[j], obs_kp[j]);
+    for (int j = tid; j < n_obs; j += FU_T) dropped += !map_usable(v, v.obs_kf[j], v.obs_kp[j]);
     __syncthreads();
     // ---- 5: a wave per chain
     int added = 0, bad_occupant = 0, list_replaced = 0, occupant_replaced = 0, undone = 0;   // the same in every lane of the wave
@@ -193,7 +175,7 @@ __global__ __launch_bounds__(FU_T) void k_fuse_apply(const int32_t *__restrict__
     for (int s = wave; s < nK; s += FU_WAVES) {
         const int head = s_head[s];
         if (head == FU_EMPTY) continue;
-        const bool multi = s_multi[s >> 5] >> (s & 31) & 1;
+        const bool multi = bit_test(s_multi, s);
         int cur = uniform(mine[s]);                                // what slot s holds, kept in registers from here on
         const bool cur_row = cur >= 0 && cur < cap_points;
         bool cur_valid = cur_row && valid[cur] != 0;
@@ -257,7 +239,7 @@ __global__ __launch_bounds__(FU_T) void k_fuse_apply(const int32_t *__restrict__
                                 }
                             }
                             if (cand) {
-                                st(&slots[(size_t)k * stride + obs_kp[t]], seen ? -1 : W);
+                                st(map_slot(v, k, v.obs_kp[t]), seen ? -1 : W);
                                 cleared += seen;
                             }
                             __threadfence_block();                 // the wave's own stores, before its lanes read the slots again
@@ -293,11 +275,9 @@ __global__ __launch_bounds__(FU_T) void k_fuse_apply(const int32_t *__restrict__
             j = next;
         }
     }
-    dropped = wave_sum(dropped), gated = wave_sum(gated), cleared = wave_sum(cleared);
-    if (lane == 0) {
-        if (dropped + undone) atomicAdd(&s_count[R_DROPPED], dropped + undone);
-        if (gated) atomicAdd(&s_count[R_GATED], gated);
-        if (cleared) atomicAdd(&s_count[R_CLEARED], cleared);
+    block_add(s_count, {R_DROPPED, R_GATED, R_CLEARED}, {dropped, gated, cleared});
+    if (lane == 0) {                                               // the chains' counts are the same in every lane of the wave
+        if (undone) atomicAdd(&s_count[R_DROPPED], undone);
         if (added) atomicAdd(&s_count[R_ADDED], added);
         if (list_replaced) atomicAdd(&s_count[R_LIST_REPLACED], list_replaced);
         if (occupant_replaced) atomicAdd(&s_count[R_OCCUPANT_REPLACED], occupant_replaced);
@@ -317,12 +297,11 @@ extern "C" int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, cons
                                       void *stream)
 {
     if (!d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (nq < 0 || n_kf < 0 || stride < 0 || cap_points < 0 || n_obs < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
+    if (nq < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
+    if (!d_n || !d_bad) return orbx_set_error(ORBX_E_ARG, "null key-frame array");   // wanted even when n_kf == 0
+    MapView m;
+    if (int rc = orbm_map_view(&m, n_kf, d_n, d_bad, d_slots, stride, d_valid, cap_points, d_obs_off, d_obs_kf, d_obs_kp, n_obs)) return rc;
     if (kf_target < 0 || kf_target >= n_kf) return orbx_set_error(ORBX_E_ARG, "kf_target is not a key frame of the table");
-    if (!d_n || !d_bad) return orbx_set_error(ORBX_E_ARG, "null key-frame array");
-    if (stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
-    if (cap_points > 0 && (!d_valid || !d_obs_off)) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
-    if (n_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
     if ((d_found == nullptr) != (d_visible == nullptr)) return orbx_set_error(ORBX_E_ARG, "d_found and d_visible go together");
     if (nq > 0 && (!d_best_idx || !d_work || !d_code || !d_refresh_sel)) return orbx_set_error(ORBX_E_ARG, "null entry array");
     if (nq > FU_MAX_NQ) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 2^30 entries in one call");
@@ -332,8 +311,8 @@ extern "C" int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, cons
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
     const size_t lds_bytes = ((size_t)((cap_points + 31) >> 5) + (size_t)stride) * 4;   // <= 64 KB + 32 KB
     if (lds_bytes + 2048 > 64 * 1024) ORB_TRY(orbx_lds_opt_in((const void *)k_fuse_apply, lds_bytes));   // with the static 1064 B: past 64 KB
-    hipLaunchKernelGGL(k_fuse_apply, dim3(1), dim3(FU_T), lds_bytes, s, d_best_idx, d_rows, nq, n_kf, kf_target, d_n, d_bad, d_slots, stride,
-                       d_valid, cap_points, d_obs_off, d_obs_kf, d_obs_kp, n_obs, d_found, d_visible, d_work, d_code, d_refresh_sel, d_result);
+    hipLaunchKernelGGL(k_fuse_apply, dim3(1), dim3(FU_T), lds_bytes, s, FuseView{m, kf_target, d_rows, d_work}, d_best_idx, nq,
+                       d_found, d_visible, d_code, d_refresh_sel, d_result);
     ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }

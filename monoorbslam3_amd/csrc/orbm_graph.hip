@@ -11,8 +11,8 @@
 // small); they mark in d_work the rows whose list has to be rebuilt, and k_graph_resort, launched behind them with one workgroup per
 // key frame, rebuilds the marked ones: a workgroup reads its own mark and its own row and writes its own list, nothing another writes.
 // k_graph_fuse_targets is one workgroup: wave 0 walks the lists (the marks decide who is appended, so the walk is sequential; the
-// lanes share a second-neighbour list) while the other waves clear d_work; then first occurrences by atomicMin and the slots in order,
-// a tile of 1024 at a time, with a block scan numbering the rows -- the technique of k_lba_problem.
+// lanes share a second-neighbour list) while the other waves clear d_work; then the targets' rows in first-occurrence order
+// (map_first_rows, orbm_map.h).
 // Integer only.  No scratch memory, no handle scratch, no allocation, no host wait.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -22,6 +22,7 @@
 #include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
+#include "orbm_map.h"
 
 namespace {
 
@@ -29,24 +30,7 @@ typedef unsigned long long u64;
 
 constexpr int GR_T = 1024;                       // the workgroup of every kernel but k_graph_connected
 constexpr int GR_WAVES = GR_T / 64;
-constexpr int GR_MAX_RECENT = 32;
-constexpr int GR_NONE = 0x7fffffff;
 constexpr u64 GR_NO_KEY = ~0ull;                 // sorts behind every entry
-constexpr int GR_KEY_SHIFT = 13;                 // a slot position (< ORBM_MEDIAN_MAX_STRIDE = 8192) below the target's position (< 4096)
-
-struct GraphView {
-    int cap, n_kf;
-    int32_t *weight, *ord_kf, *ord_n, *parent;
-};
-
-struct RecentList {
-    int32_t kf[GR_MAX_RECENT];
-};
-
-// values other threads of the workgroup (or lanes of the wave) write in the same phase: relaxed atomics, plain loads and stores in the ISA
-__device__ __forceinline__ int ld(const int32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-__device__ __forceinline__ void st(int32_t *p, int x) { __atomic_store_n(p, x, __ATOMIC_RELAXED); }
-__device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
 // descending weight on the full int32, ascending slot: ascending in this key
 __device__ __forceinline__ u64 graph_key(int w, int slot) { return (u64)(~((uint32_t)w ^ 0x80000000u)) << 32 | (uint32_t)slot; }
@@ -75,9 +59,6 @@ __device__ __forceinline__ void sort_keys(u64 *s, int n_pow2)
     __syncthreads();
 }
 
-// a list length read from device memory, kept inside the row
-__device__ __forceinline__ int list_length(const GraphView &g, int k) { return min(max(g.ord_n[k], 0), g.n_kf); }
-
 // updateBestCovisibles of key frame j: list j = the non-zero entries of row j in list order.  Every thread of the workgroup.
 __device__ __forceinline__ void rebuild_list(const GraphView &g, int j, u64 *s_key, int *s_n)
 {
@@ -90,8 +71,7 @@ __device__ __forceinline__ void rebuild_list(const GraphView &g, int j, u64 *s_k
         s_key[i] = w ? graph_key(w, i) : GR_NO_KEY;
         mine += w != 0;
     }
-    mine = wave_sum(mine);
-    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(s_n, mine);
+    block_add(s_n, 0, mine);
     sort_keys(s_key, n2);
     const int n = *s_n;
     for (int i = threadIdx.x; i < n; i += GR_T) g.ord_kf[(size_t)j * g.cap + i] = (int32_t)(uint32_t)s_key[i];
@@ -124,7 +104,7 @@ __global__ __launch_bounds__(GR_T) void k_graph_update(GraphView g, const uint8_
     __shared__ int s_max, s_least;
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < 8) s_count[tid] = 0;
-    if (tid == 0) s_max = 0, s_least = GR_NONE;
+    if (tid == 0) s_max = 0, s_least = MAP_NONE;
     __syncthreads();
     int on_bad = 0, junk = 0, over = 0, top = 0;
     for (int j = tid; j < g.n_kf; j += GR_T) {
@@ -134,13 +114,9 @@ __global__ __launch_bounds__(GR_T) void k_graph_update(GraphView g, const uint8_
         over += c >= th;
         top = max(top, c);
     }
-    on_bad = wave_sum(on_bad), junk = wave_sum(junk), over = wave_sum(over), top = wave_max(top);
-    if (lane == 0) {
-        if (on_bad) atomicAdd(&s_count[U_BAD], on_bad);
-        if (junk) atomicAdd(&s_count[U_JUNK], junk);
-        if (over) atomicAdd(&s_count[U_N], over);
-        if (top) atomicMax(&s_max, top);
-    }
+    top = wave_max(top);
+    block_add(s_count, {U_BAD, U_JUNK, U_N}, {on_bad, junk, over});
+    if (lane == 0 && top) atomicMax(&s_max, top);
     __syncthreads();
     const int c_max = s_max, n_over = s_count[U_N];
     if (c_max == 0) {                                              // kfCounter.empty(): nothing is written (KeyFrame.cpp:244)
@@ -171,8 +147,7 @@ __global__ __launch_bounds__(GR_T) void k_graph_update(GraphView g, const uint8_
         }
         s_key[j] = key;
     }
-    rebuilt = wave_sum(rebuilt);
-    if (lane == 0 && rebuilt) atomicAdd(&s_count[U_REBUILT], rebuilt);
+    block_add(s_count, U_REBUILT, rebuilt);
     sort_keys(s_key, n2);
     for (int i = tid; i < n_s; i += GR_T) g.ord_kf[(size_t)K * g.cap + i] = (int32_t)(uint32_t)s_key[i];
     if (tid == 0) {
@@ -190,7 +165,7 @@ __global__ __launch_bounds__(GR_T) void k_graph_erase(GraphView g, RecentList re
                                                       int32_t *result)
 {
     __shared__ int s_count[8];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     if (tid < 8) s_count[tid] = 0;
     for (int j = tid; j < g.n_kf; j += GR_T) work[j] = 0;
     int connections = 0, children = 0;
@@ -218,45 +193,12 @@ __global__ __launch_bounds__(GR_T) void k_graph_erase(GraphView g, RecentList re
     __syncthreads();
     int lists = 0;
     for (int j = tid; j < g.n_kf; j += GR_T) lists += work[j] != 0;
-    connections = wave_sum(connections), children = wave_sum(children), lists = wave_sum(lists);
-    if (lane == 0) {
-        if (connections) atomicAdd(&s_count[E_CONNECTIONS], connections);
-        if (children) atomicAdd(&s_count[E_CHILDREN], children);
-        if (lists) atomicAdd(&s_count[E_LISTS], lists);
-    }
+    block_add(s_count, {E_CONNECTIONS, E_CHILDREN, E_LISTS}, {connections, children, lists});
     __syncthreads();
     if (tid < 8) result[tid] = s_count[tid];
 }
 
 enum { T_TARGETS = 0, T_ROWS = 1, T_REFUSED = 2, T_BAD = 3, T_INVALID = 4, T_DROPPED = 5, T_DUPLICATES = 6 };
-
-// exclusive scan of v over the workgroup in thread order and the total; s_wave is GR_WAVES ints; two barriers
-__device__ __forceinline__ int block_scan(int v, int *s_wave, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int inc = wave_scan(v);
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = inc - v;
-    total = 0;
-#pragma unroll 1
-    for (int w = 0; w < GR_WAVES; ++w) {
-        const int x = s_wave[w];
-        if (w < wave) before += x;
-        total += x;
-    }
-    __syncthreads();
-    return before;
-}
-
-// The target walk runs in ONE wave whose lanes write marks that other lanes of the same wave read in the next step.  The LDS pipe
-// serves a wave's accesses in issue order, so the hardware needs nothing; this keeps the COMPILER from moving a later lane's read
-// above an earlier lane's write (a fence at wavefront scope and a wave barrier emit no instruction).
-__device__ __forceinline__ void wave_order()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __global__ __launch_bounds__(GR_T) void k_graph_fuse_targets(GraphView g, const int32_t *__restrict__ kf_n, const uint8_t *__restrict__ bad,
                                                              const int32_t *__restrict__ slots, int stride, const uint8_t *__restrict__ valid,
@@ -268,34 +210,32 @@ __global__ __launch_bounds__(GR_T) void k_graph_fuse_targets(GraphView g, const 
     __shared__ int s_wave[GR_WAVES];
     __shared__ int s_count[8];
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
+    const MapReadView map = {g.n_kf, stride, cap_points, 0, kf_n, bad, slots, valid, nullptr, nullptr, nullptr};   // the arguments keep their __restrict__
     if (tid < 8) s_count[tid] = 0;
-    for (int i = tid; i < ORBM_GRAPH_MAX_KF / 32; i += GR_T) s_mark[i] = 0;
+    bits_zero<GR_T>(s_mark, ORBM_GRAPH_MAX_KF);
     __syncthreads();
     if (wave == 0) {
         // ---- the targets (LocalMapping.cpp:263-277): sequential, because the marks decide; the lanes share a second-neighbour list
         int nt = 0, n_bad = 0, dropped = 0;                        // the same in every lane
-        const int nf = min(max(n_first, 0), list_length(g, cur));
+        const int nf = min(max(n_first, 0), graph_list_length(g, cur));
         for (int i = 0; i < nf; ++i) {
             const int a = uniform(g.ord_kf[(size_t)cur * g.cap + i]);
             if (a < 0 || a >= g.n_kf) {
                 ++dropped;
                 continue;
             }
-            if (__hip_atomic_load(&s_mark[a >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (a & 31) & 1) continue;
-            if (lane == 0) {
-                atomicOr(&s_mark[a >> 5], 1u << (a & 31));
-                s_targets[nt] = a;
-            }
+            if (bit_test(s_mark, a)) continue;
+            if (lane == 0) bit_set(s_mark, a), s_targets[nt] = a;
             wave_order();                                          // lane 0's mark, before any lane tests the second neighbours
-            ++nt, n_bad += bad[a] != 0;
-            const int ns = min(max(n_second, 0), list_length(g, a));
+            ++nt, n_bad += map.bad[a] != 0;
+            const int ns = min(max(n_second, 0), graph_list_length(g, a));
             for (int t0 = 0; t0 < ns; t0 += 64) {
                 const int t = t0 + lane;
                 const int b = t < ns ? g.ord_kf[(size_t)a * g.cap + t] : -1;
                 const bool out = t < ns && (b < 0 || b >= g.n_kf);
                 dropped += __popcll(__ballot(out));
                 bool cand = t < ns && !out && b != cur;
-                if (cand) cand = !(__hip_atomic_load(&s_mark[b >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> (b & 31) & 1);
+                if (cand) cand = !bit_test(s_mark, b);
                 bool twice = false;                                // an earlier entry of this tile names the same key frame
                 for (u64 m = __ballot(cand); m; m &= m - 1) {
                     const int l = __builtin_ctzll(m);
@@ -303,58 +243,22 @@ __global__ __launch_bounds__(GR_T) void k_graph_fuse_targets(GraphView g, const 
                 }
                 cand = cand && !twice;
                 const u64 keep = __ballot(cand);
-                if (cand) {
-                    atomicOr(&s_mark[b >> 5], 1u << (b & 31));
-                    s_targets[nt + __popcll(keep & ((1ull << lane) - 1))] = b;
-                }
+                if (cand) bit_set(s_mark, b), s_targets[nt + __popcll(keep & ((1ull << lane) - 1))] = b;
                 wave_order();                                      // the tile's marks, before the next tile's and the next entry's tests
-                nt +=__popcll(keep), n_bad += __popcll(__ballot(cand && bad[b] != 0));
+                nt +=__popcll(keep), n_bad += __popcll(__ballot(cand && map.bad[b] != 0));
             }
         }
         if (lane == 0) s_count[T_TARGETS] = nt, s_count[T_BAD] = n_bad, s_count[T_DROPPED] = dropped;
     } else {
-        for (int p = tid - 64; p < cap_points; p += GR_T - 64) work[p] = GR_NONE;
+        for (int p = tid - 64; p < map.cap_points; p += GR_T - 64) work[p] = MAP_NONE;
     }
     __syncthreads();
     const int nt = s_count[T_TARGETS];
     for (int t = tid; t < min(nt, cap_targets); t += GR_T) targets[t] = s_targets[t];
-    // ---- the rows (:287-300): a row's first occurrence in (target, slot) order is the least key naming it, whatever the atomics' order
+    // ---- the rows (:287-300), "kf has bad map-point" (:292) counted as invalid
     int invalid = 0, duplicates = 0;
-    for (int t = 0; t < nt; ++t) {
-        const int k = s_targets[t], nk = min(max(kf_n[k], 0), stride);
-        for (int i = tid; i < nk; i += GR_T) {
-            const int p = slots[(size_t)k * stride + i];
-            if (p < 0 || p >= cap_points) continue;
-            if (!valid[p]) ++invalid;                              // "kf has bad map-point" (:292)
-            else atomicMin(&work[p], t << GR_KEY_SHIFT | i);
-        }
-    }
-    __syncthreads();
-    int n_rows = 0;
-    for (int t = 0; t < nt; ++t) {
-        const int k = s_targets[t], nk = min(max(kf_n[k], 0), stride);
-        for (int i0 = 0; i0 < nk; i0 += GR_T) {
-            const int i = i0 + tid;
-            int p = -1;
-            bool first = false;
-            if (i < nk) {
-                p = slots[(size_t)k * stride + i];
-                if (p >= 0 && p < cap_points && valid[p]) {
-                    first = ld(&work[p]) == (t << GR_KEY_SHIFT | i);
-                    duplicates += !first;
-                }
-            }
-            int tile;
-            const int at = n_rows + block_scan(first, s_wave, tile);
-            if (first && at < cap_rows) rows[at] = p;
-            n_rows += tile;
-        }
-    }
-    invalid = wave_sum(invalid), duplicates = wave_sum(duplicates);
-    if (lane == 0) {
-        if (invalid) atomicAdd(&s_count[T_INVALID], invalid);
-        if (duplicates) atomicAdd(&s_count[T_DUPLICATES], duplicates);
-    }
+    const int n_rows = map_first_rows<GR_T>(s_targets, nt, map, work, rows, cap_rows, s_wave, invalid, duplicates);
+    block_add(s_count, {T_INVALID, T_DUPLICATES}, {invalid, duplicates});
     __syncthreads();
     if (tid == 0) s_count[T_ROWS] = n_rows, s_count[T_REFUSED] = (nt > cap_targets ? 1 : 0) | (n_rows > cap_rows ? 2 : 0);
     __syncthreads();
@@ -364,39 +268,25 @@ __global__ __launch_bounds__(GR_T) void k_graph_fuse_targets(GraphView g, const 
 __global__ __launch_bounds__(256) void k_graph_connected(GraphView g, int kf, int include_self, int max_n, int32_t *out, int n_out, int32_t *n_written)
 {
     const int self = include_self != 0;
-    const int n = min(self + min(max(max_n, 0), list_length(g, kf)), n_out);
+    const int n = min(self + min(max(max_n, 0), graph_list_length(g, kf)), n_out);
     for (int i = threadIdx.x; i < n_out; i += 256) out[i] = i >= n ? -1 : i < self ? kf : g.ord_kf[(size_t)kf * g.cap + i - self];
     if (threadIdx.x == 0) *n_written = n;
 }
-
-// the checks every entry point starts with: ORBX_E_ARG here, the limit behind the other arguments' checks
-int graph_check(const orbm_covis_graph *graph, int n_kf)
-{
-    if (!graph) return orbx_set_error(ORBX_E_ARG, "null graph");
-    if (!graph->d_weight || !graph->d_ord_kf || !graph->d_ord_n || !graph->d_parent) return orbx_set_error(ORBX_E_ARG, "null graph array");
-    if (graph->cap_kf < 0 || n_kf < 0 || n_kf > graph->cap_kf) return orbx_set_error(ORBX_E_ARG, "n_kf must lie in [0, cap_kf]");
-    return ORBX_OK;
-}
-int graph_check_limit(const orbm_covis_graph *graph)
-{
-    return graph->cap_kf > ORBM_GRAPH_MAX_KF ? orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBM_GRAPH_MAX_KF (4096) key frames in the graph") : ORBX_OK;
-}
-GraphView graph_view(const orbm_covis_graph *graph, int n_kf) { return {graph->cap_kf, n_kf, graph->d_weight, graph->d_ord_kf, graph->d_ord_n, graph->d_parent}; }
 
 } // namespace
 
 extern "C" int orbm_update_connections_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, const uint8_t *d_bad, const int32_t *d_covis,
                                               int kf_self, int first_kf, int connect_th, int32_t *d_work, int32_t *d_result, void *stream)
 {
-    if (int rc = graph_check(graph, n_kf)) return rc;
+    GraphView g;
+    if (int rc = orbm_graph_view(&g, graph, n_kf)) return rc;
     if (!d_bad || !d_covis || !d_work || !d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
     if (kf_self < 0 || kf_self >= n_kf) return orbx_set_error(ORBX_E_ARG, "kf_self is not a key frame of the graph");
     if (first_kf < -1 || first_kf >= n_kf) return orbx_set_error(ORBX_E_ARG, "first_kf must be -1 or a key frame of the graph");
     if (connect_th < 1) return orbx_set_error(ORBX_E_ARG, "connect_th must be positive");
-    if (int rc = graph_check_limit(graph)) return rc;
+    if (int rc = orbm_graph_check_limit(graph)) return rc;
     hipStream_t s;
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
-    const GraphView g = graph_view(graph, n_kf);
     hipLaunchKernelGGL(k_graph_update, dim3(1), dim3(GR_T), 0, s, g, d_bad, d_covis, kf_self, first_kf, connect_th, d_work, d_result);
     ORB_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_graph_resort, dim3(n_kf), dim3(GR_T), 0, s, g, (const int32_t *)d_work);
@@ -407,18 +297,18 @@ extern "C" int orbm_update_connections_device(orbm_t *h, const orbm_covis_graph 
 extern "C" int orbm_erase_connections_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, const int32_t *recent, int n_recent,
                                              const int32_t *d_code, int32_t *d_work, int32_t *d_result, void *stream)
 {
-    if (int rc = graph_check(graph, n_kf)) return rc;
-    if (n_recent < 0 || n_recent > GR_MAX_RECENT) return orbx_set_error(ORBX_E_ARG, "n_recent must lie in [0, 32]");
+    GraphView g;
+    if (int rc = orbm_graph_view(&g, graph, n_kf)) return rc;
+    if (n_recent < 0 || n_recent > MAP_MAX_RECENT) return orbx_set_error(ORBX_E_ARG, "n_recent must lie in [0, 32]");
     if (!d_result || (n_kf > 0 && !d_work) || (n_recent > 0 && !recent)) return orbx_set_error(ORBX_E_ARG, "null argument");
     RecentList list = {};
     for (int i = 0; i < n_recent; ++i) {
         if (recent[i] < 0 || recent[i] >= n_kf) return orbx_set_error(ORBX_E_ARG, "an entry of recent is not a key frame of the graph");
         list.kf[i] = recent[i];
     }
-    if (int rc = graph_check_limit(graph)) return rc;
+    if (int rc = orbm_graph_check_limit(graph)) return rc;
     hipStream_t s;
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
-    const GraphView g = graph_view(graph, n_kf);
     hipLaunchKernelGGL(k_graph_erase, dim3(1), dim3(GR_T), 0, s, g, list, n_recent, d_code, d_work, d_result);
     ORB_TRY(hipGetLastError());
     if (n_kf > 0) {
@@ -433,19 +323,20 @@ extern "C" int orbm_fuse_targets_device(orbm_t *h, const orbm_covis_graph *graph
                                         int n_second, int cap_targets, int cap_rows, int32_t *d_work, int32_t *d_targets, int32_t *d_rows,
                                         int32_t *d_result, void *stream)
 {
-    if (int rc = graph_check(graph, n_kf)) return rc;
-    if (stride < 0 || cap_points < 0 || n_first < 0 || n_second < 0 || cap_targets < 0 || cap_rows < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
+    GraphView g;
+    if (int rc = orbm_graph_view(&g, graph, n_kf)) return rc;
+    if (int rc = orbm_check_slots(n_kf, d_n, d_bad, d_slots, stride, d_valid, cap_points)) return rc;
+    if (n_first < 0 || n_second < 0 || cap_targets < 0 || cap_rows < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
     if (cur < 0 || cur >= n_kf) return orbx_set_error(ORBX_E_ARG, "cur is not a key frame of the graph");
-    if (!d_n || !d_bad || !d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
-    if (cap_points > 0 && (!d_valid || !d_work)) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
+    if (!d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (cap_points > 0 && !d_work) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
     if ((cap_targets > 0 && !d_targets) || (cap_rows > 0 && !d_rows)) return orbx_set_error(ORBX_E_ARG, "null output array");
-    if (int rc = graph_check_limit(graph)) return rc;
+    if (int rc = orbm_graph_check_limit(graph)) return rc;
     if (int rc = orbm_check_stride(stride)) return rc;
     if (int rc = orbm_check_points(cap_points)) return rc;
     hipStream_t s;
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
-    hipLaunchKernelGGL(k_graph_fuse_targets, dim3(1), dim3(GR_T), 0, s, graph_view(graph, n_kf), d_n, d_bad, d_slots, stride, d_valid, cap_points, cur,
+    hipLaunchKernelGGL(k_graph_fuse_targets, dim3(1), dim3(GR_T), 0, s, g, d_n, d_bad, d_slots, stride, d_valid, cap_points, cur,
                        n_first, n_second, cap_targets, cap_rows, d_work, d_targets, d_rows, d_result);
     ORB_TRY(hipGetLastError());
     return ORBX_OK;
@@ -454,14 +345,15 @@ extern "C" int orbm_fuse_targets_device(orbm_t *h, const orbm_covis_graph *graph
 extern "C" int orbm_connected_keyframes_device(orbm_t *h, const orbm_covis_graph *graph, int n_kf, int kf, int include_self, int max_n,
                                                int32_t *d_out, int n_out, int32_t *d_n_out, void *stream)
 {
-    if (int rc = graph_check(graph, n_kf)) return rc;
+    GraphView g;
+    if (int rc = orbm_graph_view(&g, graph, n_kf)) return rc;
     if (kf < 0 || kf >= n_kf) return orbx_set_error(ORBX_E_ARG, "kf is not a key frame of the graph");
     if (max_n < 0 || n_out < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
     if (!d_n_out || (n_out > 0 && !d_out)) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (int rc = graph_check_limit(graph)) return rc;
+    if (int rc = orbm_graph_check_limit(graph)) return rc;
     hipStream_t s;
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
-    hipLaunchKernelGGL(k_graph_connected, dim3(1), dim3(256), 0, s, graph_view(graph, n_kf), kf, include_self, max_n, d_out, n_out, d_n_out);
+    hipLaunchKernelGGL(k_graph_connected, dim3(1), dim3(256), 0, s, g, kf, include_self, max_n, d_out, n_out, d_n_out);
     ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }

@@ -37,39 +37,6 @@ enum { P_KEPT = 0, P_REFUSED = 1, P_BAD = 2, P_RATIO = 3, P_FEW = 4, P_AGED = 5,
 
 __device__ __forceinline__ int clamp_to(int x, int hi) { return min(max(x, 0), hi); }
 
-// sets bit p of the mask; true for the one thread that found it clear
-__device__ __forceinline__ bool claim(uint32_t *s_mask, int p)
-{
-    const uint32_t bit = 1u << (p & 31);
-    return !(atomicOr(&s_mask[p >> 5], bit) & bit);
-}
-
-// exclusive scan of v over the workgroup in thread order and the total; s_wave is KF_WAVES ints; two barriers
-__device__ __forceinline__ int block_scan(int v, int *s_wave, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int inc = wave_scan(v);
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int before = inc - v;
-    total = 0;
-#pragma unroll 1
-    for (int w = 0; w < KF_WAVES; ++w) {
-        const int x = s_wave[w];
-        if (w < wave) before += x;
-        total += x;
-    }
-    __syncthreads();
-    return before;
-}
-
-// the sum of a per-thread count over the workgroup into s_count[slot]; the caller's barrier follows
-__device__ __forceinline__ void block_add(int *s_count, int slot, int v)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_count[slot], v);
-}
-
 // row K of the key-frame table, the arrays of orbm_kf_table as their owner holds them
 struct KfRow {
     int K;
@@ -105,7 +72,7 @@ __global__ __launch_bounds__(KF_T) void k_kf_insert(KfRow row, int32_t *slots, i
         if (p != -1) {
             if (p < 0 || p >= cap_points) ++range;
             else if (!valid[p]) ++invalid;                         // eraseMapPoint (:98)
-            else slot = p, ++held, distinct += claim(s_mask, p);   // addObservation (:100) refuses a second slot; map_points keeps it
+            else slot = p, ++held, distinct += bit_set(s_mask, p);   // addObservation (:100) refuses a second slot; map_points keeps it
         }
         mine[i] = slot;
     }
@@ -138,7 +105,9 @@ __global__ __launch_bounds__(KF_T) void k_kf_register(const int32_t *n_points, i
     if (tid < 8) result[tid] = tid == G_ROWS ? b - a : tid == G_FROM ? a : tid == G_TO ? b : tid == G_RECENT ? r + (b - a) : 0;
 }
 
-// the map as orbm_build_observations_device takes and leaves it; slots and valid are written here
+// The map as orbm_build_observations_device takes and leaves it; slots and valid are written here.  This file keeps its own view, CSR
+// rules and argument checks instead of those of orbm_map.h: with the shared ones the chain insert -> build -> cull -> register measured
+// 4 % slower (tools/keyframe_latency.py, profiles/map_view_refactor_latency.txt) although k_kf_cull_points compiled to equivalent code
 struct MapView {
     int n_kf, stride, cap_points, n_obs;
     const int32_t *kf_n, *obs_off, *obs_kf, *obs_kp;
@@ -193,7 +162,7 @@ __global__ __launch_bounds__(KF_T) void k_kf_cull_points(MapView m, int32_t *rec
     int twice = 0;
     for (int j = tid; j < n; j += KF_T) {
         const int p = recent[j];
-        if (p >= 0 && p < m.cap_points) twice |= !claim(s_mask, p);
+        if (p >= 0 && p < m.cap_points) twice |= !bit_set(s_mask, p);
     }
     if (__syncthreads_or(twice)) {
         if (tid < 8) result[tid] = tid == P_REFUSED;
@@ -224,7 +193,7 @@ __global__ __launch_bounds__(KF_T) void k_kf_cull_points(MapView m, int32_t *rec
             code[j] = c;
         }
         int tile;
-        const int at = kept + block_scan(c == 0, s_wave, tile);    // its first barrier stands between the tile's reads and its writes
+        const int at = kept + block_scan<KF_WAVES>(c == 0, s_wave, tile);   // its first barrier stands between the tile's reads and its writes
         if (c == 0) recent[at] = p;
         kept += tile;
     }

@@ -5,9 +5,9 @@
 //   orbm_local_ba_apply_device     what it does with the optimiser's result (Optimize.cpp:914-950): the outlier observations erased with
 //                                  the cascade of MapPoint::eraseObservation -> setBad (MapPoint.cpp:190-226), poses and positions written
 //
-// THE SLOT ARRAYS ARE THE TRUTH, the CSR only tells where the slots naming a row are (the rules of orbm_observations.hip).
+// THE SLOT ARRAYS ARE THE TRUTH, the CSR only tells where the slots naming a row are (the rules and the view of orbm_map.h).
 //
-// The assembly.  ONE launch of ONE workgroup of 1024 threads (the shape of k_cull / k_fuse_apply: 20 key frames x 2000 slots x short lists
+// The assembly.  ONE launch of ONE workgroup of 1024 threads (the shape of orbm_map.h: 20 key frames x 2000 slots x short lists
 // is latency), in phases between barriers; d_work [cap_points + n_kf] is the caller's work array:
 //   0  work_row[p] = none, work_kf[k] = none; the CSR's unusable entries counted
 //   1  the local list: work_kf[k] = the FIRST position naming k (atomicMin: the value does not depend on the order); an entry is kept if it
@@ -37,15 +37,13 @@
 #include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
+#include "orbm_map.h"
 
 namespace {
 
 constexpr int LB_T = 1024;              // the one workgroup
 constexpr int LB_WAVES = LB_T / 64;
-constexpr int LB_KEY_SHIFT = 13;        // first-occurrence key = local index << 13 | slot
-constexpr int LB_NONE = 0x7fffffff;     // work_row / work_kf: not named / neither local nor fixed
-constexpr int LB_FIXED = 0x7ffffffe;    // work_kf: a key frame of an edge that is not local, before it has a number
-static_assert(ORBM_MEDIAN_MAX_STRIDE == 1 << LB_KEY_SHIFT, "the first-occurrence key packs the slot index into 13 bits");
+constexpr int LB_FIXED = MAP_NONE - 1;  // work_kf: a key frame of an edge that is not local, before it has a number (MAP_NONE: neither)
 static_assert(ORBM_LOCAL_BA_MAX_LOCAL == LB_T, "a thread per entry of d_local");
 
 // d_result of the assembly (int32 x 16) and of the apply (int32 x 8)
@@ -53,36 +51,10 @@ enum { P_POSES = 0, P_POINTS = 1, P_EDGES = 2, P_LOCAL = 3, P_FIXED = 4, P_REFUS
        P_NO_EDGE = 8, P_SECOND = 9, P_CSR_DROPPED = 10 };
 enum { A_ERASED = 0, A_POINTS_BAD = 1, A_CLEARED = 2, A_MOVED = 3, A_ROWS = 4, A_CSR_DROPPED = 5, A_MAP_DROPPED = 6, A_POSES = 7 };
 
-// the slots and work_kf are read while other threads write other elements of them (or the same value): relaxed atomics
-__device__ __forceinline__ int ld(const int32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-__device__ __forceinline__ void st(int32_t *p, int x) { __atomic_store_n(p, x, __ATOMIC_RELAXED); }
-
-// the key frames' slots and the observation index, as both kernels read them
-struct MapView {
-    int n_kf, stride, cap_points, n_obs;
-    const int32_t *kf_n;
-    const uint8_t *bad;
-    int32_t *slots;
-    const int32_t *obs_off, *obs_kf, *obs_kp;
-};
-
-__device__ __forceinline__ int map_slots(const MapView &v, int k) { return min(max(v.kf_n[k], 0), v.stride); }
-
-// both indices usable?  (the refresh's distrust; the slot index also has to exist in d_slots)
-__device__ __forceinline__ bool map_usable(const MapView &v, int k, int i) { return k >= 0 && k < v.n_kf && i >= 0 && i < min(v.kf_n[k], v.stride); }
-
-// CSR entry j as an observation of row p: usable, its slot names the row NOW, its key frame is not bad
-__device__ __forceinline__ bool map_live(const MapView &v, int j, int p, int &k, int &i)
+// CSR entry j as an observation of row p; the slot is read with ld, as k_lba_apply's other threads clear slots in the same phase
+template <bool W> __device__ __forceinline__ bool live_entry(const MapViewOf<W> &m, int j, int p, int &k, int &i)
 {
-    k = v.obs_kf[j], i = v.obs_kp[j];
-    return map_usable(v, k, i) && ld(&v.slots[(size_t)k * v.stride + i]) == p && v.bad[k] == 0;
-}
-
-// row p's CSR list; offsets that do not describe a list inside [0, n_obs] give an empty one
-__device__ __forceinline__ void map_list(const MapView &v, int p, int &b, int &e)
-{
-    b = v.obs_off[p], e = v.obs_off[p + 1];
-    if (b < 0 || e < b || e > v.n_obs) b = e = 0;
+    return map_entry(m, j, k, i) && map_live<true>(m, k, i, p);
 }
 
 // exclusive scan of (a, b) over the workgroup in thread order and both totals; s_wave is 2 x LB_WAVES ints
@@ -103,10 +75,9 @@ __device__ __forceinline__ void block_scan2(int a, int b, int (*s_wave)[LB_WAVES
 }
 
 struct ProblemArgs {
-    MapView m;
+    MapReadView m;
     const double *pose_R, *pose_t;       // the key-frame table's
     const void *const *kps;
-    const uint8_t *valid;
     const float *points;
     const int32_t *local;
     int n_local, first_kf, cap_poses, cap_local_points, cap_edges;
@@ -129,9 +100,9 @@ __device__ __forceinline__ int problem_edges(const ProblemArgs &a, int32_t *work
     map_list(a.m, p, b, e);
     for (int j = b; j < e; ++j) {
         int k, i, k2, i2;
-        if (!map_live(a.m, j, p, k, i)) continue;
+        if (!live_entry(a.m, j, p, k, i)) continue;
         bool again = false;                                        // a key frame twice: the LM refuses such a problem
-        for (int j2 = b; j2 < j && !again; ++j2) again = map_live(a.m, j2, p, k2, i2) && k2 == k;
+        for (int j2 = b; j2 < j && !again; ++j2) again = live_entry(a.m, j2, p, k2, i2) && k2 == k;
         if (again) {
             second += !WRITE;
             continue;
@@ -139,7 +110,7 @@ __device__ __forceinline__ int problem_edges(const ProblemArgs &a, int32_t *work
         if (WRITE) {
             const int x = e0 + n;
             if (x < a.cap_edges) a.o_edge_kf[x] = k, a.o_edge_kp[x] = i, a.o_edge_point[x] = idx;
-        } else if (ld(&work_kf[k]) == LB_NONE) {
+        } else if (ld(&work_kf[k]) == MAP_NONE) {
             st(&work_kf[k], LB_FIXED);                             // whoever stores, the value is the same
         }
         ++n;
@@ -153,11 +124,11 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
     __shared__ int s_wave[2][LB_WAVES];
     __shared__ int s_count[16];
     const int tid = threadIdx.x;
-    const MapView &m = a.m;
+    const MapReadView &m = a.m;
     int32_t *work_row = a.work, *work_kf = a.work + m.cap_points;
     // ---- 0
-    for (int p = tid; p < m.cap_points; p += LB_T) work_row[p] = LB_NONE;
-    for (int k = tid; k < m.n_kf; k += LB_T) work_kf[k] = LB_NONE;
+    for (int p = tid; p < m.cap_points; p += LB_T) work_row[p] = MAP_NONE;
+    for (int k = tid; k < m.n_kf; k += LB_T) work_kf[k] = MAP_NONE;
     if (tid < 16) s_count[tid] = 0;
     int csr_dropped = 0, no_edge = 0, second = 0;                   // per thread, summed at the end
     for (int j = tid; j < m.n_obs; j += LB_T) csr_dropped += !map_usable(m, m.obs_kf[j], m.obs_kp[j]);
@@ -175,7 +146,7 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
     block_scan2(keep, local_dropped, s_wave, li, unused, n_loc, n_local_dropped);
     int skipped_bad, n_local_bad, has_first, n_has_first;
     block_scan2(is_bad, keep && mine == a.first_kf, s_wave, skipped_bad, has_first, n_local_bad, n_has_first);
-    if (first) work_kf[mine] = keep ? li : LB_NONE;                // every read of the first positions lies before the scans' barriers
+    if (first) work_kf[mine] = keep ? li : MAP_NONE;               // every read of the first positions lies before the scans' barriers
     if (keep) s_local[li] = mine;
     __syncthreads();
     // ---- 2: the rows named by a slot of a local key frame, and where first (:783-792)
@@ -184,7 +155,7 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
         const int l = t / m.stride, i = t - l * m.stride, k = s_local[l];
         if (i >= map_slots(m, k)) continue;
         const int p = m.slots[(size_t)k * m.stride + i];
-        if (p >= 0 && p < m.cap_points && a.valid[p]) atomicMin(&work_row[p], l << LB_KEY_SHIFT | i);
+        if (p >= 0 && p < m.cap_points && m.valid[p]) atomicMin(&work_row[p], l << MAP_KEY_SHIFT | i);
     }
     __syncthreads();
     // ---- 3: points and edges in the order of first occurrence (:860-889)
@@ -197,7 +168,7 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
             const int l = t / m.stride, i = t - l * m.stride, k = s_local[l];
             if (i < map_slots(m, k)) {
                 p = m.slots[(size_t)k * m.stride + i];
-                is_first = p >= 0 && p < m.cap_points && a.valid[p] && work_row[p] == (l << LB_KEY_SHIFT | i);
+                is_first = p >= 0 && p < m.cap_points && m.valid[p] && work_row[p] == (l << MAP_KEY_SHIFT | i);
             }
         }
         if (is_first) cnt = problem_edges<false>(a, work_kf, p, 0, 0, second);
@@ -235,12 +206,7 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
     const int n_poses = n_loc + n_fixed;
     const int refused = (n_poses > a.cap_poses) | (n_points > a.cap_local_points) << 1 | (n_edges > a.cap_edges) << 2 |
                         (n_loc - (n_has_first != 0) < 1) << 3 | (n_edges < 1) << 4;
-    csr_dropped = wave_sum(csr_dropped), no_edge = wave_sum(no_edge), second = wave_sum(second);
-    if ((tid & 63) == 0) {
-        if (csr_dropped) atomicAdd(&s_count[P_CSR_DROPPED], csr_dropped);
-        if (no_edge) atomicAdd(&s_count[P_NO_EDGE], no_edge);
-        if (second) atomicAdd(&s_count[P_SECOND], second);
-    }
+    block_add(s_count, {P_CSR_DROPPED, P_NO_EDGE, P_SECOND}, {csr_dropped, no_edge, second});
     __syncthreads();                                               // work_kf and o_pose_kf as well
     if (tid == 0) {
         s_count[P_POSES] = n_poses, s_count[P_POINTS] = n_points, s_count[P_EDGES] = n_edges, s_count[P_LOCAL] = n_loc;
@@ -271,7 +237,6 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
 
 struct ApplyArgs {
     MapView m;
-    uint8_t *valid;
     int32_t *ref_kf;
     float *points;
     double *pose_R, *pose_t;             // the key-frame table's, in / out
@@ -298,7 +263,7 @@ __global__ __launch_bounds__(LB_T) void k_lba_apply(const ApplyArgs a)
             ++count[A_MAP_DROPPED];
             continue;
         }
-        bool good = a.valid[p] != 0;
+        bool good = m.valid[p] != 0;
         int lb, le;
         map_list(m, p, lb, le);
         // ---- the outlier observations of this point, in edge order (Optimize.cpp:927-934)
@@ -309,22 +274,21 @@ __global__ __launch_bounds__(LB_T) void k_lba_apply(const ApplyArgs a)
                 ++count[A_MAP_DROPPED];
                 continue;
             }
-            int32_t *slot = &m.slots[(size_t)k * m.stride + i];
-            if (ld(slot) != p || m.bad[k]) continue;               // no observation there any more
-            st(slot, -1);                                          // KeyFrame::eraseMapPoint
+            if (!map_live<true>(m, k, i, p)) continue;                  // no observation there any more
+            st(map_slot(m, k, i), -1);                             // KeyFrame::eraseMapPoint
             ++count[A_ERASED];
             int left = 0, first = -1, k2, i2;                      // MapPoint::eraseObservation (MapPoint.cpp:190-208)
             for (int j = lb; j < le; ++j) {
-                if (!map_live(m, j, p, k2, i2) || k2 == k) continue;
+                if (!live_entry(m, j, p, k2, i2) || k2 == k) continue;
                 if (left++ == 0) first = k2;
             }
             if (a.ref_kf[p] == k && left > 0) a.ref_kf[p] = first, ++count[A_MOVED];   // observations.begin()
             if (left > 2) continue;
-            a.valid[p] = 0, good = false;                          // MapPoint::setBad (:202, :210-226)
+            m.valid[p] = 0, good = false;                          // MapPoint::setBad (:202, :210-226)
             ++count[A_POINTS_BAD];
             for (int j = lb; j < le; ++j) {
-                if (!map_live(m, j, p, k2, i2) || k2 == k) continue;
-                st(&m.slots[(size_t)k2 * m.stride + i2], -1);
+                if (!live_entry(m, j, p, k2, i2) || k2 == k) continue;
+                st(map_slot(m, k2, i2), -1);
                 ++count[A_CLEARED];
             }
         }
@@ -344,23 +308,9 @@ __global__ __launch_bounds__(LB_T) void k_lba_apply(const ApplyArgs a)
         ++count[A_POSES];
     }
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const int v = wave_sum(count[c]);
-        if ((tid & 63) == 0 && v) atomicAdd(&s_count[c], v);
-    }
+    for (int c = 0; c < 8; ++c) block_add(s_count, c, count[c]);
     __syncthreads();
     if (tid < 8) a.result[tid] = s_count[tid];
-}
-
-int check_map(int n_kf, int stride, int cap_points, int n_obs, const int32_t *d_n, const uint8_t *d_bad, const int32_t *d_slots,
-              const uint8_t *d_valid, const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp)
-{
-    if (n_kf < 0 || stride < 0 || cap_points < 0 || n_obs < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
-    if (n_kf > 0 && (!d_n || !d_bad)) return orbx_set_error(ORBX_E_ARG, "null key-frame array");
-    if (n_kf > 0 && stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
-    if (cap_points > 0 && (!d_valid || !d_obs_off)) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
-    if (n_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
-    return ORBX_OK;
 }
 
 } // namespace
@@ -375,7 +325,8 @@ extern "C" int orbm_local_ba_problem_device(orbm_t *h, const orbm_kf_table *kf, 
                                             int32_t *d_result, void *stream)
 {
     if (!kf || !d_result || !d_local) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (int rc = check_map(kf->n_kf, stride, cap_points, n_obs, kf->d_n, kf->d_bad, d_slots, d_valid, d_obs_off, d_obs_kf, d_obs_kp)) return rc;
+    ProblemArgs a = {};
+    if (int rc = orbm_map_view(&a.m, kf->n_kf, kf->d_n, kf->d_bad, d_slots, stride, d_valid, cap_points, d_obs_off, d_obs_kf, d_obs_kp, n_obs)) return rc;
     if (n_local < 1 || cap_poses < 1 || cap_local_points < 1 || cap_edges < 1) return orbx_set_error(ORBX_E_ARG, "n_local and the capacities must be positive");
     if (kf->n_kf > 0 && (!kf->d_pose_R || !kf->d_pose_t || !kf->d_kps)) return orbx_set_error(ORBX_E_ARG, "null key-frame array");
     if (cap_points > 0 && !d_points) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
@@ -389,9 +340,7 @@ extern "C" int orbm_local_ba_problem_device(orbm_t *h, const orbm_kf_table *kf, 
     if (int rc = orbm_check_points(cap_points)) return rc;
     hipStream_t s;
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
-    ProblemArgs a = {};
-    a.m = {kf->n_kf, stride, cap_points, n_obs, kf->d_n, kf->d_bad, const_cast<int32_t *>(d_slots), d_obs_off, d_obs_kf, d_obs_kp};
-    a.pose_R = kf->d_pose_R, a.pose_t = kf->d_pose_t, a.kps = kf->d_kps, a.valid = d_valid, a.points = d_points, a.local = d_local;
+    a.pose_R = kf->d_pose_R, a.pose_t = kf->d_pose_t, a.kps = kf->d_kps, a.points = d_points, a.local = d_local;
     a.n_local = n_local, a.first_kf = first_kf, a.cap_poses = cap_poses, a.cap_local_points = cap_local_points, a.cap_edges = cap_edges;
     a.work = d_work, a.o_pose_R = d_pose_R, a.o_pose_t = d_pose_t, a.o_pose_fixed = d_pose_fixed, a.o_points = d_ba_points;
     a.o_edge_pose = d_edge_pose, a.o_edge_point = d_edge_point, a.o_edge_z = d_edge_z, a.o_edge_inv_sigma2 = d_edge_inv_sigma2;
@@ -411,7 +360,8 @@ extern "C" int orbm_local_ba_apply_device(orbm_t *h, int n_kf, const int32_t *d_
                                           const double *d_est_points, const uint8_t *d_outlier, int32_t *d_result, void *stream)
 {
     if (!d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (int rc = check_map(n_kf, stride, cap_points, n_obs, d_n, d_bad, d_slots, d_valid, d_obs_off, d_obs_kf, d_obs_kp)) return rc;
+    ApplyArgs a = {};
+    if (int rc = orbm_map_view(&a.m, n_kf, d_n, d_bad, d_slots, stride, d_valid, cap_points, d_obs_off, d_obs_kf, d_obs_kp, n_obs)) return rc;
     if (n_local < 0 || n_points < 0 || n_edges < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
     if (cap_points > 0 && (!d_ref_kf || !d_points)) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
     if (n_local > 0 && (!d_kf_pose_R || !d_kf_pose_t || !d_pose_kf || !d_est_pose_R || !d_est_pose_t)) return orbx_set_error(ORBX_E_ARG, "null pose array");
@@ -421,9 +371,7 @@ extern "C" int orbm_local_ba_apply_device(orbm_t *h, int n_kf, const int32_t *d_
     if (int rc = orbm_check_points(cap_points)) return rc;
     hipStream_t s;
     if (int rc = orbm_begin_device(h, stream, &s)) return rc;
-    ApplyArgs a = {};
-    a.m = {n_kf, stride, cap_points, n_obs, d_n, d_bad, d_slots, d_obs_off, d_obs_kf, d_obs_kp};
-    a.valid = d_valid, a.ref_kf = d_ref_kf, a.points = d_points, a.pose_R = d_kf_pose_R, a.pose_t = d_kf_pose_t;
+    a.ref_kf = d_ref_kf, a.points = d_points, a.pose_R = d_kf_pose_R, a.pose_t = d_kf_pose_t;
     a.n_local = n_local, a.n_points = n_points, a.n_edges = n_edges;
     a.pose_kf = d_pose_kf, a.point_row = d_point_row, a.edge_off = d_edge_off, a.edge_kf = d_edge_kf, a.edge_kp = d_edge_kp;
     a.est_R = d_est_pose_R, a.est_t = d_est_pose_t, a.est_points = d_est_points, a.outlier = d_outlier, a.result = d_result;

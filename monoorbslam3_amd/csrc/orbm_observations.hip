@@ -38,6 +38,7 @@
 #include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
+#include "orbm_map.h"
 
 namespace {
 
@@ -47,11 +48,9 @@ constexpr int OB_T = 256;               // threads of the per-slot kernels
 constexpr int OB_MAX_GRID = 2048;       // workgroups; the threads stride beyond that
 constexpr int OB_SCAN_T = 1024;         // the scan's one workgroup
 constexpr int OB_WAVES = 4;             // rows in flight per workgroup of the sort
-constexpr int OB_KEY_SHIFT = 13;        // key = k << 13 | i
-constexpr int OB_MAX_KF = 262143;       // (n_kf << 13) fits in int32
+constexpr int OB_MAX_KF = 262143;       // the sort key k << MAP_KEY_SHIFT | i fits in int32
 constexpr int CL_T = 1024;              // the culling's one workgroup
 constexpr int CL_MAX_RECENT = 32;
-static_assert(ORBM_MEDIAN_MAX_STRIDE == 1 << OB_KEY_SHIFT, "the sort key packs the slot index into 13 bits");
 
 // result slots of the build and of the culling
 enum { B_NOBS = 0, B_OVERFLOW = 1, B_INVALID = 2, B_BAD_KF = 3, B_LONGEST = 4, B_TWICE = 5, B_LONG = 6 };
@@ -83,17 +82,13 @@ __global__ __launch_bounds__(OB_T) void k_obs_slots(int n_kf, const int32_t *__r
         if (bad[k]) { ++bad_kf; continue; }                        // KeyFrame::setBad erased them (KeyFrame.cpp:410)
         if (SCATTER) {
             const int pos = atomicAdd(&off[p + 1], 1);
-            if ((unsigned)pos < (unsigned)cap_obs) keys[pos] = (k << OB_KEY_SHIFT) | i;   // the count said so; never past the array
+            if ((unsigned)pos < (unsigned)cap_obs) keys[pos] = (k << MAP_KEY_SHIFT) | i;   // the count said so; never past the array
         } else {
             atomicAdd(&off[p + 1], 1);
         }
     }
     if (SCATTER) return;
-    invalid = wave_sum(invalid), bad_kf = wave_sum(bad_kf);
-    if ((threadIdx.x & 63) == 0) {
-        if (invalid) atomicAdd(&result[B_INVALID], invalid);
-        if (bad_kf) atomicAdd(&result[B_BAD_KF], bad_kf);
-    }
+    block_add(result, {B_INVALID, B_BAD_KF}, {invalid, bad_kf});
 }
 
 // off[0] = 0, off[p + 1] = the count of row p  ->  off[j] = the sum of the entries below j: row p starts at off[p + 1]
@@ -115,12 +110,9 @@ __global__ __launch_bounds__(OB_SCAN_T) void k_obs_scan(int32_t *__restrict__ of
     }
     const int incl = wave_scan(sum);
     if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
-    n_long = wave_sum(n_long);
+    block_add(&s_long, 0, n_long);
     longest = wave_max(longest);
-    if ((tid & 63) == 0) {
-        atomicMax(&s_longest, longest);
-        if (n_long) atomicAdd(&s_long, n_long);
-    }
+    if ((tid & 63) == 0) atomicMax(&s_longest, longest);
     __syncthreads();
     int before = incl - sum, total = 0;
     for (int w = 0; w < OB_SCAN_T / 64; ++w) {
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(OB_WAVES * 64) void k_obs_sort(const int32_t *__res
         for (int t0 = b; t0 < end; t0 += 64) {
             const int j = t0 + lane;
             const int key = j < end ? obs_kf[j] : 0;
-            const int k = key >> OB_KEY_SHIFT;
+            const int k = key >> MAP_KEY_SHIFT;
             int prev = __shfl_up(k, 1);
             if (lane == 0) prev = carry;
             carry = __builtin_amdgcn_readlane(k, 63);
@@ -198,57 +190,32 @@ struct CullArgs {
     double redundant_ratio, max_gap;
 };
 
-struct CullView {
-    int n_kf, stride, cap_points, n_obs;
+// the map (orbm_map.h) and the key-frame table's key points, for the octaves
+struct CullView : MapView {
     const void *const *kps;
-    const int32_t *kf_n;
-    const uint8_t *bad;       // read as it is NOW: never through the key-frame table's const pointer
-    const int32_t *slots;
-    const int32_t *obs_off, *obs_kf, *obs_kp;
 };
-
-// CSR entry j: both indices usable?  (the refresh's distrust; the slot index also has to exist in d_slots)
-__device__ __forceinline__ bool cull_entry(const CullView &v, int j, int &k, int &i)
-{
-    k = v.obs_kf[j], i = v.obs_kp[j];
-    return k >= 0 && k < v.n_kf && i >= 0 && i < min(v.kf_n[k], v.stride);
-}
-
-__device__ __forceinline__ bool cull_live(const CullView &v, int k, int i, int p)
-{
-    return v.slots[(size_t)k * v.stride + i] == p && v.bad[k] == 0;
-}
-
-__device__ __forceinline__ void cull_list(const CullView &v, int p, int &b, int &e)
-{
-    b = v.obs_off[p], e = v.obs_off[p + 1];
-    if (b < 0 || e < b || e > v.n_obs) b = e = 0;                  // offsets that do not describe a list: an empty one
-}
 
 __device__ __forceinline__ int cull_octave(const CullView &v, int k, int i)
 {
     return *(const int32_t *)((const char *)v.kps[k] + (size_t)i * sizeof(orbx_kp) + offsetof(orbx_kp, octave));
 }
 
-__global__ __launch_bounds__(CL_T) void k_cull(const CullArgs a, int n_kf, const void *const *kps, const int32_t *kf_n, uint8_t *bad,
-                                               int32_t *slots, int stride, uint8_t *valid, int cap_points, const int32_t *obs_off,
-                                               const int32_t *obs_kf, const int32_t *obs_kp, int n_obs, int32_t *ref_kf, int32_t *code,
-                                               int32_t *num_mp, int32_t *num_redundant, int32_t *result)
+__global__ __launch_bounds__(CL_T) void k_cull(const CullArgs a, const CullView v, uint8_t *bad, int32_t *ref_kf, int32_t *code, int32_t *num_mp,
+                                               int32_t *num_redundant, int32_t *result)
 {
     extern __shared__ uint32_t s_claim[];                          // bit p: row p's cascade has an owner
     __shared__ int s_count[8];
-    __shared__ int s_mp, s_red;
+    __shared__ int s_cand[2];                                      // numMP and the redundant slots of the candidate
     const int tid = threadIdx.x;
-    const CullView v = {n_kf, stride, cap_points, n_obs, kps, kf_n, bad, slots, obs_off, obs_kf, obs_kp};
-    for (int w = tid; w < (cap_points + 31) >> 5; w += CL_T) s_claim[w] = 0;
+    bits_zero<CL_T>(s_claim, v.cap_points);
     if (tid < 8) s_count[tid] = 0;
     if (tid < a.n_recent) code[tid] = -1, num_mp[tid] = 0, num_redundant[tid] = 0;
     __syncthreads();
     int dropped = 0, points_bad = 0, cleared = 0, reassigned = 0;   // per thread, summed at the end
     int culled = 0, kept = 0, skipped = 0;                          // the same in every thread
-    for (int j = tid; j < n_obs; j += CL_T) {
+    for (int j = tid; j < v.n_obs; j += CL_T) {
         int k, i;
-        dropped += !cull_entry(v, j, k, i);
+        dropped += !map_entry(v, j, k, i);
     }
     int last = 0;
     for (int idx = 1; idx < a.n_recent - 1; ++idx) {
@@ -261,34 +228,30 @@ __global__ __launch_bounds__(CL_T) void k_cull(const CullArgs a, int n_kf, const
             ++skipped;
             continue;
         }
-        if (tid == 0) s_mp = 0, s_red = 0;
+        if (tid == 0) s_cand[0] = 0, s_cand[1] = 0;
         __syncthreads();
-        const int n_c = min(max(kf_n[c], 0), stride);
-        int32_t *mine = slots + (size_t)c * stride;
+        const int n_c = map_slots(v, c);
+        int32_t *mine = map_slot(v, c, 0);
         // ---- numMP and the redundant slots (:339-362)
         int mp = 0, red = 0;
         for (int i = tid; i < n_c; i += CL_T) {
             const int p = mine[i];
-            if (p < 0 || p >= cap_points || !valid[p]) continue;
+            if (p < 0 || p >= v.cap_points || !v.valid[p]) continue;
             ++mp;
             int b, e, live = 0, others = 0;
-            cull_list(v, p, b, e);
+            map_list(v, p, b, e);
             const int level = cull_octave(v, c, i);
             for (int j = b; j < e; ++j) {
                 int k2, i2;
-                if (!cull_entry(v, j, k2, i2) || !cull_live(v, k2, i2, p)) continue;
+                if (!map_entry(v, j, k2, i2) || !map_live(v, k2, i2, p)) continue;
                 ++live;                                            // getNumObs()
                 others += k2 != c && cull_octave(v, k2, i2) <= level + 1;
             }
             red += live > a.th_obs && others >= a.th_obs;          // the break of :355 only caps the count
         }
-        mp = wave_sum(mp), red = wave_sum(red);
-        if ((tid & 63) == 0) {
-            if (mp) atomicAdd(&s_mp, mp);
-            if (red) atomicAdd(&s_red, red);
-        }
+        block_add(s_cand, {0, 1}, {mp, red});
         __syncthreads();
-        mp = s_mp, red = s_red;
+        mp = s_cand[0], red = s_cand[1];
         __syncthreads();                                           // read by everyone before the next candidate resets them
         if (tid == 0) num_mp[idx] = mp, num_redundant[idx] = red;
         if (!((double)red > a.redundant_ratio * (double)mp)) {     // :364
@@ -303,42 +266,35 @@ __global__ __launch_bounds__(CL_T) void k_cull(const CullArgs a, int n_kf, const
         __syncthreads();
         for (int i = tid; i < n_c; i += CL_T) {
             const int p = mine[i];
-            if (p < 0 || p >= cap_points || !valid[p]) continue;
-            const uint32_t bit = 1u << (p & 31);
-            if (atomicOr(&s_claim[p >> 5], bit) & bit) continue;   // another slot of c names p and owns it
+            if (p < 0 || p >= v.cap_points || !v.valid[p]) continue;
+            if (!bit_set(s_claim, p)) continue;                    // another slot of c names p and owns it
             int b, e, left = 0, first = -1;
-            cull_list(v, p, b, e);
+            map_list(v, p, b, e);
             for (int j = b; j < e; ++j) {
                 int k2, i2;
-                if (!cull_entry(v, j, k2, i2) || k2 == c || !cull_live(v, k2, i2, p)) continue;
+                if (!map_entry(v, j, k2, i2) || k2 == c || !map_live(v, k2, i2, p)) continue;
                 if (left++ == 0) first = k2;
             }
             if (ref_kf[p] == c && left > 0) ref_kf[p] = first, ++reassigned;   // observations.begin() (MapPoint.cpp:198-199)
             if (left > 2) continue;
-            valid[p] = 0;                                          // MapPoint::setBad (:202, :210-226)
+            v.valid[p] = 0;                                        // MapPoint::setBad (:202, :210-226)
             ++points_bad;
             for (int j = b; j < e; ++j) {
                 int k2, i2;
-                if (!cull_entry(v, j, k2, i2) || k2 == c || !cull_live(v, k2, i2, p)) continue;
-                slots[(size_t)k2 * stride + i2] = -1;              // KeyFrame::eraseMapPoint
+                if (!map_entry(v, j, k2, i2) || k2 == c || !map_live(v, k2, i2, p)) continue;
+                *map_slot(v, k2, i2) = -1;                         // KeyFrame::eraseMapPoint
                 ++cleared;
             }
         }
         __syncthreads();
         for (int i = tid; i < n_c; i += CL_T) {                    // map_points.clear() (KeyFrame.cpp:418); the claims go with it
             const int p = mine[i];
-            if (p >= 0 && p < cap_points) atomicAnd(&s_claim[p >> 5], ~(1u << (p & 31)));
+            if (p >= 0 && p < v.cap_points) atomicAnd(&s_claim[p >> 5], ~(1u << (p & 31)));
             mine[i] = -1;
         }
         __syncthreads();
     }
-    dropped = wave_sum(dropped), points_bad = wave_sum(points_bad), cleared = wave_sum(cleared), reassigned = wave_sum(reassigned);
-    if ((tid & 63) == 0) {
-        if (dropped) atomicAdd(&s_count[C_DROPPED], dropped);
-        if (points_bad) atomicAdd(&s_count[C_POINTS_BAD], points_bad);
-        if (cleared) atomicAdd(&s_count[C_CLEARED], cleared);
-        if (reassigned) atomicAdd(&s_count[C_REASSIGNED], reassigned);
-    }
+    block_add(s_count, {C_DROPPED, C_POINTS_BAD, C_CLEARED, C_REASSIGNED}, {dropped, points_bad, cleared, reassigned});
     if (tid == 0) s_count[C_CULLED] = culled, s_count[C_KEPT] = kept, s_count[C_SKIPPED] = skipped;
     __syncthreads();
     if (tid < 8) result[tid] = s_count[tid];
@@ -351,11 +307,7 @@ extern "C" int orbm_build_observations_device(orbm_t *h, int n_kf, const int32_t
                                               int32_t *d_obs_kf, int32_t *d_obs_kp, int32_t *d_result, void *stream)
 {
     if (!d_obs_off || !d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (n_kf < 0 || stride < 0 || cap_points < 0 || cap_obs < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
-    if (n_kf > 0 && (!d_n || !d_bad)) return orbx_set_error(ORBX_E_ARG, "null key-frame array");
-    if (n_kf > 0 && stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
-    if (cap_points > 0 && !d_valid) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
-    if (cap_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
+    if (int rc = orbm_check_map(n_kf, d_n, d_bad, d_slots, stride, d_valid, cap_points, d_obs_off, d_obs_kf, d_obs_kp, cap_obs)) return rc;   // the CSR to be
     if (int rc = orbm_check_stride(stride)) return rc;
     if (n_kf > OB_MAX_KF) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than 262143 key frames in one call");
     if (int rc = orbm_check_points(cap_points)) return rc;
@@ -390,12 +342,11 @@ extern "C" int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, ui
                                           int32_t *d_num_mp, int32_t *d_num_redundant, int32_t *d_result, void *stream)
 {
     if (!kf || !d_result) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (kf->n_kf < 0 || stride < 0 || cap_points < 0 || n_obs < 0 || n_recent < 0 || th_obs < 0)
-        return orbx_set_error(ORBX_E_ARG, "negative count");
-    if (kf->n_kf > 0 && (!kf->d_kps || !kf->d_n || !d_bad)) return orbx_set_error(ORBX_E_ARG, "null key-frame array");
-    if (kf->n_kf > 0 && stride > 0 && !d_slots) return orbx_set_error(ORBX_E_ARG, "null slot array");
-    if (cap_points > 0 && (!d_valid || !d_obs_off || !d_ref_kf)) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
-    if (n_obs > 0 && (!d_obs_kf || !d_obs_kp)) return orbx_set_error(ORBX_E_ARG, "null observation array");
+    MapView m;
+    if (int rc = orbm_map_view(&m, kf->n_kf, kf->d_n, d_bad, d_slots, stride, d_valid, cap_points, d_obs_off, d_obs_kf, d_obs_kp, n_obs)) return rc;
+    if (n_recent < 0 || th_obs < 0) return orbx_set_error(ORBX_E_ARG, "negative count");
+    if (kf->n_kf > 0 && !kf->d_kps) return orbx_set_error(ORBX_E_ARG, "null key-frame array");
+    if (cap_points > 0 && !d_ref_kf) return orbx_set_error(ORBX_E_ARG, "null map-point table array");
     if (n_recent > 0 && (!recent || !timestamps || !d_code || !d_num_mp || !d_num_redundant))
         return orbx_set_error(ORBX_E_ARG, "null candidate array");
     if (int rc = orbm_check_kf_rows(kf->d_kps)) return rc;
@@ -412,8 +363,7 @@ extern "C" int orbm_cull_keyframes_device(orbm_t *h, const orbm_kf_table *kf, ui
     a.n_recent = n_recent, a.first_kf = first_kf, a.th_obs = th_obs, a.redundant_ratio = redundant_ratio, a.max_gap = max_gap;
     const size_t claim_bytes = (size_t)((cap_points + 31) >> 5) * 4;   // <= 64 KB
     if (claim_bytes + 1024 > 64 * 1024) ORB_TRY(orbx_lds_opt_in((const void *)k_cull, claim_bytes));   // with the static 48 B: past 64 KB
-    hipLaunchKernelGGL(k_cull, dim3(1), dim3(CL_T), claim_bytes, s, a, kf->n_kf, kf->d_kps, kf->d_n, d_bad, d_slots, stride, d_valid,
-                       cap_points, d_obs_off, d_obs_kf, d_obs_kp, n_obs, d_ref_kf, d_code, d_num_mp, d_num_redundant, d_result);
+    hipLaunchKernelGGL(k_cull, dim3(1), dim3(CL_T), claim_bytes, s, a, CullView{m, kf->d_kps}, d_bad, d_ref_kf, d_code, d_num_mp, d_num_redundant, d_result);
     ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }

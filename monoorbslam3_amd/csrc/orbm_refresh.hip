@@ -63,6 +63,7 @@ __device__ __forceinline__ void camera_centre(const double *__restrict__ pose_R,
 }
 
 // observation j of a list that ends at `end`: usable (both indices in range) and of a key frame that is not bad?
+// Its own, not map_usable of orbm_map.h: the refresh reads descriptors, not slots, so the bound is kf.d_n[k] with no stride.
 __device__ __forceinline__ bool good_observation(const orbm_kf_table &kf, const int32_t *__restrict__ obs_kf, const int32_t *__restrict__ obs_kp,
                                                  int j, int end, int &k, int &f)
 {
