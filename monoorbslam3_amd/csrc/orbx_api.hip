@@ -1239,6 +1239,16 @@ extern "C" int orbx_dev_octree_plan(const orbx_cfg *cfg, int requota, int w0, in
     return ORBX_OK;
 }
 
+// Which (frame, item) the workgroup `block_id` of a batch kernel with `per_frame` workgroups per frame takes (the quadtree and
+// k_desc_bins: item = level), no device needed.  Returns 1 and fills *frame / *item for a live workgroup, 0 for a surplus one
+// (a frame count that is no multiple of 8: it returns at once), ORBX_E_ARG for a block outside the launch's grid.
+extern "C" int orbx_dev_xcd_map(int per_frame, int n_frames, int block_id, int *frame, int *item)
+{
+    if (per_frame < 1 || n_frames < 1 || !frame || !item) return orbx_set_error(ORBX_E_ARG, "bad argument");
+    const int rc = orbx_xcd_map_query(per_frame, n_frames, block_id, frame, item);
+    return rc < 0 ? orbx_set_error(ORBX_E_ARG, "block outside the grid") : rc;
+}
+
 extern "C" const char *orbx_last_error(void) { return g_err.c_str(); }
 extern "C" const char *orbx_version(void) { return "orbx 0.1 (gfx950)"; }
 

@@ -135,6 +135,9 @@ struct OrbxOctPlan { int kind; size_t lds_bytes, huge_bytes; int huge_end; };
 OrbxOctPlan orbx_octree_plan(const OrbxLevels &levels, int n_frames, int level_begin, int level_end, int n_cus = ORBX_N_CUS);
 void orbx_launch_octree(hipStream_t s, const OrbxLevels *d_levels, const OrbxLevels &levels, const OrbxBuffers &b,
                         int n_frames, size_t sort_lds_bytes, int level_begin, int level_end, int n_cus = ORBX_N_CUS);
+// The workgroup -> (frame, level) mapping of the batch quadtree and k_desc_bins as the host sees it (orbx_dev_xcd_map):
+// 1 = live, 0 = surplus workgroup (returns at once), -1 = block_id outside the launch's grid.
+int orbx_xcd_map_query(int per_frame, int n_frames, long long block_id, int *frame, int *item);
 void orbx_launch_orient_desc(hipStream_t s, const uint8_t *l0, size_t l0_fs, int l0_pitch, const OrbxLevels *d_levels,
                              const OrbxLevels &levels, const OrbxBuffers &b, const int *u_max, orbx_kp *out_kp,
                              uint8_t *out_desc, int cap, int32_t *out_n, int n_frames, hipEvent_t blur_done, int desc_level_min = 0,

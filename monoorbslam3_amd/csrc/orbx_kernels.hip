@@ -23,25 +23,59 @@ typedef unsigned long long u64;
 // A call with fewer than 8 frames would leave XCDs idle that way -- a single frame would run on ONE XCD, an eighth of
 // the chip, which is what a latency-bound call can least afford -- so below 8 frames the blocks are dealt in plain order
 // (frame = id / per_frame) and every frame spreads over all XCDs.
-// Launch with orbx_xcd_grid(per_frame, n_frames) blocks.
-__device__ __forceinline__ bool xcd_remap(int per_frame, int n_frames, int *frame, int *item)
+// Every batch kernel whose grid is (frame, something) goes through one of the two helpers below, on a 1-D grid of
+// orbx_xcd_grid(per_frame, n_frames) blocks: orbx_xcd_map / xcd_remap where the items of a frame share data (tiles, strips,
+// key-point blocks: a frame's items follow each other), orbx_xcd_map_levels where the item is a pyramid level.
+__host__ __device__ __forceinline__ bool orbx_xcd_map(int id, int per_frame, int n_frames, int *frame, int *item)
 {
     if (n_frames < 8) {
-        const int id = blockIdx.x, f = id / per_frame;
+        const int f = id / per_frame;
         *item = id - f * per_frame;
         *frame = f;
         return f < n_frames;
     }
-    const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
+    const int xcd = id & 7, j = id >> 3;
     const int g = j / per_frame;
     *item = j - g * per_frame;
     *frame = g * 8 + xcd;
+    return *frame < n_frames;
+}
+__device__ __forceinline__ bool xcd_remap(int per_frame, int n_frames, int *frame, int *item)
+{
+    return orbx_xcd_map((int)blockIdx.x, per_frame, n_frames, frame, item);
+}
+// The kernels with one workgroup per (frame, level) -- the batch quadtree, k_desc_bins -- take the same grid and the same
+// frames per XCD, but level by level, lowest level first: item = level, and all of an XCD's frames at level 0 come before the
+// first at level 1.  A level's workgroups differ several times in weight (1242 x 375 / 2000 features: 3099 candidates and
+// 27.6 us at level 0, 691 and 10.7 us at level 7), so the heaviest start first and the light ones fill the tail.
+// NEVER launch such a kernel as a (levels, frames) 2-D grid: its linear block id is level + n_levels * frame, and with a level
+// count that divides 8 (or is a multiple of it) every workgroup of a level lands on ONE XCD -- the kernel then lasts as long as
+// the XCD that got level 0 (512 frames x 8 levels: quadtree 226 us that way, 118 us this way; profiles/xcd_balance.md).
+// Below 8 frames: plain order, level by level (a level's workgroups go to as many XCDs).
+__host__ __device__ __forceinline__ bool orbx_xcd_map_levels(int id, int per_frame, int n_frames, int *frame, int *item)
+{
+    if (n_frames < 8) {
+        const int it = id / n_frames;
+        *item = it;
+        *frame = id - it * n_frames;
+        return it < per_frame;
+    }
+    const int xcd = id & 7, j = id >> 3, groups = (n_frames + 7) >> 3; // frames per XCD, surplus ones included
+    const int it = j / groups;
+    *item = it;
+    *frame = (j - it * groups) * 8 + xcd;
     return *frame < n_frames;
 }
 static inline unsigned orbx_xcd_grid(int per_frame, int n_frames)
 {
     if (n_frames < 8) return (unsigned)n_frames * (unsigned)per_frame;
     return 8u * (unsigned)((n_frames + 7) / 8) * (unsigned)per_frame;
+}
+
+int orbx_xcd_map_query(int per_frame, int n_frames, long long block_id, int *frame, int *item)
+{
+    if (block_id < 0 || block_id >= (long long)orbx_xcd_grid(per_frame, n_frames)) return -1;
+    return orbx_xcd_map_levels((int)block_id, per_frame, n_frames, frame, item) ? 1 : 0;
 }
 
 // Development hook (orbx_dev_set_lds_pad, not declared in include/): extra dynamic LDS per workgroup of a batch kernel, so that a
@@ -1799,7 +1833,9 @@ namespace oct_batch {
 #define OCT_NT ORBX_OCT_THREADS_BATCH
 #define OCT_REG 8
 #define OCT_MIN_WAVES 4 // four 256-thread workgroups per CU: the register allocator stays at 128 VGPRs (133 without the bound: three workgroups, 0.23 -> 0.27 ms)
+#define OCT_XCD 1 // more workgroups than the chip holds at once: every XCD gets its share of every level (orbx_xcd_map_levels)
 #include "orbx_octree.h"
+#undef OCT_XCD
 #undef OCT_MIN_WAVES
 #undef OCT_REG
 #undef OCT_NT
@@ -1878,8 +1914,9 @@ void orbx_launch_octree(hipStream_t s, const OrbxLevels *d_levels, const OrbxLev
     switch (p.kind) {
     case 0:
         (void)orbx_lds_opt_in(reinterpret_cast<const void *>(oct_batch::k_octree_lds), p.lds_bytes); // per device; a refusal shows as the launch error the caller checks
-        hipLaunchKernelGGL(oct_batch::k_octree_lds, grid, dim3(ORBX_OCT_THREADS_BATCH), p.lds_bytes + dev_pad(oct_batch::k_octree_lds, 2, p.lds_bytes), s,
-                           d_levels, b, level_begin, lds);
+        hipLaunchKernelGGL(oct_batch::k_octree_lds, dim3(orbx_xcd_grid(level_end - level_begin, n_frames)), dim3(ORBX_OCT_THREADS_BATCH),
+                           p.lds_bytes + dev_pad(oct_batch::k_octree_lds, 2, p.lds_bytes), s, d_levels, b, level_begin, lds,
+                           level_end - level_begin, n_frames);
         break;
     case 2:
         (void)orbx_lds_opt_in(reinterpret_cast<const void *>(oct_huge::k_octree_lds), p.huge_bytes);
@@ -2336,11 +2373,15 @@ __host__ __device__ __forceinline__ int bd_sub_bucket(int x, int y, int n_ty)
 // also the frame's total count (what k_orient_desc's first workgroup does on the two-kernel path).
 __global__ __launch_bounds__(256) void k_desc_bins(const OrbxLevels *__restrict__ levels, BdLevels lv, OrbxBuffers b,
                                                    int *__restrict__ bk_start, int bk_stride, BdItem *__restrict__ items, int cap,
-                                                   int32_t *__restrict__ out_n)
+                                                   int32_t *__restrict__ out_n, int n_fused_levels, int n_frames)
 {
     extern __shared__ int s_bins[]; // [nb + 1] starts, [nb] cursors
     __shared__ int s_part[256];
-    const int level = blockIdx.x, frame = blockIdx.y, tid = threadIdx.x;
+    int frame, level;
+    if (!orbx_xcd_map_levels((int)blockIdx.x, n_fused_levels, n_frames, &frame, &level)) return;
+    frame = __builtin_amdgcn_readfirstlane(frame); // (uniform, but the division leaves them in vector registers)
+    level = __builtin_amdgcn_readfirstlane(level);
+    const int tid = threadIdx.x;
     const int kc = levels->kcap_total, L = levels->n_levels;
     const int *cnts = b.sel_count + frame * ORBX_MAX_LEVELS;
     if (level == 0 && tid == 0) {
@@ -2647,8 +2688,8 @@ void orbx_launch_desc_bins(hipStream_t s, const OrbxLevels *d_levels, const Orbx
     if (n_fused_levels <= 0) return;
     int max_nb = 1;
     for (int l = 0; l < n_fused_levels; ++l) max_nb = std::max(max_nb, 2 * tab.n_bx[l] * tab.n_ty[l]);
-    hipLaunchKernelGGL(k_desc_bins, dim3(n_fused_levels, n_frames), dim3(256), sizeof(int) * (2 * (size_t)max_nb + 1), s, d_levels, tab, b,
-                       d_bk_start, bk_stride, reinterpret_cast<BdItem *>(d_items), cap, out_n);
+    hipLaunchKernelGGL(k_desc_bins, dim3(orbx_xcd_grid(n_fused_levels, n_frames)), dim3(256), sizeof(int) * (2 * (size_t)max_nb + 1), s, d_levels,
+                       tab, b, d_bk_start, bk_stride, reinterpret_cast<BdItem *>(d_items), cap, out_n, n_fused_levels, n_frames);
 }
 
 void orbx_launch_desc_fused(hipStream_t s, const uint8_t *l0, size_t l0_fs, int l0_pitch, const OrbxLevels &levels, const OrbxBuffers &b,

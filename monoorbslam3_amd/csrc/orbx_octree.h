@@ -573,8 +573,21 @@ __device__ __forceinline__ void octl_apply_pyr(const OctL &c, const OctPyr &py, 
 #ifndef OCT_MIN_WAVES
 #define OCT_MIN_WAVES 1
 #endif
-__global__ __launch_bounds__(OCT_NT, OCT_MIN_WAVES) void k_octree_lds(const OrbxLevels *__restrict__ levels, OrbxBuffers b, int level0, int dyn_lds_bytes)
+#ifdef OCT_XCD // 1-D grid of orbx_xcd_grid(n_levels, n_frames) workgroups, (frame, level) from orbx_xcd_map_levels (orbx_kernels.hip)
+#define OCT_GRID_ARGS , int n_levels, int n_frames
+#else          // grid (levels, frames)
+#define OCT_GRID_ARGS
+#endif
+__global__ __launch_bounds__(OCT_NT, OCT_MIN_WAVES) void k_octree_lds(const OrbxLevels *__restrict__ levels, OrbxBuffers b, int level0, int dyn_lds_bytes OCT_GRID_ARGS)
+#undef OCT_GRID_ARGS
 {
+#ifdef OCT_XCD
+    int frame, level;
+    if (!orbx_xcd_map_levels((int)blockIdx.x, n_levels, n_frames, &frame, &level)) return; // surplus workgroup of a frame count that is no multiple of 8
+    // (the division leaves its uniform results in vector registers, and every address derived from them with it: back to scalars)
+    frame = __builtin_amdgcn_readfirstlane(frame);
+    level = level0 + __builtin_amdgcn_readfirstlane(level);
+#endif
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ int lds[64];
     int par = 0; // which half of `lds` the next scan uses
@@ -585,7 +598,9 @@ __global__ __launch_bounds__(OCT_NT, OCT_MIN_WAVES) void k_octree_lds(const Orbx
     // phase stamps, a level-0 quadtree stood still for 49 us -- the run time of the FAST launch beside it -- at default priority.
     __builtin_amdgcn_s_setprio(3);
 #endif
+#ifndef OCT_XCD
     const int level = level0 + blockIdx.x, frame = blockIdx.y;
+#endif
     const OrbxLevel lv = levels->lv[level];
     const int tid = threadIdx.x;
     OctL c;

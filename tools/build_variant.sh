@@ -9,7 +9,7 @@ mkdir -p ../lib/variants
 name=$1; shift
 FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-result --offload-arch=gfx950 -mllvm -amdgpu-mfma-vgpr-form=1"
 objs=""
-for f in orbx_kernels orbx_api orbm_matcher orbba orbf_frame orbv_vocab orbd_dist; do
+for f in orbx_kernels orbx_api $(basename -s .hip orbm_*.hip) orbba orbf_frame orbv_vocab orbd_dist orbi_imu; do # the Makefile's SRCS
   if [[ " $VARIANT_FILES " == *" $f "* ]]; then
     /opt/rocm/bin/hipcc $FLAGS "$@" -c -o /tmp/var_${name}_$f.o $f.hip &
     objs="$objs /tmp/var_${name}_$f.o"
