@@ -1,5 +1,5 @@
 /*
- * orbi.h -- IMU preintegration and the frame-pose prediction on the device (liborbx.so, gfx950).
+ * orbi.h -- IMU preintegration, the frame-pose prediction and the linearised inertial factors on the device (liborbx.so, gfx950).
  *
  * What the tracker does with the inertial samples of a frame once the mapper has initialised the IMU (reference
  * modules/Sensor/Imu.cpp:76-204, modules/BasicObject/Frame.cpp:57-88, KeyFrame.cpp:100-115, Tracking.cpp:90-91, :185-243):
@@ -7,7 +7,9 @@
  * them, and hand that pose to the projection search.  Everything here lives in caller-owned DEVICE memory, so the chain
  *   orbi_integrate_device -> orbi_predict_device -> orbm_project_frame_device (orbm.h) -> the searches -> poseOptimize ->
  *   orbi_imu_pose_device
- * runs on one stream without a host hop.  The inertial optimisers of Optimize.cpp and KeyFrame::setPrioriInformation are not here.
+ * runs on one stream without a host hop.  Of the inertial optimisers of Optimize.cpp the per-iteration linearisation of their
+ * inertial edges, bias walks and priors is here, with KeyFrame::setPrioriInformation ("Inertial factors linearised on the device"
+ * below); their Levenberg-Marquardt loops are not.
  *
  * Every entry point is a handle-less `*_device` entry point under the one stream rule of orbx.h ("Streams and threads"): it
  * enqueues on exactly the `stream` it is given (a hipStream_t; NULL is stream 0 itself), allocates nothing and never waits on
@@ -80,6 +82,66 @@
  * One wave per job, four waves per workgroup: the record, the 9x9 product's intermediate and the 3x3 temporaries live in the
  * wave's own part of LDS, the lanes are spread over matrix entries, and the phases of a sample are separated by wave-level
  * fences only -- no workgroup barrier inside the sample loop.
+ *
+ * ---- Inertial factors linearised on the device (declarations: orbi_factors.h, included at the end of this file) ----
+ *
+ * What poseInertialOptimize, poseFullOptimize, localInertialBundleAdjustment and localFullBundleAdjustment (Optimize.cpp:547-608,
+ * :610-760, :960-1060, :1090-1250) do per iteration with their inertial edges, for a caller who keeps g2o's solver (orbba_linearize is
+ * the same layer for the visual edges): computeError, linearizeOplus, the information matrices and constructQuadraticForm.  The loops
+ * themselves, the visual edges in the IMU-pose parametrisation and the edges of the IMU initialisation are not here.  Same rules as
+ * above: handle-less, one stream, no allocation, no host wait, arguments first (ORBX_E_ARG), then ORBX_E_NO_DEVICE, no CPU path,
+ * d_result 8 x int32 written by every call.
+ *
+ * The graph (orbi_graph, by value; all arrays the caller's, in device memory)
+ *   vertices   n_states states, each the estimates of one VertexPose and three Vertex3D in DOUBLE as g2o holds them: Rwb[n][9] (row-
+ *              major), twb[n][3], v[n][3], bg[n][3], ba[n][3]; fixed[n] (uint8): ORBI_FIX_POSE / _VELO / _GYRO / _ACC = setFixed of that
+ *              vertex, also "this state has no such vertex".
+ *   dof        15 per state, [dphi, dt, dv, dbg, dba].  The pose part is CameraImuPose::update (G2oTypes.cpp:10-25): t_wb += R_wb*dt, then
+ *              R_wb <- R_wb*ExpSO3(dphi), and NormalizeRotation after every third update (d_iter, the caller's counter per state).
+ *   edges      orbi_edge {i, j, rec, flags}: EdgeInertial (G2oTypes.cpp:377-445) between states i (first) and j (second) with record
+ *              `rec` of the bank; with both poses fixed it is EdgeInertialOnly (:309-356, the same residual and the same velocity and
+ *              bias Jacobians).  The bias vertices it reads are state i's.  ORBI_EDGE_WALKS: the edge also carries the gyro and the acc
+ *              EdgeBiasWalk between the bias vertices of i and j (Optimize.cpp:1019-1029, :1163-1170), e = b_j - b_i, J = (-I, +I).
+ *   priors     orbi_prior per slot, floats as KeyFrame holds them; orbi_prior_job {state, prior, mask}: the EdgePriori3D of the
+ *              state's velocity (ORBI_PRIOR_VELO), gyro bias (_GYRO) and acc bias (_ACC), e = priori - estimate, J = -I.  THE ACC
+ *              PRIOR IS WEIGHTED WITH acc_info, as poseInertialOptimize does (Optimize.cpp:594); with ORBI_PRIOR_ACC_GYRO_INFO it is
+ *              weighted with gyro_info, which is what localFullBundleAdjustment passes (Optimize.cpp:1189).  Two jobs naming one
+ *              (state, bit) are both applied, as g2o would.
+ *   distrust   an edge with i, j or rec outside its range, or i == j, and a prior job with its state or slot outside its range, is
+ *              dropped and counted; its outputs are zero.
+ *
+ * Arithmetic.  The parts the reference computes in float are float, in this header's orders, bit for bit tests/imu_model.py: with
+ * bgf, baf = the bias vertices of state i cast to float, dbg = bgf - bias.bg, dba = baf - bias.ba (Imu.cpp:182-192):
+ *       dR = NormalizeRotationf(dR*ExpSO3f(JRg*dbg))   dV = (dV + JVg*dbg) + JVa*dba   dP = (dP + JPg*dbg) + JPa*dba
+ * Everything behind the cast to double is IEEE double: +, -, *, / without fused multiply-add, the device's sqrt, sin, cos and atan2,
+ * each expression read left to right, a 3x3 product summed as (p0 + p1) + p2, longer sums ascending from zero; LogSO3,
+ * RightJacobianSO3 and InverseRightJacobianSO3 with their 1e-6 branches and the tr == 3 exit (LieAlgeBra.cpp:60-112); dt and g =
+ * (0, 0, -gravity) are the floats widened; tests/factors_model.py restates it and the device is held to 1e-9 of it.
+ *   information   d_info = (X + X^T)/2, X the general inverse of C[0:9,0:9] widened to double (Gauss-Jordan on [C | I], partial
+ *              pivoting: the first row of the largest |entry|; the pivot row is divided by the pivot), NOT symmetrised first
+ *              (G2oTypes.cpp:366-367).  The eigenvalue clamp behind it (:368-372) is omitted: the smallest eigenvalue is 7e6 .. 3e9
+ *              on records of 2 .. 400 samples, against the threshold 1e-12 (tests/test_factors_cpu.py asserts the clamp is a no-op on
+ *              every test record).  d_walk_info: the inverses of C[9:12,9:12] and C[12:15,12:15] by cofactors (adj/det).
+ *   priors     orbi_prior_information_device, in double from the float C, stored as float: velo_info = V*diag(lambda)*V^T of the
+ *              symmetrised C[3:6,3:6] by ORBI_JACOBI_SWEEPS cyclic Jacobi sweeps over the pairs (0,1), (0,2), (1,2) (theta = (a_qq -
+ *              a_pp)/(2 a_pq), t = sgn(theta)/(|theta| + sqrt(theta^2 + 1)), c = 1/sqrt(t^2 + 1), s = t*c), eigenvalues < 1e-12 set to 0;
+ *              gyro_info / acc_info by cofactors.
+ *   the form   chi2 = e^T*Omega*e.  Huber (huber_delta > 0, inertial edges only; g2o's RobustKernelHuber as in orbba.h): chi2 >
+ *              delta^2: rho = 2*sqrt(chi2)*delta - delta^2, w = delta/sqrt(chi2); else rho = chi2, w = 1.  H += J^T*(w*Omega)*J,
+ *              b -= J^T*(w*Omega)*e with the columns of fixed dof removed from J, so that rows and columns of fixed dof are zero; chi2
+ *              does not look at the fixed masks.  d_H_off[e] is the block (rows: state i, columns: state j) of edge e alone.  A
+ *              diagonal block and b add up their contributions in ascending edge order (the edge's inertial part, then its walks),
+ *              the prior jobs last in ascending order; d_total = (plain, robustified) adds up edges ascending, each as inertial, gyro
+ *              walk, acc walk, then prior jobs ascending as velocity, gyro, acc.  No floating-point atomics: the same input gives the
+ *              same bytes.
+ *
+ * Kernel resources (gfx950, VGPRs / scratch bytes / static LDS bytes; tests/test_factors_resources.py reads them from the ISA):
+ *   k_fac_prior_info 103 / 0 / 32 B, k_fac_init 40 / 0 / 32 B, k_fac_edge_info 40 / 0 / 5792 B, k_fac_edge 81 / 0 / 28640 B,
+ *   k_fac_gather 50 / 0 / 32 B, k_fac_oplus 70 / 0 / 32 B, k_fac_recover 38 / 0 / 32 B, k_fac_clear 2 / 0 / 0 B.
+ * The graphs are tiny (2 states for the tracker, a few tens for a local window) and every call is latency-bound: nothing here has
+ * been tuned for throughput and no throughput claim is made.  An inertial edge is one wave, four per workgroup (k_imu's shape), its
+ * 9x30 Jacobian, the 9x9 information and their product in the wave's own LDS slice; a wave per state then gathers its edges in edge
+ * order from the caller's workspace.  The float helpers come from csrc/orbi_so3.h, shared with orbi_imu.hip.
  */
 #ifndef ORBI_H
 #define ORBI_H
@@ -180,4 +242,8 @@ int orbi_imu_pose_device(orbi_calib calib, const double *d_pose_R, const double 
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- Inertial factors linearised on the device: the declarations (the text is above) ---- */
+#include "orbi_factors.h"
+
 #endif

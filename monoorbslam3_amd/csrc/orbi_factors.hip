@@ -1,0 +1,889 @@
+// Inertial factors linearised on the device (include/orbi.h, "Inertial factors linearised on the device"; include/orbi_factors.h):
+//   orbi_prior_information_device   KeyFrame::setPrioriInformation, the constructor's priors          KeyFrame.cpp:23-24, 86-98
+//   orbi_graph_init_device          the vertices of the inertial optimisers                           Optimize.cpp:557-573, 623-651, 992-1007
+//   orbi_edge_information_device    the information of EdgeInertial[Only] and of the bias walks       G2oTypes.cpp:366-367, Optimize.cpp:1022, 1028
+//   orbi_linearize_device           computeError, linearizeOplus, constructQuadraticForm              G2oTypes.cpp:377-445, G2oTypes.h:324-343, 452-470
+//   orbi_graph_oplus_device         oplusImpl                                                         G2oTypes.cpp:10-25
+//   orbi_graph_recover_device       step 5 of the optimisers                                          Optimize.cpp:602-607, 1044-1053
+//
+// The float part of an edge (the deltas of the bias vertices cast to float) is orbi_imu.hip's arithmetic, from the shared orbi_so3.h;
+// everything behind the cast is IEEE double, +, -, *, / in the header's orders without fused multiply-add, and the device's sin, cos,
+// atan2 and sqrt.
+//
+// Shape: the graphs are tiny (two states for the tracker, a few tens for a local window), so every kernel is latency-bound and the
+// aim is few launches and short dependent chains, not throughput.  An inertial edge is ONE WAVE, four per workgroup (k_imu's shape):
+// its vertices, the 3x3 temporaries, the 9x30 Jacobian, the 9x9 information and their product live in the wave's own slice of LDS,
+// the lanes are spread over matrix entries and the phases are separated by wave-level fences only.  The edge leaves its two diagonal
+// blocks and its right-hand sides in the caller's workspace; then ONE WAVE PER STATE adds them up in ascending edge order, the priors
+// last, so no floating-point atomic is needed and the same input gives the same bytes.  One more wave computes the priors' chi2 and
+// the totals in their fixed order.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <string>
+
+#include "../../include/orbi.h"
+#include "../../include/orbx.h"
+#include "orb_host.h"
+#include "orb_math.h"
+#include "orbi_so3.h"
+
+#pragma clang fp contract(off)
+
+static_assert(sizeof(orbi_edge) == 16 && sizeof(orbi_prior) == 144 && sizeof(orbi_prior_job) == 12 && sizeof(orbi_graph) == 56,
+              "orbi_factors.h fixes these layouts");
+
+namespace {
+
+__device__ __forceinline__ double dsum3(double p0, double p1, double p2) { return ORB_DADD(ORB_DADD(p0, p1), p2); }
+__device__ __forceinline__ double dmul(double a, double b) { return ORB_DMUL(a, b); }
+// entries (i, j) of A*B, A^T*B, A*B^T, A^T*B^T and (s*hat(x,y,z))*hat(x,y,z); matrices row-major
+__device__ __forceinline__ double dm3(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[3 * i], B[j]), dmul(A[3 * i + 1], B[3 + j]), dmul(A[3 * i + 2], B[6 + j])); }
+__device__ __forceinline__ double dm3t(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[i], B[j]), dmul(A[3 + i], B[3 + j]), dmul(A[6 + i], B[6 + j])); }
+__device__ __forceinline__ double dm3nt(const double *A, const double *B, int i, int j) { return dsum3(dmul(-A[3 * i], B[3 * j]), dmul(-A[3 * i + 1], B[3 * j + 1]), dmul(-A[3 * i + 2], B[3 * j + 2])); } // (-A)*B^T
+__device__ __forceinline__ double dm3tt(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[i], B[3 * j]), dmul(A[3 + i], B[3 * j + 1]), dmul(A[6 + i], B[3 * j + 2])); }
+__device__ __forceinline__ double dmv3t(const double *A, double x0, double x1, double x2, int i) { return dsum3(dmul(A[i], x0), dmul(A[3 + i], x1), dmul(A[6 + i], x2)); } // (A^T*x)_i
+__device__ __forceinline__ double dhat(double x, double y, double z, int e)
+{
+    return e == 1 ? -z : e == 2 ? y : e == 3 ? z : e == 5 ? -x : e == 6 ? -y : e == 7 ? x : 0.0;
+}
+__device__ __forceinline__ double deye(int e) { return (e == 0 || e == 4 || e == 8) ? 1.0 : 0.0; }
+__device__ __forceinline__ double dsww(double s, double x, double y, double z, int i, int j) // ((s*W)*W)_ij, W = Hat(x, y, z), zeros multiplied
+{
+    return dsum3(dmul(dmul(s, dhat(x, y, z, 3 * i)), dhat(x, y, z, j)), dmul(dmul(s, dhat(x, y, z, 3 * i + 1)), dhat(x, y, z, 3 + j)),
+                 dmul(dmul(s, dhat(x, y, z, 3 * i + 2)), dhat(x, y, z, 6 + j)));
+}
+__device__ __forceinline__ double dnorm2(double x, double y, double z) { return dsum3(dmul(x, x), dmul(y, y), dmul(z, z)); }
+// the double Newton step towards the polar factor: NormalizeRotationf's sequence, widened
+__device__ __forceinline__ double dcof(const double *X, int i, int j)
+{
+    const int p = i == 2 ? 0 : i + 1, r = i == 0 ? 2 : i - 1, q = j == 2 ? 0 : j + 1, s = j == 0 ? 2 : j - 1;
+    return dmul(X[3 * p + q], X[3 * r + s]) - dmul(X[3 * p + s], X[3 * r + q]);
+}
+__device__ __forceinline__ double ddet(const double *X) { return dsum3(dmul(X[0], dcof(X, 0, 0)), dmul(X[1], dcof(X, 0, 1)), dmul(X[2], dcof(X, 0, 2))); }
+
+constexpr int FAC_WAVES = 4, FAC_T = 64 * FAC_WAVES;
+
+// per-workgroup counters -> d_result: one workgroup writes, several add to what k_fac_clear zeroed ahead of them on the stream
+__global__ void k_fac_clear(int32_t *__restrict__ result)
+{
+    if (threadIdx.x < 8) result[threadIdx.x] = 0;
+}
+__device__ __forceinline__ void flush_counts(const int *s_cnt, int32_t *result)
+{
+    if (threadIdx.x < 8) {
+        const int v = s_cnt[threadIdx.x];
+        if (gridDim.x == 1) result[threadIdx.x] = v;
+        else if (v) atomicAdd(&result[threadIdx.x], v);
+    }
+}
+
+// ---- orbi_prior_information_device: a thread per job ---------------------------------------------------------------------------------
+// one cyclic Jacobi rotation of the symmetric A on the pair (P, Q), R the third index; V collects the eigenvectors in its columns
+#define JROT(P, Q, R)                                                                             \
+    do {                                                                                          \
+        const double apq = A[P][Q];                                                               \
+        if (apq != 0.0) {                                                                         \
+            const double th = (A[Q][Q] - A[P][P]) / (2.0 * apq);                                  \
+            const double t = (th < 0.0 ? -1.0 : 1.0) / (fabs(th) + sqrt(th * th + 1.0));          \
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;                                  \
+            const double arp = A[R][P], arq = A[R][Q];                                            \
+            A[P][P] = A[P][P] - t * apq, A[Q][Q] = A[Q][Q] + t * apq;                             \
+            A[P][Q] = A[Q][P] = 0.0;                                                              \
+            A[R][P] = A[P][R] = c * arp - s * arq;                                                \
+            A[R][Q] = A[Q][R] = s * arp + c * arq;                                                \
+            _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                       \
+                const double vp = V[k][P], vq = V[k][Q];                                          \
+                V[k][P] = c * vp - s * vq, V[k][Q] = s * vp + c * vq;                             \
+            }                                                                                     \
+        }                                                                                         \
+    } while (0)
+
+// the inverse of the 3x3 block of the float C at (o, o) by cofactors, in double; false when its determinant is 0
+__device__ __forceinline__ bool inverse3(const float *C, int o, double inv[9])
+{
+    double X[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) X[k] = (double)C[15 * (o + k / 3) + o + k % 3];
+    const double det = ddet(X);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) inv[k] = dcof(X, k % 3, k / 3) / det;   // the adjugate: cofactor (j, i)
+    return det != 0.0;
+}
+
+__global__ __launch_bounds__(64) void k_fac_prior_info(orbi_prior *__restrict__ priors, int n_priors, const orbi_record *__restrict__ bank, int cap,
+                                                       const float *__restrict__ src, int n_src, const int32_t *__restrict__ jobs, int n,
+                                                       int32_t *__restrict__ result)
+{
+    __shared__ int s_cnt[8];
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int job = blockIdx.x * 64 + threadIdx.x;
+    if (job < n) {
+        const int slot = jobs[3 * job], rec = jobs[3 * job + 1], st = jobs[3 * job + 2];
+        int code = ORBI_R_DONE;
+        if (slot < 0 || slot >= n_priors || rec < 0 || rec >= cap || st < -1 || st >= n_src || (st >= 0 && !src)) code = ORBI_R_RANGE;
+        else {
+            for (int k = 0; k < job; ++k)
+                if (jobs[3 * k] == slot) code = ORBI_R_DUPLICATE;
+        }
+        if (code == ORBI_R_DONE) {
+            const float *C = bank[rec].C;
+            double gi[9], ai[9];
+            const bool ok_g = inverse3(C, 9, gi), ok_a = inverse3(C, 12, ai);
+            if (!ok_g || !ok_a) code = ORBI_R_REFUSED;
+            else {
+                double A[3][3], V[3][3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        A[i][j] = ((double)C[15 * (3 + i) + 3 + j] + (double)C[15 * (3 + j) + 3 + i]) / 2.0;
+                        V[i][j] = i == j ? 1.0 : 0.0;
+                    }
+                for (int sweep = 0; sweep < ORBI_JACOBI_SWEEPS; ++sweep) {
+                    JROT(0, 1, 2);
+                    JROT(0, 2, 1);
+                    JROT(1, 2, 0);
+                }
+                double lam[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) lam[k] = A[k][k] < 1e-12 ? 0.0 : A[k][k];
+                orbi_prior *p = priors + slot;
+#pragma unroll
+                for (int i = 0; i < 3; ++i)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j)
+                        p->velo_info[3 * i + j] = (float)dsum3(dmul(dmul(V[i][0], lam[0]), V[j][0]), dmul(dmul(V[i][1], lam[1]), V[j][1]),
+                                                               dmul(dmul(V[i][2], lam[2]), V[j][2]));
+#pragma unroll
+                for (int k = 0; k < 9; ++k) p->gyro_info[k] = (float)gi[k], p->acc_info[k] = (float)ai[k];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) p->bias_priori[k] = bank[rec].updated_bias[k];
+                if (st >= 0) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) p->velo_priori[k] = src[15 * (size_t)st + 12 + k];
+                }
+            }
+        }
+        atomicAdd(&s_cnt[code], 1);
+    }
+    __syncthreads();
+    flush_counts(s_cnt, result);
+}
+
+// ---- orbi_graph_init_device / orbi_graph_oplus_device / orbi_graph_recover_device: a thread per job or state ------------------------------
+__global__ __launch_bounds__(64) void k_fac_init(const orbi_graph g, const orbi_record *__restrict__ bank, int cap, const float *__restrict__ src,
+                                                 int n_src, const int32_t *__restrict__ jobs, int n, int32_t *__restrict__ result)
+{
+    __shared__ int s_cnt[8];
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int job = blockIdx.x * 64 + threadIdx.x;
+    if (job < n) {
+        const int st = jobs[3 * job], from = jobs[3 * job + 1], rec = jobs[3 * job + 2];
+        int code = ORBI_R_DONE;
+        if (st < 0 || st >= g.n_states || from < 0 || from >= n_src || rec < -1 || rec >= cap) code = ORBI_R_RANGE;
+        else {
+            for (int k = 0; k < job; ++k)
+                if (jobs[3 * k] == st) code = ORBI_R_DUPLICATE;
+        }
+        if (code == ORBI_R_DONE) {
+            const float *f = src + 15 * (size_t)from;
+            for (int k = 0; k < 9; ++k) g.Rwb[9 * (size_t)st + k] = (double)f[k];
+            for (int k = 0; k < 3; ++k) {
+                g.twb[3 * (size_t)st + k] = (double)f[9 + k];
+                g.v[3 * (size_t)st + k] = (double)f[12 + k];
+                g.bg[3 * (size_t)st + k] = rec >= 0 ? (double)bank[rec].updated_bias[k] : 0.0;
+                g.ba[3 * (size_t)st + k] = rec >= 0 ? (double)bank[rec].updated_bias[3 + k] : 0.0;
+            }
+        }
+        atomicAdd(&s_cnt[code], 1);
+    }
+    __syncthreads();
+    flush_counts(s_cnt, result);
+}
+
+// NormalizeRotation in double: two Newton steps, in registers
+__device__ __forceinline__ void dnormalize(double X[9])
+{
+#pragma unroll
+    for (int step = 0; step < 2; ++step) {
+        double Y[9];
+        const double det = ddet(X);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Y[k] = dmul(0.5, X[k] + dcof(X, k / 3, k % 3) / det);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) X[k] = Y[k];
+    }
+}
+
+__global__ __launch_bounds__(64) void k_fac_oplus(const orbi_graph g, const double *__restrict__ dx, int32_t *__restrict__ iter,
+                                                  int32_t *__restrict__ result)
+{
+    __shared__ int s_cnt[8];
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s < g.n_states) {
+        const int fixed = g.fixed[s];
+        const double *d = dx + 15 * (size_t)s;
+        if (!(fixed & ORBI_FIX_POSE)) {   // CameraImuPose::update
+            double R[9], E[9], N[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) R[k] = g.Rwb[9 * (size_t)s + k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) g.twb[3 * (size_t)s + k] = g.twb[3 * (size_t)s + k] + dsum3(dmul(R[3 * k], d[3]), dmul(R[3 * k + 1], d[4]), dmul(R[3 * k + 2], d[5]));
+            const double x = d[0], y = d[1], z = d[2];
+            const double d2 = dnorm2(x, y, z), dd = sqrt(d2);
+            const bool small = dd < 1e-6;
+            const double s1 = small ? 1.0 : sin(dd) / dd, s2 = small ? 0.5 : (1.0 - cos(dd)) / d2;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) E[k] = (deye(k) + dmul(s1, dhat(x, y, z, k))) + dsww(s2, x, y, z, k / 3, k % 3);
+            dnormalize(E);                  // ExpSO3 returns NormalizeRotation(res)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) N[k] = dm3(R, E, k / 3, k % 3);
+            const int it = iter[s] + 1;
+            if (it == 3) dnormalize(N);
+            iter[s] = it == 3 ? 0 : it;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) g.Rwb[9 * (size_t)s + k] = N[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (!(fixed & ORBI_FIX_VELO)) g.v[3 * (size_t)s + k] = g.v[3 * (size_t)s + k] + d[6 + k];
+            if (!(fixed & ORBI_FIX_GYRO)) g.bg[3 * (size_t)s + k] = g.bg[3 * (size_t)s + k] + d[9 + k];
+            if (!(fixed & ORBI_FIX_ACC)) g.ba[3 * (size_t)s + k] = g.ba[3 * (size_t)s + k] + d[12 + k];
+        }
+        if ((fixed & 15) != 15) atomicAdd(&s_cnt[ORBI_R_DONE], 1);
+    }
+    __syncthreads();
+    flush_counts(s_cnt, result);
+}
+
+__global__ __launch_bounds__(64) void k_fac_recover(const orbi_graph g, const orbi_calib cal, const int32_t *__restrict__ jobs, int n,
+                                                    float *__restrict__ dst, int n_dst, float *__restrict__ bias, double *__restrict__ pose_R,
+                                                    double *__restrict__ pose_t, int32_t *__restrict__ result)
+{
+    __shared__ int s_cnt[8];
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int job = blockIdx.x * 64 + threadIdx.x;
+    if (job < n) {
+        const int st = jobs[3 * job], to = jobs[3 * job + 1], flags = jobs[3 * job + 2];
+        int code = ORBI_R_DONE;
+        if (st < 0 || st >= g.n_states || to < 0 || to >= n_dst) code = ORBI_R_RANGE;
+        else {
+            for (int k = 0; k < job; ++k)
+                if (jobs[3 * k + 1] == to) code = ORBI_R_DUPLICATE;
+        }
+        if (code != ORBI_R_DONE) {
+            for (int k = 0; k < 6; ++k) bias[6 * (size_t)job + k] = 0.f;
+        } else {
+            float *o = dst + 15 * (size_t)to;
+            for (int k = 0; k < 3; ++k) {
+                o[12 + k] = (float)g.v[3 * (size_t)st + k];
+                bias[6 * (size_t)job + k] = (float)g.bg[3 * (size_t)st + k];
+                bias[6 * (size_t)job + 3 + k] = (float)g.ba[3 * (size_t)st + k];
+            }
+            if (flags & ORBI_RECOVER_POSE) {
+                float R[9], t[3], tbw[3];
+#pragma unroll
+                for (int k = 0; k < 9; ++k) o[k] = R[k] = (float)g.Rwb[9 * (size_t)st + k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) o[9 + k] = t[k] = (float)g.twb[3 * (size_t)st + k];
+                if (pose_R) {               // T_cw = T_cb * T_wb.inverse(), k_imu_predict's orders
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) tbw[k] = sum3(mul(-R[k], t[0]), mul(-R[3 + k], t[1]), mul(-R[6 + k], t[2]));
+#pragma unroll
+                    for (int k = 0; k < 9; ++k) {
+                        const int i = k / 3, j = k % 3;
+                        pose_R[9 * (size_t)job + k] = (double)sum3(mul(cal.Rcb[3 * i], R[3 * j]), mul(cal.Rcb[3 * i + 1], R[3 * j + 1]), mul(cal.Rcb[3 * i + 2], R[3 * j + 2]));
+                    }
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        pose_t[3 * (size_t)job + k] = (double)add(sum3(mul(cal.Rcb[3 * k], tbw[0]), mul(cal.Rcb[3 * k + 1], tbw[1]), mul(cal.Rcb[3 * k + 2], tbw[2])), cal.tcb[k]);
+                }
+            }
+        }
+        atomicAdd(&s_cnt[code], 1);
+    }
+    __syncthreads();
+    flush_counts(s_cnt, result);
+}
+
+// ---- orbi_edge_information_device: a wave per edge -------------------------------------------------------------------------------------
+// Gauss-Jordan with partial pivoting on the augmented [C | I] (9 x 18) in the wave's LDS slice; then the two walk blocks by cofactors
+__global__ __launch_bounds__(FAC_T) void k_fac_edge_info(const orbi_record *__restrict__ bank, int cap, const orbi_edge *__restrict__ edges, int n_edges,
+                                                         double *__restrict__ info, double *__restrict__ walk_info, int32_t *__restrict__ result)
+{
+    __shared__ int s_cnt[8];
+    __shared__ double s_m[FAC_WAVES][162 + 18];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int e = blockIdx.x * FAC_WAVES + wave;
+    if (e < n_edges) {
+        double *M = s_m[wave], *Wk = s_m[wave] + 162;
+        const int rec = __builtin_amdgcn_readfirstlane(edges[e].rec), flags = __builtin_amdgcn_readfirstlane(edges[e].flags);
+        int code = ORBI_R_DONE;
+        bool walk_ok[2] = {false, false};
+        if (rec < 0 || rec >= cap) code = ORBI_R_RANGE;
+        else {
+            const float *C = bank[rec].C;
+            for (int x = lane; x < 162; x += 64) {
+                const int r = x / 18, c = x - 18 * r;
+                M[x] = c < 9 ? (double)C[15 * r + c] : (c - 9 == r ? 1.0 : 0.0);
+            }
+            if (lane < 18) Wk[lane] = (double)C[15 * (9 + 3 * (lane / 9) + (lane % 9) / 3) + 9 + 3 * (lane / 9) + lane % 3];
+            WSYNC();
+            for (int k = 0; k < 9; ++k) {
+                int p = k;                       // the first row of the largest |entry| in column k, rows k .. 8: the same in every lane
+                double best = fabs(M[18 * k + k]);
+                for (int r = k + 1; r < 9; ++r) {
+                    const double v = fabs(M[18 * r + k]);
+                    if (v > best) best = v, p = r;
+                }
+                if (!(best > 0.0)) { code = ORBI_R_REFUSED; break; }
+                if (p != k) {
+                    double u = 0.0, v = 0.0;
+                    if (lane < 18) u = M[18 * k + lane], v = M[18 * p + lane];
+                    WSYNC();
+                    if (lane < 18) M[18 * k + lane] = v, M[18 * p + lane] = u;
+                    WSYNC();
+                }
+                const double piv = M[18 * k + k];
+                double val[3];
+#pragma unroll
+                for (int h = 0; h < 3; ++h) {
+                    const int x = lane + 64 * h;
+                    val[h] = 0.0;
+                    if (x < 162) {
+                        const int r = x / 18, c = x - 18 * r;
+                        const double pr = M[18 * k + c] / piv;
+                        val[h] = r == k ? pr : M[x] - dmul(M[18 * r + k], pr);
+                    }
+                }
+                WSYNC();
+#pragma unroll
+                for (int h = 0; h < 3; ++h)
+                    if (lane + 64 * h < 162) M[lane + 64 * h] = val[h];
+                WSYNC();
+            }
+            const double d0 = ddet(Wk), d1 = ddet(Wk + 9);
+            walk_ok[0] = d0 != 0.0, walk_ok[1] = d1 != 0.0;
+            if (code == ORBI_R_DONE && (flags & ORBI_EDGE_WALKS) && !(walk_ok[0] && walk_ok[1])) code = ORBI_R_REFUSED;
+        }
+        for (int x = lane; x < 81; x += 64) {
+            const int r = x / 9, c = x - 9 * r;
+            info[81 * (size_t)e + x] = code == ORBI_R_DONE ? (M[18 * r + 9 + c] + M[18 * c + 9 + r]) / 2.0 : 0.0;
+        }
+        if (lane < 18) {
+            const int b = lane / 9, k = lane - 9 * b;
+            double v = 0.0;
+            if (code == ORBI_R_DONE && (b == 0 ? walk_ok[0] : walk_ok[1])) v = dcof(Wk + 9 * b, k % 3, k / 3) / ddet(Wk + 9 * b);
+            walk_info[18 * (size_t)e + lane] = v;
+        }
+        if (lane == 0) atomicAdd(&s_cnt[code], 1);
+    }
+    __syncthreads();
+    flush_counts(s_cnt, result);
+}
+
+// ---- orbi_linearize_device ---------------------------------------------------------------------------------------------------------------
+struct LinArgs {
+    orbi_graph g;
+    const orbi_record *bank;
+    int cap;
+    float gravity;
+    const orbi_edge *edges;
+    int n_edges;
+    const double *info, *walk_info;
+    const orbi_prior *priors;
+    int n_priors;
+    const orbi_prior_job *pjobs;
+    int n_pjobs;
+    double delta;
+    int mode;
+    double *work, *err, *chi2, *chi2_prior, *total, *H_diag, *H_off, *b, *J;
+    float *flt;
+    int32_t *result;
+};
+
+// the workspace of an edge: H_ii (225), H_jj (225), b_i (15), b_j (15), W_gyro*e_gyro (3), W_acc*e_acc (3), status, Huber weight
+enum { W_HII = 0, W_HJJ = 225, W_B = 450, W_WALK = 480, W_STATUS = 486, W_RHO1 = 487 };
+static_assert(W_RHO1 + 1 == ORBI_EDGE_WORK, "orbi_factors.h states the workspace of an edge");
+enum { ST_OK = 0, ST_RANGE = 1, ST_REFUSED = 3 };   // == ORBI_R_DONE, ORBI_R_RANGE, ORBI_R_REFUSED
+
+// a wave's LDS slice: floats (the record's first 79 floats as orbi_record lays them out, then the float temporaries) and doubles
+enum {
+    F_BIAS = 0, F_DT = 18, F_DR = 19, F_DV = 28, F_DP = 31, F_JRG = 34, F_JVG = 43, F_JVA = 52, F_JPG = 61, F_JPA = 70, F_REC = 79,
+    X_DB = 79, X_TH = 85, X_DVP = 88, X_W = 94, X_E = 103, X_M = 112, X_M2 = 121, X_DRU = 130, X_WORDS = 140
+};
+enum {
+    D_R1 = 0, D_R2 = 9, D_T1 = 18, D_T2 = 21, D_V1 = 24, D_V2 = 27, D_B1 = 30, D_B2 = 36,   // (bg, ba) of state i, of state j
+    D_DR = 42, D_JRG = 51, D_JVG = 60, D_JVA = 69, D_JPG = 78, D_JPA = 87, D_DVP = 96, D_DBG = 102, D_TH = 105,
+    D_A1 = 108, D_RR = 117, D_ER = 126, D_JR = 135, D_INVJ = 144, D_T3 = 153, D_T4 = 162, D_T5 = 171,
+    D_E = 180, D_A = 189, D_C = 192, D_WE = 195, D_J = 204, D_INFO = 474, D_WJ = 555, D_WORDS = 825
+};
+static_assert(offsetof(orbi_record, JPa) == 4 * F_JPA && offsetof(orbi_record, C) == 4 * F_REC && offsetof(orbi_record, delta_t) == 4 * F_DT,
+              "the LDS image is the head of the record");
+
+// entry (r, c) of the raw 9 x 30 Jacobian (G2oTypes.cpp:413-444), columns [dphi1, dt1, dv1, dbg, dba | dphi2, dt2, dv2, -, -]
+__device__ __forceinline__ double jac_entry(const double *S, double dt, int r, int c)
+{
+    const int rb = r / 3, i = r - 3 * rb, cb = c / 3, j = c - 3 * cb;
+    if (rb == 0) {
+        if (cb == 0) return dm3(S + D_T3, S + D_R1, i, j);             // ((-invJr)*R2^T)*R1
+        if (cb == 3) return dm3(S + D_T5, S + D_JRG, i, j);            // (((-invJr)*eR^T)*Jr)*JRg
+        if (cb == 5) return S[D_INVJ + 3 * i + j];
+        return 0.0;
+    }
+    if (rb == 1) {
+        if (cb == 0) return dhat(S[D_A], S[D_A + 1], S[D_A + 2], 3 * i + j);
+        if (cb == 2) return -S[D_R1 + 3 * j + i];                      // -Rb1w
+        if (cb == 3) return -S[D_JVG + 3 * i + j];
+        if (cb == 4) return -S[D_JVA + 3 * i + j];
+        if (cb == 7) return S[D_R1 + 3 * j + i];
+        return 0.0;
+    }
+    if (cb == 0) return dhat(S[D_C], S[D_C + 1], S[D_C + 2], 3 * i + j);
+    if (cb == 1) return i == j ? -1.0 : -0.0;                          // -Identity
+    if (cb == 2) return dmul(-S[D_R1 + 3 * j + i], dt);                // (-Rb1w)*dt
+    if (cb == 3) return -S[D_JPG + 3 * i + j];
+    if (cb == 4) return -S[D_JPA + 3 * i + j];
+    if (cb == 6) return S[D_RR + 3 * i + j];                           // Rb1w*R2
+    return 0.0;
+}
+
+__device__ __forceinline__ bool dof_fixed(int fixed, int dof) { return (fixed >> (dof < 6 ? 0 : dof / 3 - 1)) & 1; }
+
+__global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
+{
+    __shared__ __attribute__((aligned(16))) double s_d[FAC_WAVES][D_WORDS];
+    __shared__ float s_f[FAC_WAVES][X_WORDS];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int e = blockIdx.x * FAC_WAVES + wave;
+    if (e >= a.n_edges) return;                      // no workgroup barrier in this kernel
+    double *S = s_d[wave];
+    float *F = s_f[wave];
+    double *work = a.work + (size_t)ORBI_EDGE_WORK * e;
+    const int si = __builtin_amdgcn_readfirstlane(a.edges[e].i), sj = __builtin_amdgcn_readfirstlane(a.edges[e].j);
+    const int rec = __builtin_amdgcn_readfirstlane(a.edges[e].rec), flags = __builtin_amdgcn_readfirstlane(a.edges[e].flags);
+    const int g = lane / 9, q = lane - 9 * g, i = q / 3, j = q - 3 * i;
+    int status = ST_OK;
+    if (si < 0 || si >= a.g.n_states || sj < 0 || sj >= a.g.n_states || si == sj || rec < 0 || rec >= a.cap) status = ST_RANGE;
+    else if (a.info[81 * (size_t)e] == 0.0) status = ST_REFUSED;   // what orbi_edge_information_device leaves for a refused edge
+    if (status != ST_OK) {
+        if (lane < 9) a.err[9 * (size_t)e + lane] = 0.0;
+        if (lane < 3) a.chi2[3 * (size_t)e + lane] = 0.0;
+        if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = 0.f;
+        if (a.mode == 0) {
+            for (int x = lane; x < 225; x += 64) a.H_off[225 * (size_t)e + x] = 0.0;
+            if (a.J)
+                for (int x = lane; x < 270; x += 64) a.J[270 * (size_t)e + x] = 0.0;
+        }
+        if (lane == 0) work[W_STATUS] = (double)status;
+        return;
+    }
+    // ---- load: the head of the record, the vertices of both states, the information
+    const float *recf = (const float *)(a.bank + rec);
+    for (int k = lane; k < F_REC; k += 64) F[k] = recf[k];
+    if (lane < 9) S[D_R1 + lane] = a.g.Rwb[9 * (size_t)si + lane];
+    else if (lane < 18) S[D_R2 + lane - 9] = a.g.Rwb[9 * (size_t)sj + lane - 9];
+    else if (lane < 21) S[D_T1 + lane - 18] = a.g.twb[3 * (size_t)si + lane - 18];
+    else if (lane < 24) S[D_T2 + lane - 21] = a.g.twb[3 * (size_t)sj + lane - 21];
+    else if (lane < 27) S[D_V1 + lane - 24] = a.g.v[3 * (size_t)si + lane - 24];
+    else if (lane < 30) S[D_V2 + lane - 27] = a.g.v[3 * (size_t)sj + lane - 27];
+    else if (lane < 33) S[D_B1 + lane - 30] = a.g.bg[3 * (size_t)si + lane - 30];
+    else if (lane < 36) S[D_B1 + lane - 30] = a.g.ba[3 * (size_t)si + lane - 33];
+    else if (lane < 39) S[D_B2 + lane - 36] = a.g.bg[3 * (size_t)sj + lane - 36];
+    else if (lane < 42) S[D_B2 + lane - 36] = a.g.ba[3 * (size_t)sj + lane - 39];
+    for (int x = lane; x < 81; x += 64) S[D_INFO + x] = a.info[81 * (size_t)e + x];
+    const int fix_i = a.g.fixed[si], fix_j = a.g.fixed[sj];
+    WSYNC();
+    // ---- the float part: the bias vertices cast to float, getDeltaRotation / Velocity / Position (Imu.cpp:182-192)
+    if (lane < 6) F[X_DB + lane] = sub((float)S[D_B1 + lane], F[F_BIAS + lane]);
+    WSYNC();
+    if (lane < 3) F[X_TH + lane] = mv3(F + F_JRG, F + X_DB, lane);
+    else if (lane < 6) F[X_DVP + lane - 3] = add(add(F[F_DV + lane - 3], mv3(F + F_JVG, F + X_DB, lane - 3)), mv3(F + F_JVA, F + X_DB + 3, lane - 3));
+    else if (lane < 9) F[X_DVP + lane - 3] = add(add(F[F_DP + lane - 6], mv3(F + F_JPG, F + X_DB, lane - 6)), mv3(F + F_JPA, F + X_DB + 3, lane - 6));
+    WSYNC();
+    {
+        const float tx = F[X_TH], ty = F[X_TH + 1], tz = F[X_TH + 2];
+        const So3 so = so3_scalars(tx, ty, tz);
+        if (g == 0) F[X_W + q] = hat(tx, ty, tz, q);
+        WSYNC();
+        if (g == 0) F[X_E + q] = exp_entry(so, F + X_W, q);
+        WSYNC();
+        if (g == 0) F[X_M + q] = m3(F + F_DR, F + X_E, i, j);
+        WSYNC();
+        if (g == 0) F[X_M2 + q] = newton_entry(F + X_M, i, j);
+        WSYNC();
+        if (g == 0) F[X_DRU + q] = newton_entry(F + X_M2, i, j);
+        WSYNC();
+    }
+    if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = lane < 9 ? F[X_DRU + lane] : F[X_DVP + lane - 9];
+    // ---- everything behind the cast to double
+    const double dt = (double)F[F_DT], G = (double)a.gravity;
+    if (g == 0) S[D_DR + q] = (double)F[X_DRU + q];
+    else if (g < 6) S[D_JRG + 9 * (g - 1) + q] = (double)F[F_JRG + 9 * (g - 1) + q];
+    else if (g == 6 && q < 6) S[D_DVP + q] = (double)F[X_DVP + q];
+    else if (g == 6) S[D_DBG + q - 6] = (double)F[X_DB + q - 6];
+    WSYNC();
+    if (g == 0) S[D_A1 + q] = dm3tt(S + D_DR, S + D_R1, i, j);                    // dR^T * Rb1w
+    else if (g == 1) S[D_RR + q] = dm3t(S + D_R1, S + D_R2, i, j);                // Rb1w * R2
+    else if (g == 2 && q < 3) {                                                   // Rb1w*(v2 - v1 - g*dt) and ev
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = (S[D_V2 + k] - S[D_V1 + k]) - dmul(k == 2 ? -G : 0.0, dt);
+        const double v = dmv3t(S + D_R1, d[0], d[1], d[2], q);
+        S[D_A + q] = v, S[D_E + 3 + q] = v - S[D_DVP + q];
+    } else if (g == 3 && q < 3) {                                                 // Rb1w*(t2 - t1 - v1*dt - 0.5*g*dt*dt) and ep
+        double d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) d[k] = ((S[D_T2 + k] - S[D_T1 + k]) - dmul(S[D_V1 + k], dt)) - dmul(dmul(dmul(0.5, k == 2 ? -G : 0.0), dt), dt);
+        const double v = dmv3t(S + D_R1, d[0], d[1], d[2], q);
+        S[D_C + q] = v, S[D_E + 6 + q] = v - S[D_DVP + 3 + q];
+    } else if (g == 4 && q < 3) S[D_TH + q] = dsum3(dmul(S[D_JRG + 3 * q], S[D_DBG]), dmul(S[D_JRG + 3 * q + 1], S[D_DBG + 1]), dmul(S[D_JRG + 3 * q + 2], S[D_DBG + 2]));
+    WSYNC();
+    if (g == 0) S[D_ER + q] = dm3(S + D_A1, S + D_R2, i, j);                      // eR
+    else if (g == 1) {                                                            // RightJacobianSO3(JRg * delta_bg)
+        const double x = S[D_TH], y = S[D_TH + 1], z = S[D_TH + 2];
+        const double d2 = dnorm2(x, y, z), d = sqrt(d2);
+        double v = deye(q);
+        if (!(d < 1e-6)) v = (deye(q) - dmul((1.0 - cos(d)) / d2, dhat(x, y, z, q))) + dsww((d - sin(d)) / dmul(d2, d), x, y, z, i, j);
+        S[D_JR + q] = v;
+    }
+    WSYNC();
+    {   // LogSO3(eR) and InverseRightJacobianSO3(er), the scalars in every lane
+        const double *R = S + D_ER;
+        const double tr = (R[0] + R[4]) + R[8];
+        double er0 = 0.0, er1 = 0.0, er2 = 0.0;
+        if (tr != 3.0) {
+            const double w0 = dmul(0.5, R[7] - R[5]), w1 = dmul(0.5, R[2] - R[6]), w2 = dmul(0.5, R[3] - R[1]);
+            const double sn = sqrt(dnorm2(w0, w1, w2)), cs = dmul(0.5, tr - 1.0);
+            const double th = atan2(sn, cs);
+            if (fabs(th) < 1e-6) er0 = w0, er1 = w1, er2 = w2;
+            else er0 = dmul(th, w0) / sn, er1 = dmul(th, w1) / sn, er2 = dmul(th, w2) / sn;
+        }
+        const double d2 = dnorm2(er0, er1, er2), d = sqrt(d2);
+        if (g == 0) {
+            double v = deye(q);
+            if (!(d < 1e-6)) {
+                const double coef = 1.0 / d2 - (1.0 + cos(d)) / dmul(dmul(2.0, d), sin(d));
+                v = (deye(q) + dhat(er0, er1, er2, q) / 2.0) + dsww(coef, er0, er1, er2, i, j);
+            }
+            S[D_INVJ + q] = v;
+        } else if (g == 1 && q < 3) S[D_E + q] = q == 0 ? er0 : q == 1 ? er1 : er2;
+    }
+    WSYNC();
+    if (g == 0) S[D_T3 + q] = dm3nt(S + D_INVJ, S + D_R2, i, j);                  // (-invJr) * R2^T
+    else if (g == 1) S[D_T4 + q] = dm3nt(S + D_INVJ, S + D_ER, i, j);             // (-invJr) * eR^T
+    else if (g == 2) {                                                            // Omega * e
+        double s = 0.0;
+        for (int k = 0; k < 9; ++k) s = s + dmul(S[D_INFO + 9 * q + k], S[D_E + k]);
+        S[D_WE + q] = s;
+    }
+    WSYNC();
+    if (g == 0) S[D_T5 + q] = dm3(S + D_T4, S + D_JR, i, j);
+    WSYNC();
+    // ---- chi2, the Huber kernel (g2o's RobustKernelHuber), the walks
+    double chi = 0.0;
+    for (int k = 0; k < 9; ++k) chi = chi + dmul(S[D_E + k], S[D_WE + k]);
+    double rho1 = 1.0;
+    if (a.delta > 0.0 && chi > dmul(a.delta, a.delta)) rho1 = a.delta / sqrt(chi);
+    double we[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, wchi[2] = {0.0, 0.0};
+    if (flags & ORBI_EDGE_WALKS) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const double *W = a.walk_info + 18 * (size_t)e + 9 * b;
+            const double e0 = S[D_B2 + 3 * b] - S[D_B1 + 3 * b], e1 = S[D_B2 + 3 * b + 1] - S[D_B1 + 3 * b + 1], e2 = S[D_B2 + 3 * b + 2] - S[D_B1 + 3 * b + 2];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) we[b][k] = dsum3(dmul(W[3 * k], e0), dmul(W[3 * k + 1], e1), dmul(W[3 * k + 2], e2));
+            wchi[b] = dsum3(dmul(e0, we[b][0]), dmul(e1, we[b][1]), dmul(e2, we[b][2]));
+        }
+    }
+    if (lane < 9) a.err[9 * (size_t)e + lane] = S[D_E + lane];
+    if (lane < 3) a.chi2[3 * (size_t)e + lane] = lane == 0 ? chi : lane == 1 ? wchi[0] : wchi[1];
+    if (lane == 0) work[W_STATUS] = (double)ST_OK, work[W_RHO1] = rho1;
+    if (lane < 6) work[W_WALK + lane] = lane == 0 ? we[0][0] : lane == 1 ? we[0][1] : lane == 2 ? we[0][2] : lane == 3 ? we[1][0] : lane == 4 ? we[1][1] : we[1][2];
+    if (a.mode != 0) return;
+    // ---- the Jacobian: raw to d_J, with the columns of fixed dof zeroed to LDS
+#pragma unroll
+    for (int h = 0; h < 5; ++h) {
+        const int x = lane + 64 * h;
+        if (x < 270) {
+            const int r = x / 30, c = x - 30 * r;
+            const double v = jac_entry(S, dt, r, c);
+            if (a.J) a.J[270 * (size_t)e + x] = v;
+            S[D_J + x] = dof_fixed(c < 15 ? fix_i : fix_j, c < 15 ? c : c - 15) ? 0.0 : v;
+        }
+    }
+    WSYNC();
+    // W*J with W = rho1 * Omega
+#pragma unroll
+    for (int h = 0; h < 5; ++h) {
+        const int x = lane + 64 * h;
+        if (x < 270) {
+            const int r = x / 30, c = x - 30 * r;
+            double s = 0.0;
+            for (int k = 0; k < 9; ++k) s = s + dmul(S[D_INFO + 9 * r + k], S[D_J + 30 * k + c]);
+            S[D_WJ + x] = dmul(rho1, s);
+        }
+    }
+    WSYNC();
+    // J^T*(W*J): H_ii and H_jj to the workspace, H_ij (with the walks' -W) to d_H_off; b = -J^T*(W*e)
+    for (int x = lane; x < 675; x += 64) {
+        const int blk = x / 225, y = x - 225 * blk, r = y / 15, c = y - 15 * r;
+        const int ca = (blk == 1 ? 15 : 0) + r, cb = (blk == 0 ? 0 : 15) + c;
+        double s = 0.0;
+        for (int k = 0; k < 9; ++k) s = s + dmul(S[D_J + 30 * k + ca], S[D_WJ + 30 * k + cb]);
+        if (blk == 2) {
+            if ((flags & ORBI_EDGE_WALKS) && r >= 9 && c >= 9 && r / 3 == c / 3 && !dof_fixed(fix_i, r) && !dof_fixed(fix_j, c))
+                s = s - a.walk_info[18 * (size_t)e + 9 * (r / 3 - 3) + 3 * (r % 3) + c % 3];
+            a.H_off[225 * (size_t)e + y] = s;
+        } else work[225 * blk + y] = s;
+    }
+    if (lane < 30) {
+        double s = 0.0;
+        for (int k = 0; k < 9; ++k) s = s + dmul(S[D_J + 30 * k + lane], dmul(rho1, S[D_WE + k]));
+        work[W_B + lane] = -s;
+    }
+}
+
+// mode 0: waves [0, n_states) gather a state each; the last wave (the only one of mode 1) does the priors' chi2, the totals, d_result
+__global__ __launch_bounds__(FAC_T) void k_fac_gather(const LinArgs a)
+{
+    __shared__ int s_cnt[8];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_gather = a.mode == 0 ? a.g.n_states : 0;
+    const int s = blockIdx.x * FAC_WAVES + wave;
+    if (s < n_gather) {
+        const int fixed = a.g.fixed[s];
+        double h[4] = {0.0, 0.0, 0.0, 0.0}, bb = 0.0;       // entries lane + 64k of the 15 x 15 block; entry `lane` of b
+        int hr[4], hc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hr[k] = (lane + 64 * k) / 15, hc[k] = (lane + 64 * k) % 15;
+        for (int c0 = 0; c0 < a.n_edges; c0 += 64) {
+            const int e = c0 + lane;
+            int side = 0;                                     // 1: this state is the edge's i, 2: its j
+            if (e < a.n_edges && a.work[(size_t)ORBI_EDGE_WORK * e + W_STATUS] == (double)ST_OK) side = a.edges[e].i == s ? 1 : a.edges[e].j == s ? 2 : 0;
+            unsigned long long mi = __ballot(side == 1), mj = __ballot(side == 2), m = mi | mj;
+            while (m) {
+                const int bit = __builtin_ctzll(m);
+                m &= m - 1;
+                const int ee = c0 + bit;
+                const bool first = (mi >> bit) & 1;
+                const double *w = a.work + (size_t)ORBI_EDGE_WORK * ee;
+                const int fl = a.edges[ee].flags;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (lane + 64 * k < 225) h[k] = h[k] + w[(first ? W_HII : W_HJJ) + lane + 64 * k];
+                if (lane < 15) bb = bb + w[W_B + (first ? 0 : 15) + lane];
+                if (fl & ORBI_EDGE_WALKS) {                   // J = -I (first) / +I: H += W, b -= J^T * (W*e)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (lane + 64 * k < 225 && hr[k] >= 9 && hc[k] >= 9 && hr[k] / 3 == hc[k] / 3 && !dof_fixed(fixed, hr[k]))
+                            h[k] = h[k] + a.walk_info[18 * (size_t)ee + 9 * (hr[k] / 3 - 3) + 3 * (hr[k] % 3) + hc[k] % 3];
+                    if (lane >= 9 && lane < 15 && !dof_fixed(fixed, lane)) bb = first ? bb + w[W_WALK + lane - 9] : bb - w[W_WALK + lane - 9];
+                }
+            }
+        }
+        for (int c0 = 0; c0 < a.n_pjobs; c0 += 64) {
+            const int p = c0 + lane;
+            bool hit = false;
+            if (p < a.n_pjobs) hit = a.pjobs[p].state == s && a.pjobs[p].prior >= 0 && a.pjobs[p].prior < a.n_priors;
+            unsigned long long m = __ballot(hit);
+            while (m) {
+                const int bit = __builtin_ctzll(m);
+                m &= m - 1;
+                const orbi_prior_job pj = a.pjobs[c0 + bit];
+                const orbi_prior *pr = a.priors + pj.prior;
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {                 // velocity, gyro, acc: e = priori - estimate, J = -I
+                    if (!((pj.mask >> v) & 1) || ((fixed >> (v + 1)) & 1)) continue;
+                    const float *Om = v == 0 ? pr->velo_info : (v == 1 || (pj.mask & ORBI_PRIOR_ACC_GYRO_INFO)) ? pr->gyro_info : pr->acc_info;
+                    const float *me = v == 0 ? pr->velo_priori : pr->bias_priori + 3 * (v - 1);
+                    const double *est = (v == 0 ? a.g.v : v == 1 ? a.g.bg : a.g.ba) + 3 * (size_t)s;
+                    const int base = 6 + 3 * v;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+                        if (lane + 64 * k < 225 && hr[k] >= base && hr[k] < base + 3 && hc[k] >= base && hc[k] < base + 3)
+                            h[k] = h[k] + (double)Om[3 * (hr[k] - base) + hc[k] - base];
+                    if (lane >= base && lane < base + 3) {
+                        const int r = lane - base;
+                        bb = bb + dsum3(dmul((double)Om[3 * r], (double)me[0] - est[0]), dmul((double)Om[3 * r + 1], (double)me[1] - est[1]),
+                                        dmul((double)Om[3 * r + 2], (double)me[2] - est[2]));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (lane + 64 * k < 225) a.H_diag[225 * (size_t)s + lane + 64 * k] = h[k];
+        if (lane < 15) a.b[15 * (size_t)s + lane] = bb;
+    }
+    if (s != n_gather) return;                                // uniform per wave; the tail wave alone uses s_cnt
+    if (lane < 8) s_cnt[lane] = 0;
+    WSYNC();
+    for (int p = lane; p < a.n_pjobs; p += 64) {
+        const orbi_prior_job pj = a.pjobs[p];
+        double c[3] = {0.0, 0.0, 0.0};
+        const bool ok = pj.state >= 0 && pj.state < a.g.n_states && pj.prior >= 0 && pj.prior < a.n_priors;
+        if (ok) {
+            const orbi_prior *pr = a.priors + pj.prior;
+#pragma unroll
+            for (int v = 0; v < 3; ++v) {
+                if (!((pj.mask >> v) & 1)) continue;
+                const float *Om = v == 0 ? pr->velo_info : (v == 1 || (pj.mask & ORBI_PRIOR_ACC_GYRO_INFO)) ? pr->gyro_info : pr->acc_info;
+                const float *me = v == 0 ? pr->velo_priori : pr->bias_priori + 3 * (v - 1);
+                const double *est = (v == 0 ? a.g.v : v == 1 ? a.g.bg : a.g.ba) + 3 * (size_t)pj.state;
+                const double e0 = (double)me[0] - est[0], e1 = (double)me[1] - est[1], e2 = (double)me[2] - est[2];
+                double we[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) we[k] = dsum3(dmul((double)Om[3 * k], e0), dmul((double)Om[3 * k + 1], e1), dmul((double)Om[3 * k + 2], e2));
+                c[v] = dsum3(dmul(e0, we[0]), dmul(e1, we[1]), dmul(e2, we[2]));
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < 3; ++v) a.chi2_prior[3 * (size_t)p + v] = c[v];
+        atomicAdd(&s_cnt[ok ? ORBI_R_PRIOR_DONE : ORBI_R_PRIOR_RANGE], 1);
+    }
+    for (int e = lane; e < a.n_edges; e += 64) atomicAdd(&s_cnt[(int)a.work[(size_t)ORBI_EDGE_WORK * e + W_STATUS]], 1);
+    __threadfence();                                          // lane 0 reads what the other lanes wrote to d_chi2_prior
+    WSYNC();
+    if (lane < 8) a.result[lane] = s_cnt[lane];
+    if (lane == 0) {                                          // the totals in their one order
+        double plain = 0.0, robust = 0.0;
+        const double dsqr = dmul(a.delta, a.delta);
+        for (int e = 0; e < a.n_edges; ++e) {
+            const double c0 = a.chi2[3 * (size_t)e], c1 = a.chi2[3 * (size_t)e + 1], c2 = a.chi2[3 * (size_t)e + 2];
+            const double r0 = (a.delta > 0.0 && c0 > dsqr) ? dmul(dmul(2.0, sqrt(c0)), a.delta) - dsqr : c0;
+            plain = ((plain + c0) + c1) + c2;
+            robust = ((robust + r0) + c1) + c2;
+        }
+        for (int p = 0; p < a.n_pjobs; ++p)
+            for (int v = 0; v < 3; ++v) {
+                const double c = a.chi2_prior[3 * (size_t)p + v];
+                plain = plain + c, robust = robust + c;
+            }
+        a.total[0] = plain, a.total[1] = robust;
+    }
+}
+
+int check_graph(const orbi_graph &g, const void *result)
+{
+    if (!g.Rwb || !g.twb || !g.v || !g.bg || !g.ba || !g.fixed || g.n_states < 0 || !result)
+        return orbx_set_error(ORBX_E_ARG, "null graph array or result, or a negative state count");
+    if (g.n_states > ORBI_MAX_JOBS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBI_MAX_JOBS (4096) states");
+    return ORBX_OK;
+}
+
+int check_jobs(const void *jobs, int n, const void *result)
+{
+    if (!jobs || n < 0 || !result) return orbx_set_error(ORBX_E_ARG, "null job list or result, or a negative job count");
+    if (n > ORBI_MAX_JOBS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBI_MAX_JOBS (4096) jobs in one call");
+    return ORBX_OK;
+}
+
+// launches `grid` workgroups of a kernel that ends in flush_counts; eight zeros first unless exactly one workgroup writes them
+#define LAUNCH_COUNTED(kernel, grid, threads, s, result, ...)                                           \
+    do {                                                                                                \
+        if ((grid) != 1) hipLaunchKernelGGL(k_fac_clear, dim3(1), dim3(64), 0, s, result);              \
+        if ((grid) > 0) hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, __VA_ARGS__);       \
+        ORB_TRY(hipGetLastError());                                                                     \
+    } while (0)
+
+} // namespace
+
+extern "C" int orbi_prior_information_device(orbi_prior *d_priors, int n_priors, const orbi_record *d_bank, int cap, const float *d_src, int n_src,
+                                             const int32_t *d_jobs, int n, int32_t *d_result, void *stream)
+{
+    if (int rc = check_jobs(d_jobs, n, d_result)) return rc;
+    if (!d_priors || n_priors < 1 || !d_bank || cap < 1 || n_src < 0) return orbx_set_error(ORBX_E_ARG, "null priors or bank, n_priors or cap < 1, or a negative n_src");
+    if (int rc = orb_need_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (n + 63) / 64;
+    LAUNCH_COUNTED(k_fac_prior_info, grid, 64, s, d_result, d_priors, n_priors, d_bank, cap, d_src, n_src, d_jobs, n, d_result);
+    return ORBX_OK;
+}
+
+extern "C" int orbi_graph_init_device(orbi_graph graph, const orbi_record *d_bank, int cap, const float *d_src, int n_src, const int32_t *d_jobs, int n,
+                                      int32_t *d_result, void *stream)
+{
+    if (int rc = check_graph(graph, d_result)) return rc;
+    if (int rc = check_jobs(d_jobs, n, d_result)) return rc;
+    if (!d_bank || cap < 1 || !d_src || n_src < 1) return orbx_set_error(ORBX_E_ARG, "null bank or source states, or cap or n_src < 1");
+    if (int rc = orb_need_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (n + 63) / 64;
+    LAUNCH_COUNTED(k_fac_init, grid, 64, s, d_result, graph, d_bank, cap, d_src, n_src, d_jobs, n, d_result);
+    return ORBX_OK;
+}
+
+extern "C" int orbi_edge_information_device(const orbi_record *d_bank, int cap, const orbi_edge *d_edges, int n_edges, double *d_info,
+                                            double *d_walk_info, int32_t *d_result, void *stream)
+{
+    if (int rc = check_jobs(d_edges, n_edges, d_result)) return rc;
+    if (!d_bank || cap < 1 || !d_info || !d_walk_info) return orbx_set_error(ORBX_E_ARG, "null bank, d_info or d_walk_info, or cap < 1");
+    if (int rc = orb_need_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (n_edges + FAC_WAVES - 1) / FAC_WAVES;
+    LAUNCH_COUNTED(k_fac_edge_info, grid, FAC_T, s, d_result, d_bank, cap, d_edges, n_edges, d_info, d_walk_info, d_result);
+    return ORBX_OK;
+}
+
+extern "C" int orbi_linearize_device(orbi_graph graph, const orbi_record *d_bank, int cap, float gravity, const orbi_edge *d_edges, int n_edges,
+                                     const double *d_info, const double *d_walk_info, const orbi_prior *d_priors, int n_priors,
+                                     const orbi_prior_job *d_prior_jobs, int n_prior_jobs, double huber_delta, int mode, double *d_work,
+                                     double *d_err, double *d_chi2, double *d_chi2_prior, double *d_total, double *d_H_diag, double *d_H_off,
+                                     double *d_b, double *d_J, float *d_float, int32_t *d_result, void *stream)
+{
+    if (int rc = check_graph(graph, d_result)) return rc;
+    if (int rc = check_jobs(d_edges, n_edges, d_result)) return rc;
+    if (n_prior_jobs < 0 || n_priors < 0 || (n_prior_jobs > 0 && (!d_prior_jobs || !d_priors || !d_chi2_prior)))
+        return orbx_set_error(ORBX_E_ARG, "prior jobs without their list, the priors or d_chi2_prior, or a negative count");
+    if (n_prior_jobs > ORBI_MAX_JOBS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBI_MAX_JOBS (4096) prior jobs in one call");
+    if (!d_bank || cap < 1 || !d_info || !d_walk_info || !d_work || !d_err || !d_chi2 || !d_total || !(huber_delta == huber_delta))
+        return orbx_set_error(ORBX_E_ARG, "null bank, information, workspace or output, cap < 1, or huber_delta is not a number");
+    if (mode != 0 && mode != 1) return orbx_set_error(ORBX_E_ARG, "mode is 0 (linearise) or 1 (computeError only)");
+    if (mode == 0 && (!d_H_diag || !d_H_off || !d_b)) return orbx_set_error(ORBX_E_ARG, "mode 0 needs d_H_diag, d_H_off and d_b");
+    if (int rc = orb_need_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    LinArgs a = {};
+    a.g = graph, a.bank = d_bank, a.cap = cap, a.gravity = gravity, a.edges = d_edges, a.n_edges = n_edges, a.info = d_info, a.walk_info = d_walk_info;
+    a.priors = d_priors, a.n_priors = n_priors, a.pjobs = d_prior_jobs, a.n_pjobs = n_prior_jobs, a.delta = huber_delta, a.mode = mode;
+    a.work = d_work, a.err = d_err, a.chi2 = d_chi2, a.chi2_prior = d_chi2_prior, a.total = d_total, a.H_diag = d_H_diag, a.H_off = d_H_off;
+    a.b = d_b, a.J = mode == 0 ? d_J : nullptr, a.flt = d_float, a.result = d_result;
+    if (n_edges > 0) hipLaunchKernelGGL(k_fac_edge, dim3((n_edges + FAC_WAVES - 1) / FAC_WAVES), dim3(FAC_T), 0, s, a);
+    const int waves = (mode == 0 ? graph.n_states : 0) + 1;
+    hipLaunchKernelGGL(k_fac_gather, dim3((waves + FAC_WAVES - 1) / FAC_WAVES), dim3(FAC_T), 0, s, a);
+    ORB_TRY(hipGetLastError());
+    return ORBX_OK;
+}
+
+extern "C" int orbi_graph_oplus_device(orbi_graph graph, const double *d_dx, int32_t *d_iter, int32_t *d_result, void *stream)
+{
+    if (int rc = check_graph(graph, d_result)) return rc;
+    if (!d_dx || !d_iter) return orbx_set_error(ORBX_E_ARG, "null d_dx or d_iter");
+    if (int rc = orb_need_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (graph.n_states + 63) / 64;
+    LAUNCH_COUNTED(k_fac_oplus, grid, 64, s, d_result, graph, d_dx, d_iter, d_result);
+    return ORBX_OK;
+}
+
+extern "C" int orbi_graph_recover_device(orbi_graph graph, orbi_calib calib, const int32_t *d_jobs, int n, float *d_dst, int n_dst, float *d_bias,
+                                         double *d_pose_R, double *d_pose_t, int32_t *d_result, void *stream)
+{
+    if (int rc = check_graph(graph, d_result)) return rc;
+    if (int rc = check_jobs(d_jobs, n, d_result)) return rc;
+    if (!d_dst || n_dst < 1 || !d_bias) return orbx_set_error(ORBX_E_ARG, "null destination or bias array, or n_dst < 1");
+    if (!d_pose_R != !d_pose_t) return orbx_set_error(ORBX_E_ARG, "d_pose_R and d_pose_t go together");
+    if (int rc = orb_need_device()) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (n + 63) / 64;
+    LAUNCH_COUNTED(k_fac_recover, grid, 64, s, d_result, graph, calib, d_jobs, n, d_dst, n_dst, d_bias, d_pose_R, d_pose_t, d_result);
+    return ORBX_OK;
+}
