@@ -18,9 +18,16 @@
  * on the Tracking thread (Tracking.cpp:273-358) while localBundleAdjustment runs on LocalMapping's (LocalMapping.cpp:45-52): every
  * host-pointer call leases a non-blocking stream, a device arena and a page-locked staging block from a per-device pool for its
  * duration -- one copy up, one copy down, one small read-back per LM trial; no stream-0 operation, no allocation in steady state.
+ * orbba_local_bundle_adjustment included: both of its rounds run in one arena between the one copy up and the one copy down.
+ * Checks: a host-pointer call checks its arguments AND the content of its problem -- "edge index out of range", "edges must be grouped
+ * by point", and for the LM entry points "every pose is fixed" and "a point is observed twice by the same key frame"; the edges are
+ * walked in edge order and the first offending edge decides -- before it looks for a device: a malformed problem is ORBX_E_ARG with or
+ * without one, and ORBX_E_NO_DEVICE means the arguments were fine.  ORBX_E_UNSUPPORTED (free poses x points above 2^28) comes behind
+ * every argument error and before the device as well.
  * The _device entry points take device pointers and enqueue on the caller's stream without a copy or a wait -- with ONE stated
  * exception, orbba_local_bundle_adjustment_device: the LM loop's accept / reject decision is the host's, so that call waits on the
- * caller's stream for one small read-back per trial (and leases the pool's arena and staging block, not its stream).
+ * caller's stream for one small read-back per trial (and leases the pool's arena and staging block, not its stream; the arena goes
+ * back to the pool behind a wait on the caller's stream, on an error return as well).
  */
 #ifndef ORBBA_H
 #define ORBBA_H
@@ -100,7 +107,8 @@ int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o, orbba_lm_r
 /* Optimize.cpp:892-922: optimize(5) with Huber; edges with chi2 > 5.991 go to level 1 and the kernel is dropped;
  * optimize(10); outlier[e] = 1 for every edge demoted after the first round (its stale e->chi2() stays above 5.991, see
  * orbba_lm_result.chi2) and for every still-active edge whose chi2 at the final estimate exceeds 5.991 -- the
- * observations the reference then erases (:917-935).  outlier may be NULL. */
+ * observations the reference then erases (:917-935).  outlier may be NULL, and so may each array of *r.  The problem goes up once
+ * and the results come down once; device_ms spans both rounds. */
 int orbba_local_bundle_adjustment(const orbba_problem *p, orbba_lm_result *r, uint8_t *outlier, int device);
 
 /* The same for a caller whose problem lies in DEVICE memory -- orbm_local_ba_problem_device (orbm.h) assembles one from the

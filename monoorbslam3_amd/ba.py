@@ -13,11 +13,8 @@ from . import _lib
 
 def set_variant(name, value):
     """orbba_set_variant (per process): "chol" = "lds" | "global", "pose_lds" = edges of a frame staged in LDS (0 .. 3000)."""
-    L = _lib.lib()
-    L.orbba_set_variant.restype = C.c_int
-    L.orbba_set_variant.argtypes = [C.c_int, C.c_int]
     which = {"chol": 0, "pose_lds": 1}[name]
-    _lib.check(L.orbba_set_variant(which, int({"lds": 0, "global": 1}.get(value, value))))
+    _lib.check(_L().orbba_set_variant(which, int({"lds": 0, "global": 1}.get(value, value))))
 
 
 class _Problem(C.Structure):
@@ -47,10 +44,7 @@ HUBER_MONO = float(np.sqrt(np.float32(5.991)))  # thHuberMono = sqrtf(5.991) (Op
 def linearize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2,
               huber_delta=HUBER_MONO, device=-1):
     """Returns dict(chi2, error, H_pp, b_p, H_ll, b_l, H_lp, kernel_ms)."""
-    L = _lib.lib()
-    fn = L.orbba_linearize
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(_Problem), C.POINTER(_Result), C.c_int]
+    fn = _L().orbba_linearize
     f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     R, t, P = f8(pose_R).reshape(-1, 9), f8(pose_t).reshape(-1, 3), f8(points).reshape(-1, 3)
     fix = np.ascontiguousarray(pose_fixed, dtype=np.uint8)
@@ -111,10 +105,7 @@ def optimize(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edg
              good_step_upper=0.0, user_lambda_init=0.0):
     """optimizer.optimize(iterations) of Optimize::localBundleAdjustment's graph (Optimize.cpp:811-893) on the GPU.  max_trials, tau,
     good_step_lower / _upper and user_lambda_init are orbba_lm_options' fields of those names: 0 takes g2o's default."""
-    L = _lib.lib()
-    fn = L.orbba_optimize
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(_Problem), C.POINTER(_LmOptions), C.POINTER(_LmResult), C.c_int]
+    fn = _L().orbba_optimize
     prob, keep = _problem(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2, huber_delta)
     opt = _LmOptions(max_iterations=iterations, max_trials=max_trials, tau=tau, good_step_lower=good_step_lower,
                      good_step_upper=good_step_upper, user_lambda_init=user_lambda_init)
@@ -130,10 +121,7 @@ def local_bundle_adjustment(cam, pose_R, pose_t, pose_fixed, points, edge_pose, 
                             huber_delta=HUBER_MONO, device=-1):
     """Optimize.cpp:892-922: optimize(5) with Huber, drop the chi2 > 5.991 edges and the kernel, optimize(10); the
     returned dict also holds `outlier` (the observations the reference erases at :924-935)."""
-    L = _lib.lib()
-    fn = L.orbba_local_bundle_adjustment
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(_Problem), C.POINTER(_LmResult), C.c_void_p, C.c_int]
+    fn = _L().orbba_local_bundle_adjustment
     prob, keep = _problem(cam, pose_R, pose_t, pose_fixed, points, edge_pose, edge_point, edge_z, edge_inv_sigma2, huber_delta)
     out, res = _lm_out(prob)
     outlier = np.zeros(prob.n_edges, np.uint8)
@@ -149,10 +137,7 @@ def local_bundle_adjustment_device(cam, d, n_poses, n_points, n_edges, huber_del
     outlier u8 [n_edges].  The three sizes are host ints (the assembly's result[0:3], read back once).  Runs on `stream` (torch's
     current stream when None) and WAITS on it, once per LM trial.  Returns dict(iterations, trials, lam, chi2_initial, chi2_final,
     device_ms); an argument error found on the device raises and leaves the outputs as passed."""
-    L = _lib.lib()
-    fn = L.orbba_local_bundle_adjustment_device
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(_Problem), C.POINTER(_LmResult), C.c_void_p, C.c_void_p]
+    fn = _L().orbba_local_bundle_adjustment_device
     p = lambda k: d[k].data_ptr()  # noqa: E731
     prob = _Problem(cam[0], cam[1], cam[2], cam[3], huber_delta, n_poses, n_points, n_edges, p("pose_R"), p("pose_t"), p("pose_fixed"),
                     p("ba_points"), p("edge_pose"), p("edge_point"), p("edge_z"), p("edge_inv_sigma2"), *_cam_tail(cam))
@@ -173,13 +158,38 @@ class _PoseResult(C.Structure):
                 ("chi2", C.c_void_p), ("kernel_ms", C.c_float)]
 
 
+_sigs_done = False
+
+
+def _L():
+    """the library with the orbba_* signatures set, once (include/orbba.h)"""
+    global _sigs_done
+    L = _lib.lib()
+    if not _sigs_done:
+        vp, i32, ptr = C.c_void_p, C.c_int, C.POINTER
+        sigs = {
+            "orbba_set_variant": [i32, i32],
+            "orbba_linearize": [ptr(_Problem), ptr(_Result), i32],
+            "orbba_optimize": [ptr(_Problem), ptr(_LmOptions), ptr(_LmResult), i32],
+            "orbba_local_bundle_adjustment": [ptr(_Problem), ptr(_LmResult), vp, i32],
+            "orbba_local_bundle_adjustment_device": [ptr(_Problem), ptr(_LmResult), vp, vp],
+            "orbba_pose_optimize_batch": [ptr(_PoseProblem), ptr(_PoseResult), i32],
+            "orbba_pose_optimize_batch_device": [ptr(_PoseProblem), ptr(_PoseResult), vp],
+            "orbba_pose_edges_device": [i32, i32] + [vp] * 9,
+            "orbba_pose_drop_outliers_device": [i32] + [vp] * 5,
+        }
+        for name, args in sigs.items():
+            fn = getattr(L, name)  # AttributeError if the library does not export it
+            fn.restype = i32
+            fn.argtypes = args
+        _sigs_done = True
+    return L
+
+
 def pose_optimize_batch(cam, pose_R, pose_t, edge_off, points, edge_z, edge_inv_sigma2, huber_delta=HUBER_MONO, device=-1):
     """Optimize::poseOptimize (Optimize.cpp:444-545) for many frames at once; frame f owns edges
     edge_off[f]:edge_off[f+1].  Returns dict(pose_R, pose_t, inlier, n_inliers, chi2, kernel_ms)."""
-    L = _lib.lib()
-    fn = L.orbba_pose_optimize_batch
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(_PoseProblem), C.POINTER(_PoseResult), C.c_int]
+    fn = _L().orbba_pose_optimize_batch
     f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     R, t = f8(pose_R).reshape(-1, 9), f8(pose_t).reshape(-1, 3)
     off = np.ascontiguousarray(edge_off, dtype=np.int32)
@@ -199,35 +209,23 @@ def pose_optimize_batch(cam, pose_R, pose_t, edge_off, points, edge_z, edge_inv_
 
 def pose_edges_device(n2, nq, d_frame_mp, d_kps, d_q_points, d_edge_off, d_points, d_z, d_w, d_edge_kp=None, stream=None):
     """orbba_pose_edges_device on torch device tensors: poseOptimize's edges from a device-resident frame's frame_mp."""
-    import torch
-    L = _lib.lib()
-    fn = L.orbba_pose_edges_device
-    fn.restype, fn.argtypes = C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 9
-    st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    fn = _L().orbba_pose_edges_device
     _lib.check(fn(n2, nq, d_frame_mp.data_ptr(), d_kps.data_ptr(), d_q_points.data_ptr(), d_edge_off.data_ptr(), d_points.data_ptr(),
-                  d_z.data_ptr(), d_w.data_ptr(), d_edge_kp.data_ptr() if d_edge_kp is not None else None, st))
+                  d_z.data_ptr(), d_w.data_ptr(), d_edge_kp.data_ptr() if d_edge_kp is not None else None, _lib.stream_arg(stream)))
 
 
 def pose_drop_outliers_device(n2, d_edge_off, d_edge_kp, d_inlier, d_frame_mp, stream=None):
     """orbba_pose_drop_outliers_device on torch device tensors (Optimize.cpp:531-537): frame_mp[edge_kp[e]] = -1 for every edge
     e < edge_off[1] that pose_optimize_batch_device left with inlier[e] == 0."""
-    import torch
-    L = _lib.lib()
-    fn = L.orbba_pose_drop_outliers_device
-    fn.restype, fn.argtypes = C.c_int, [C.c_int] + [C.c_void_p] * 5
-    st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
-    _lib.check(fn(n2, d_edge_off.data_ptr(), d_edge_kp.data_ptr(), d_inlier.data_ptr(), d_frame_mp.data_ptr(), st))
+    fn = _L().orbba_pose_drop_outliers_device
+    _lib.check(fn(n2, d_edge_off.data_ptr(), d_edge_kp.data_ptr(), d_inlier.data_ptr(), d_frame_mp.data_ptr(), _lib.stream_arg(stream)))
 
 
 def pose_optimize_batch_device(cam, d_R, d_t, d_edge_off, d_points, d_z, d_w, d_R_out, d_t_out, d_inlier, d_n_inliers, d_chi2,
                                n_frames=1, huber_delta=HUBER_MONO, stream=None):
     """orbba_pose_optimize_batch_device: every array a torch device tensor (float64 / int32 / uint8), nothing copied."""
-    import torch
-    L = _lib.lib()
-    fn = L.orbba_pose_optimize_batch_device
-    fn.restype, fn.argtypes = C.c_int, [C.POINTER(_PoseProblem), C.POINTER(_PoseResult), C.c_void_p]
-    st = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    fn = _L().orbba_pose_optimize_batch_device
     prob = _PoseProblem(cam[0], cam[1], cam[2], cam[3], huber_delta, n_frames, 0, 0, d_edge_off.data_ptr(), d_R.data_ptr(),
                         d_t.data_ptr(), d_points.data_ptr(), d_z.data_ptr(), d_w.data_ptr(), *_cam_tail(cam))
     res = _PoseResult(d_R_out.data_ptr(), d_t_out.data_ptr(), d_inlier.data_ptr(), d_n_inliers.data_ptr(), d_chi2.data_ptr(), 0.0)
-    _lib.check(fn(C.byref(prob), C.byref(res), st))
+    _lib.check(fn(C.byref(prob), C.byref(res), _lib.stream_arg(stream)))

@@ -110,8 +110,10 @@ typedef GrowBuf<true> PinBuf;
 
 // Workspaces (a non-blocking stream and scratch, W::init() makes them) of the calls that must not share a stream or scratch:
 // the handle-less BA entry points and orbv_transform on a shared vocabulary.  A call leases one of its device for its duration;
-// when the lease returns, the workspace's stream is synchronised first -- an error return may leave work in flight, and the
-// next lessee must not meet it.  The pool never frees a workspace; its owner does, if at all.
+// when the lease returns, the stream the call ran on is synchronised first -- an error return may leave work in flight, and the
+// next lessee must not meet it.  That stream is the workspace's own unless the call sets `stream` to another behind acquire(): a
+// device-pointer call that borrows the scratch but enqueues on its caller's stream.  The pool never frees a workspace; its owner
+// does, if at all.
 template <typename W> struct LeasePool {
     std::mutex mu;
     std::vector<W *> idle;
@@ -119,13 +121,14 @@ template <typename W> struct LeasePool {
 template <typename W> struct Lease {
     LeasePool<W> &pool;
     W *w = nullptr;
+    hipStream_t stream = nullptr; // the stream the call runs on
     explicit Lease(LeasePool<W> &p) : pool(p) {}
     Lease(const Lease &) = delete;
     Lease &operator=(const Lease &) = delete;
     ~Lease()
     {
         if (!w) return;
-        (void)hipStreamSynchronize(w->stream);
+        (void)hipStreamSynchronize(stream);
         std::lock_guard<std::mutex> lock(pool.mu);
         pool.idle.push_back(w);
     }
@@ -136,6 +139,7 @@ template <typename W> struct Lease {
             for (size_t i = pool.idle.size(); i-- > 0;)
                 if (pool.idle[i]->device == device) {
                     w = pool.idle[i];
+                    stream = w->stream;
                     pool.idle.erase(pool.idle.begin() + (long)i);
                     return hipSuccess;
                 }
@@ -145,6 +149,7 @@ template <typename W> struct Lease {
         hipError_t e = n->init();
         if (e != hipSuccess) { delete n; return e; }
         w = n;
+        stream = w->stream;
         return hipSuccess;
     }
 };

@@ -21,6 +21,7 @@
 #include "../../include/orbx.h"
 #include "orb_device.h"
 #include "orb_host.h"
+#include "orbba_problem.h"
 
 // kernel-choice switches of the BA entry points (include/orbba.h: orbba_set_variant); the entry points take no handle, so the
 // switches are per process and read per call
@@ -34,10 +35,9 @@ extern "C" int orbba_set_variant(int which, int value)
 }
 
 struct BaCam { double fx, fy, cx, cy, delta; int model; double k[4]; };
-static BaCam make_cam(double fx, double fy, double cx, double cy, double delta, int model, const double *k)
+template <typename Problem> static BaCam make_cam(const Problem *p) // orbba_problem and orbba_pose_problem name the camera alike
 {
-    BaCam c = {fx, fy, cx, cy, delta, model, {k[0], k[1], k[2], k[3]}};
-    return c;
+    return {p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, {p->fisheye_k[0], p->fisheye_k[1], p->fisheye_k[2], p->fisheye_k[3]}};
 }
 // camera->project(Pc) (G2oTypes.h:250 through Camera): Pinhole.cpp:28-32, or the Kannala-Brandt model of Fisheye.cpp:35-49
 __device__ __forceinline__ void ba_project(const BaCam &cam, double X, double Y, double Z, double *u, double *v)
@@ -253,33 +253,28 @@ struct Layout {
     size_t n = 0;
     size_t add(size_t bytes) { const size_t o = n; n += (bytes + 255) & ~(size_t)255; return o; }
 };
-inline void put(uint8_t *base, size_t off, const void *src, size_t bytes) { if (bytes) memcpy(base + off, src, bytes); }
+// typed addresses in a block -- the device arena or the page-locked staging block -- by byte offset, and copies between the staging
+// block and the caller's host arrays
+struct Arena {
+    uint8_t *base;
+    uint8_t *at(size_t off) const { return base + off; }
+    double *D(size_t off) const { return reinterpret_cast<double *>(base + off); }
+    int *I(size_t off) const { return reinterpret_cast<int *>(base + off); }
+    void put(size_t off, const void *src, size_t bytes) const { if (bytes) memcpy(base + off, src, bytes); }
+    void get(void *dst, size_t off, size_t bytes) const { if (dst && bytes) memcpy(dst, base + off, bytes); } // an output may be NULL
+};
+inline int ba_refuse(const BaVerdict &v) { return orbx_set_error(v.code, v.text); }
 } // namespace
 
 extern "C" int orbba_linearize(const orbba_problem *p, orbba_result *r, int device)
 {
     if (!p || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (p->n_poses < 1 || p->n_points < 1 || p->n_edges < 0) return orbx_set_error(ORBX_E_ARG, "bad sizes");
-    if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || (p->n_edges && (!p->edge_pose || !p->edge_point || !p->edge_z || !p->edge_inv_sigma2)))
-        return orbx_set_error(ORBX_E_ARG, "null input array");
+    BaIndex ix;
+    if (BaVerdict v = ba_check_problem(p, 0); v.code) return ba_refuse(v);
+    if (BaVerdict v = ba_build_index(p, false, &ix); v.code) return ba_refuse(v);
     if (int rc = orb_need_device(&device)) return rc;
     ORB_TRY(hipSetDevice(device));
     const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
-    // host-side index structures: edges per pose (CSR, edge order) and the contiguous range of each point
-    std::vector<int> pose_off(NP + 1, 0), pose_edges(std::max(NE, 1)), point_off(NL + 1, 0);
-    for (int e = 0; e < NE; ++e) {
-        if (p->edge_pose[e] < 0 || p->edge_pose[e] >= NP || p->edge_point[e] < 0 || p->edge_point[e] >= NL)
-            return orbx_set_error(ORBX_E_ARG, "edge index out of range");
-        if (e && p->edge_point[e] < p->edge_point[e - 1]) return orbx_set_error(ORBX_E_ARG, "edges must be grouped by point");
-        pose_off[p->edge_pose[e] + 1]++;
-        point_off[p->edge_point[e] + 1]++;
-    }
-    for (int i = 0; i < NP; ++i) pose_off[i + 1] += pose_off[i];
-    for (int i = 0; i < NL; ++i) point_off[i + 1] += point_off[i];
-    {
-        std::vector<int> fill(pose_off.begin(), pose_off.end() - 1);
-        for (int e = 0; e < NE; ++e) pose_edges[fill[p->edge_pose[e]]++] = e;
-    }
     // arena: [inputs, one copy up][edge-major scratch][outputs, one copy down: the small blocks first, H_lp last]
     Layout L;
     const size_t oR = L.add(72 * (size_t)NP), ot = L.add(24 * (size_t)NP), ofix = L.add(NP), oP = L.add(24 * (size_t)NL),
@@ -298,39 +293,32 @@ extern "C" int orbba_linearize(const orbba_problem *p, orbba_result *r, int devi
     BaWork *w = lease.w;
     ORB_TRY(w->need(L.n, std::max(in_bytes, out_end - out_begin)));
     hipStream_t s = w->stream;
-    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>();
-    put(h, oR, p->pose_R, 72 * (size_t)NP); put(h, ot, p->pose_t, 24 * (size_t)NP); put(h, ofix, p->pose_fixed, NP);
-    put(h, oP, p->points, 24 * (size_t)NL);
-    if (NE) {
-        put(h, oep, p->edge_pose, 4 * (size_t)NE); put(h, oel, p->edge_point, 4 * (size_t)NE); put(h, oz, p->edge_z, 16 * (size_t)NE);
-        put(h, ow, p->edge_inv_sigma2, 8 * (size_t)NE); put(h, ope, pose_edges.data(), 4 * (size_t)NE);
-    }
-    put(h, opo, pose_off.data(), 4 * (size_t)(NP + 1)); put(h, olo, point_off.data(), 4 * (size_t)(NL + 1));
-    ORB_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
-    const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
-    auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
-    auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
+    const Arena a = {w->d.as<uint8_t>()}, h = {w->h.as<uint8_t>()};
+    h.put(oR, p->pose_R, 72 * (size_t)NP); h.put(ot, p->pose_t, 24 * (size_t)NP); h.put(ofix, p->pose_fixed, NP);
+    h.put(oP, p->points, 24 * (size_t)NL);
+    h.put(oep, p->edge_pose, 4 * (size_t)NE); h.put(oel, p->edge_point, 4 * (size_t)NE); h.put(oz, p->edge_z, 16 * (size_t)NE);
+    h.put(ow, p->edge_inv_sigma2, 8 * (size_t)NE); h.put(ope, ix.pose_edges.data(), 4 * (size_t)NE);
+    h.put(opo, ix.pose_off.data(), 4 * (size_t)(NP + 1)); h.put(olo, ix.point_off.data(), 4 * (size_t)(NL + 1));
+    ORB_TRY(hipMemcpyAsync(a.base, h.base, in_bytes, hipMemcpyHostToDevice, s));
+    const BaCam cam = make_cam(p);
     ORB_TRY(hipEventRecord(w->e0, s));
     if (NE)
-        hipLaunchKernelGGL(k_ba_edges, dim3((NE + 255) / 256), dim3(256), 0, s, cam, NE, D(oR), D(ot), d + ofix, D(oP), I(oep), I(oel), D(oz),
-                           D(ow), (const uint8_t *)nullptr, D(ochi), D(oerr), D(oHlp), D(oCpp), D(oCll));
-    hipLaunchKernelGGL(k_ba_reduce_pose, dim3(NP), dim3(256), 0, s, I(opo), I(ope), D(oCpp), D(oHpp), D(obp));
-    hipLaunchKernelGGL(k_ba_reduce_point, dim3((NL + 255) / 256), dim3(256), 0, s, NL, I(olo), D(oCll), D(oHll), D(obl));
+        hipLaunchKernelGGL(k_ba_edges, dim3((NE + 255) / 256), dim3(256), 0, s, cam, NE, a.D(oR), a.D(ot), a.at(ofix), a.D(oP), a.I(oep),
+                           a.I(oel), a.D(oz), a.D(ow), (const uint8_t *)nullptr, a.D(ochi), a.D(oerr), a.D(oHlp), a.D(oCpp), a.D(oCll));
+    hipLaunchKernelGGL(k_ba_reduce_pose, dim3(NP), dim3(256), 0, s, a.I(opo), a.I(ope), a.D(oCpp), a.D(oHpp), a.D(obp));
+    hipLaunchKernelGGL(k_ba_reduce_point, dim3((NL + 255) / 256), dim3(256), 0, s, NL, a.I(olo), a.D(oCll), a.D(oHll), a.D(obl));
     ORB_TRY(hipEventRecord(w->e1, s));
     ORB_TRY(hipGetLastError());
-    ORB_TRY(hipMemcpyAsync(h, d + out_begin, out_end - out_begin, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(h.base, a.at(out_begin), out_end - out_begin, hipMemcpyDeviceToHost, s));
     ORB_TRY(hipStreamSynchronize(s));
     float ms = 0;
     ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
     r->kernel_ms = ms;
-    auto O = [&](size_t off) { return h + (off - out_begin); }; // an output's place in the staging block
-    if (r->chi2 && NE) memcpy(r->chi2, O(ochi), 8 * (size_t)NE);
-    if (r->error && NE) memcpy(r->error, O(oerr), 16 * (size_t)NE);
-    if (r->H_lp && NE) memcpy(r->H_lp, O(oHlp), 144 * (size_t)NE);
-    if (r->H_pp) memcpy(r->H_pp, O(oHpp), 288 * (size_t)NP);
-    if (r->b_p) memcpy(r->b_p, O(obp), 48 * (size_t)NP);
-    if (r->H_ll) memcpy(r->H_ll, O(oHll), 72 * (size_t)NL);
-    if (r->b_l) memcpy(r->b_l, O(obl), 24 * (size_t)NL);
+    // an output's place in the staging block is its place in the arena behind out_begin
+    h.get(r->chi2, ochi - out_begin, 8 * (size_t)NE); h.get(r->error, oerr - out_begin, 16 * (size_t)NE);
+    h.get(r->H_lp, oHlp - out_begin, 144 * (size_t)NE);
+    h.get(r->H_pp, oHpp - out_begin, 288 * (size_t)NP); h.get(r->b_p, obp - out_begin, 48 * (size_t)NP);
+    h.get(r->H_ll, oHll - out_begin, 72 * (size_t)NL); h.get(r->b_l, obl - out_begin, 24 * (size_t)NL);
     return ORBX_OK;
 }
 
@@ -700,14 +688,16 @@ __global__ __launch_bounds__(256) void k_lm_diag_max(int n_free, const int *__re
 }
 
 namespace {
-// One LM problem in the arena: its sizes and the offsets of its arrays.  The host form fills [0, in_bytes) in one copy; the device form
-// copies the caller's arrays in and builds the index structures there (below), before it knows the number of free poses: everything up
-// to and including o_edge_of's START does not depend on it.
+// One LM problem in the arena: its sizes and the offsets of its arrays.  What a host form brings back leads -- [read-back block]
+// [chi2 out][outlier out][estimates R t P], ONE copy down from wherever the caller's first output lies -- and the estimates also open
+// what it sends: [oR, in_end) is its ONE copy up.  The device form copies the caller's arrays in and builds the index structures in
+// place (below), before it knows the number of free poses: everything up to and including o_edge_of's START does not depend on it.
 struct LmPlan {
     int NP, NL, NE, NF, N, EB, LB;
-    size_t oR, ot, oP, est_bytes;                                  // the estimates, in and out
-    size_t ofix, oep, oel, oz, ow, oact, opo, ope, olo, oslot, ofree, oix, oeo, in_bytes;
-    size_t oRb, oHlp, oCpp, oCll, oHpp, obp, oHll, obl, oinv, otl, oS, orhs, oxp, oxl, ochi, ochi1, orb, bytes;
+    size_t ochio, oout, orb;                                       // results of the host forms besides the estimates
+    size_t oR, ot, oP, est_bytes, est_end;                         // the estimates, in and out
+    size_t ofix, oep, oel, oz, ow, oact, opo, ope, olo, oslot, ofree, oix, oeo, in_end;
+    size_t oRb, oHlp, oCpp, oCll, oHpp, obp, oHll, obl, oinv, otl, oS, orhs, oxp, oxl, ochi, ochi1, bytes;
     // what the host reads per trial, ONE copy: [chi2 partials at the iteration's estimate: EB][at the trial's: EB]
     // [computeScale partials of the points: LB][of the poses: 1][max |H_jj|: 1][Cholesky flag: int in 8 bytes]
     int RB_CUR, RB_TRY, RB_SCL, RB_POSE, RB_MAX, RB_FLAG, RB_N;
@@ -717,24 +707,24 @@ LmPlan lm_plan(int NP, int NL, int NE, int NF)
     LmPlan q = {};
     q.NP = NP, q.NL = NL, q.NE = NE, q.NF = NF, q.N = 6 * NF, q.EB = (NE + 255) / 256, q.LB = (NL + 255) / 256;
     const int N = q.N;
-    // arena: [estimates R t P -- in and out][other inputs][scratch][chi2 out][read-back block]
+    q.RB_CUR = 0, q.RB_TRY = q.EB, q.RB_SCL = 2 * q.EB, q.RB_POSE = 2 * q.EB + q.LB, q.RB_MAX = q.RB_POSE + 1, q.RB_FLAG = q.RB_POSE + 2;
+    q.RB_N = q.RB_POSE + 3;
+    // arena: [chi2 out][outlier out][read-back block][estimates R t P -- in and out][other inputs][scratch]
     Layout L;
+    q.ochio = L.add(8 * (size_t)NE), q.oout = L.add(NE), q.orb = L.add(8 * (size_t)q.RB_N);
     q.oR = L.add(72 * (size_t)NP), q.ot = L.add(24 * (size_t)NP), q.oP = L.add(24 * (size_t)NL);
-    q.est_bytes = L.n;
+    q.est_bytes = L.n - q.oR, q.est_end = L.n;
     q.ofix = L.add(NP), q.oep = L.add(4 * (size_t)NE), q.oel = L.add(4 * (size_t)NE), q.oz = L.add(16 * (size_t)NE);
     q.ow = L.add(8 * (size_t)NE), q.oact = L.add(NE), q.opo = L.add(4 * (size_t)(NP + 1)), q.ope = L.add(4 * (size_t)NE);
     q.olo = L.add(4 * (size_t)(NL + 1)), q.oslot = L.add(4 * (size_t)NP), q.ofree = L.add(4 * (size_t)NP), q.oix = L.add(64);
     q.oeo = L.add((size_t)4 * NF * NL);
-    q.in_bytes = L.n;
+    q.in_end = L.n;
     q.oRb = L.add(q.est_bytes); // push() / pop(): R, t, P kept in the same relative layout
     q.oHlp = L.add(144 * (size_t)NE), q.oCpp = L.add(216 * (size_t)NE), q.oCll = L.add(72 * (size_t)NE);
     q.oHpp = L.add(288 * (size_t)NP), q.obp = L.add(48 * (size_t)NP), q.oHll = L.add(72 * (size_t)NL), q.obl = L.add(24 * (size_t)NL);
     q.oinv = L.add(72 * (size_t)NL), q.otl = L.add(24 * (size_t)NL), q.oS = L.add((size_t)8 * N * N), q.orhs = L.add(8 * (size_t)N);
     q.oxp = L.add(8 * (size_t)N), q.oxl = L.add(24 * (size_t)NL);
     q.ochi = L.add(8 * (size_t)NE), q.ochi1 = L.add(8 * (size_t)NE);
-    q.RB_CUR = 0, q.RB_TRY = q.EB, q.RB_SCL = 2 * q.EB, q.RB_POSE = 2 * q.EB + q.LB, q.RB_MAX = q.RB_POSE + 1, q.RB_FLAG = q.RB_POSE + 2;
-    q.RB_N = q.RB_POSE + 3;
-    q.orb = L.add(8 * (size_t)q.RB_N);
     q.bytes = L.n;
     return q;
 }
@@ -748,38 +738,27 @@ LmKnobs lm_knobs(const orbba_lm_options *o)
 }
 inline double lm_sum(const double *rb, int from, int n) { double v = 0.0; for (int b = 0; b < n; ++b) v += rb[from + b]; return v; }
 
-// optimizer.optimize(max_iterations) on a problem that lies in the arena `d` as `q` describes it, index structures included, enqueued on
+// optimizer.optimize(max_iterations) on a problem that lies in the arena `a` as `q` describes it, index structures included, enqueued on
 // `s`; `rb` is the page-locked read-back block.  THE loop: the host-pointer and the device-pointer entry points both run it.  It waits
 // on `s` once per trial and returns behind the last evaluation, whose chi2 partials (q.RB_TRY) the caller reads back with its results.
-int lm_loop(const LmPlan &q, uint8_t *d, double *rb, hipStream_t s, const BaCam &cam, const uint8_t *d_active, const LmKnobs &o, LmOutcome *out)
+int lm_loop(const LmPlan &q, const Arena &a, double *rb, hipStream_t s, const BaCam &cam, const uint8_t *d_active, const LmKnobs &o, LmOutcome *out)
 {
-    const int NP = q.NP, NL = q.NL, NE = q.NE, NF = q.NF, N = q.N, EB = q.EB, LB = q.LB;
-    const int RB_CUR = q.RB_CUR, RB_TRY = q.RB_TRY, RB_SCL = q.RB_SCL, RB_POSE = q.RB_POSE, RB_MAX = q.RB_MAX, RB_FLAG = q.RB_FLAG, RB_N = q.RB_N;
-    const size_t oR = q.oR, ot = q.ot, oP = q.oP, est_bytes = q.est_bytes, ofix = q.ofix, oep = q.oep, oel = q.oel, oz = q.oz, ow = q.ow, opo = q.opo,
-                 ope = q.ope, olo = q.olo, ofree = q.ofree, oslot = q.oslot, oeo = q.oeo, oRb = q.oRb, oHlp = q.oHlp, oCpp = q.oCpp, oCll = q.oCll,
-                 oHpp = q.oHpp, obp = q.obp, oHll = q.oHll, obl = q.obl, oinv = q.oinv, otl = q.otl, oS = q.oS, orhs = q.orhs, oxp = q.oxp,
-                 oxl = q.oxl, ochi = q.ochi, orb = q.orb;
-    const double tau = o.tau, lower = o.lower, upper = o.upper;
-    const int max_trials = o.max_trials;
-    auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
-    auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
-
     // errors at the current estimate (+ the whole linearisation when `full`); activeRobustChi2 as partial sums into the
     // read-back block's slot `slot`
     auto evaluate = [&](bool full, int slot) {
-        hipLaunchKernelGGL(k_ba_edges, dim3(EB), dim3(256), 0, s, cam, NE, D(oR), D(ot), d + ofix, D(oP), I(oep), I(oel), D(oz), D(ow),
-                           d_active, D(ochi), (double *)nullptr, full ? D(oHlp) : nullptr, full ? D(oCpp) : nullptr,
-                           full ? D(oCll) : nullptr);
+        hipLaunchKernelGGL(k_ba_edges, dim3(q.EB), dim3(256), 0, s, cam, q.NE, a.D(q.oR), a.D(q.ot), a.at(q.ofix), a.D(q.oP), a.I(q.oep),
+                           a.I(q.oel), a.D(q.oz), a.D(q.ow), d_active, a.D(q.ochi), (double *)nullptr, full ? a.D(q.oHlp) : nullptr,
+                           full ? a.D(q.oCpp) : nullptr, full ? a.D(q.oCll) : nullptr);
         if (full) {
-            hipLaunchKernelGGL(k_ba_reduce_pose, dim3(NP), dim3(256), 0, s, I(opo), I(ope), D(oCpp), D(oHpp), D(obp));
-            hipLaunchKernelGGL(k_ba_reduce_point, dim3(LB), dim3(256), 0, s, NL, I(olo), D(oCll), D(oHll), D(obl));
+            hipLaunchKernelGGL(k_ba_reduce_pose, dim3(q.NP), dim3(256), 0, s, a.I(q.opo), a.I(q.ope), a.D(q.oCpp), a.D(q.oHpp), a.D(q.obp));
+            hipLaunchKernelGGL(k_ba_reduce_point, dim3(q.LB), dim3(256), 0, s, q.NL, a.I(q.olo), a.D(q.oCll), a.D(q.oHll), a.D(q.obl));
         }
-        hipLaunchKernelGGL(k_lm_chi2, dim3(EB), dim3(256), 0, s, NE, cam.delta, D(ochi), d_active, D(orb) + slot);
+        hipLaunchKernelGGL(k_lm_chi2, dim3(q.EB), dim3(256), 0, s, q.NE, cam.delta, a.D(q.ochi), d_active, a.D(q.orb) + slot);
     };
     // the read-back block in host memory: the call's only waits besides the final one
     auto read_back = [&]() -> int {
         ORB_TRY(hipGetLastError());
-        ORB_TRY(hipMemcpyAsync(rb, d + orb, 8 * (size_t)RB_N, hipMemcpyDeviceToHost, s));
+        ORB_TRY(hipMemcpyAsync(rb, a.at(q.orb), 8 * (size_t)q.RB_N, hipMemcpyDeviceToHost, s));
         ORB_TRY(hipStreamSynchronize(s));
         return ORBX_OK;
     };
@@ -788,15 +767,16 @@ int lm_loop(const LmPlan &q, uint8_t *d, double *rb, hipStream_t s, const BaCam 
     double lam = 0.0, ni = 2.0, chi_initial = 0.0, current = 0.0;
     int its = 0, trials_total = 0, rc = ORBX_OK;
     for (int it = 0; it < o.max_iterations; ++it) {
-        evaluate(true, RB_CUR);
+        evaluate(true, q.RB_CUR);
         bool have_current = false;
         if (it == 0) {
             if (o.user_lambda_init > 0) lam = o.user_lambda_init;
             else { // computeLambdaInit: tau * max |H_jj| over the free vertices
-                hipLaunchKernelGGL(k_lm_diag_max, dim3(1), dim3(256), 0, s, NF, I(ofree), D(oHpp), NL, D(oHll), D(orb) + RB_MAX);
+                hipLaunchKernelGGL(k_lm_diag_max, dim3(1), dim3(256), 0, s, q.NF, a.I(q.ofree), a.D(q.oHpp), q.NL, a.D(q.oHll),
+                                   a.D(q.orb) + q.RB_MAX);
                 if ((rc = read_back())) return rc;
-                lam = tau * rb[RB_MAX];
-                current = sum(RB_CUR, EB);
+                lam = o.tau * rb[q.RB_MAX];
+                current = sum(q.RB_CUR, q.EB);
                 have_current = true;
             }
             ni = 2.0;
@@ -805,199 +785,144 @@ int lm_loop(const LmPlan &q, uint8_t *d, double *rb, hipStream_t s, const BaCam 
         int qmax = 0;
         do {
             // push(): keep the estimates
-            ORB_TRY(hipMemcpyAsync(d + oRb, d + oR, est_bytes, hipMemcpyDeviceToDevice, s)); // R, t, P and their copies are laid out alike
-            hipLaunchKernelGGL(k_lm_points, dim3(LB), dim3(256), 0, s, NL, lam, D(oHll), D(obl), D(oinv), D(otl));
-            hipLaunchKernelGGL(k_lm_schur, dim3(NF * (NF + 1) / 2), dim3(256), 0, s, NF, NL, lam, I(ofree), I(oeo), D(oHpp), D(obp), D(oHlp),
-                               D(oinv), D(otl), D(oS), D(orhs));
-            int *const d_flag = reinterpret_cast<int *>(D(orb) + RB_FLAG);
+            ORB_TRY(hipMemcpyAsync(a.at(q.oRb), a.at(q.oR), q.est_bytes, hipMemcpyDeviceToDevice, s)); // R, t, P and their copies are laid out alike
+            hipLaunchKernelGGL(k_lm_points, dim3(q.LB), dim3(256), 0, s, q.NL, lam, a.D(q.oHll), a.D(q.obl), a.D(q.oinv), a.D(q.otl));
+            hipLaunchKernelGGL(k_lm_schur, dim3(q.NF * (q.NF + 1) / 2), dim3(256), 0, s, q.NF, q.NL, lam, a.I(q.ofree), a.I(q.oeo), a.D(q.oHpp),
+                               a.D(q.obp), a.D(q.oHlp), a.D(q.oinv), a.D(q.otl), a.D(q.oS), a.D(q.orhs));
+            int *const d_flag = reinterpret_cast<int *>(a.D(q.orb) + q.RB_FLAG);
             // ORBBA_VAR_CHOL = 1: the global-memory kernel, the parity twin (read per call)
-            bool in_lds = N <= CH_MAX_N && g_ba_chol.load() == 0;
+            bool in_lds = q.N <= CH_MAX_N && g_ba_chol.load() == 0;
             if (in_lds) {
-                const size_t lds = sizeof(double) * ((size_t)(N + 1) * (N + 1) + N);
+                const size_t lds = sizeof(double) * ((size_t)(q.N + 1) * (q.N + 1) + q.N);
                 // per device; when the opt-in or the launch is refused the global-memory kernel solves the system instead --
                 // a launch that did not happen would leave the previous iteration's step in xp / the flag
                 in_lds = orbx_lds_opt_in(reinterpret_cast<const void *>(k_lm_chol_solve_lds), lds) == hipSuccess;
                 if (in_lds) {
-                    hipLaunchKernelGGL(k_lm_chol_solve_lds, dim3(1), dim3(CH_T), lds, s, N, D(oS), D(orhs), D(oxp), d_flag);
+                    hipLaunchKernelGGL(k_lm_chol_solve_lds, dim3(1), dim3(CH_T), lds, s, q.N, a.D(q.oS), a.D(q.orhs), a.D(q.oxp), d_flag);
                     in_lds = hipGetLastError() == hipSuccess;
                 }
             }
             if (!in_lds) {
-                hipLaunchKernelGGL(k_lm_chol_solve, dim3(1), dim3(256), 0, s, N, D(oS), D(orhs), D(oxp), d_flag);
+                hipLaunchKernelGGL(k_lm_chol_solve, dim3(1), dim3(256), 0, s, q.N, a.D(q.oS), a.D(q.orhs), a.D(q.oxp), d_flag);
                 ORB_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(k_lm_backsub, dim3(LB), dim3(256), 0, s, NL, lam, I(olo), I(oep), I(oslot), D(oHlp), D(oxp), D(obl), D(oinv),
-                               D(oxl), D(orb) + RB_SCL);
-            hipLaunchKernelGGL(k_lm_update_poses, dim3(1), dim3(256), 0, s, NF, lam, I(ofree), D(oxp), D(obp), D(oR), D(ot), D(orb) + RB_POSE);
-            hipLaunchKernelGGL(k_lm_update_points, dim3((3 * NL + 255) / 256), dim3(256), 0, s, 3 * NL, D(oxl), D(oP));
-            evaluate(false, RB_TRY);
+            hipLaunchKernelGGL(k_lm_backsub, dim3(q.LB), dim3(256), 0, s, q.NL, lam, a.I(q.olo), a.I(q.oep), a.I(q.oslot), a.D(q.oHlp), a.D(q.oxp),
+                               a.D(q.obl), a.D(q.oinv), a.D(q.oxl), a.D(q.orb) + q.RB_SCL);
+            hipLaunchKernelGGL(k_lm_update_poses, dim3(1), dim3(256), 0, s, q.NF, lam, a.I(q.ofree), a.D(q.oxp), a.D(q.obp), a.D(q.oR), a.D(q.ot),
+                               a.D(q.orb) + q.RB_POSE);
+            hipLaunchKernelGGL(k_lm_update_points, dim3((3 * q.NL + 255) / 256), dim3(256), 0, s, 3 * q.NL, a.D(q.oxl), a.D(q.oP));
+            evaluate(false, q.RB_TRY);
             if ((rc = read_back())) return rc;
-            if (!have_current) { current = sum(RB_CUR, EB); have_current = true; }
+            if (!have_current) { current = sum(q.RB_CUR, q.EB); have_current = true; }
             if (it == 0 && qmax == 0) chi_initial = current;
-            double temp = sum(RB_TRY, EB);
+            double temp = sum(q.RB_TRY, q.EB);
             int ok2 = 0;
-            memcpy(&ok2, rb + RB_FLAG, sizeof(int));
+            memcpy(&ok2, rb + q.RB_FLAG, sizeof(int));
             if (!ok2) temp = std::numeric_limits<double>::max();
-            double scale = rb[RB_POSE]; // poses first, then the points block by block
-            for (int b = 0; b < LB; ++b) scale += rb[RB_SCL + b];
+            double scale = rb[q.RB_POSE]; // poses first, then the points block by block
+            for (int b = 0; b < q.LB; ++b) scale += rb[q.RB_SCL + b];
             scale += 1e-3;
             rho = (current - temp) / scale;
             ++trials_total;
             if (rho > 0 && std::isfinite(temp)) {
                 double alpha = 1.0 - std::pow(2 * rho - 1, 3);
-                alpha = std::min(alpha, upper);
-                lam *= std::max(lower, alpha);
+                alpha = std::min(alpha, o.upper);
+                lam *= std::max(o.lower, alpha);
                 ni = 2.0;
                 current = temp;
             } else {
                 lam *= ni;
                 ni *= 2;
                 // pop(): restore
-                ORB_TRY(hipMemcpyAsync(d + oR, d + oRb, est_bytes, hipMemcpyDeviceToDevice, s));
+                ORB_TRY(hipMemcpyAsync(a.at(q.oR), a.at(q.oRb), q.est_bytes, hipMemcpyDeviceToDevice, s));
                 if (!std::isfinite(lam)) break;
             }
             ++qmax;
-        } while (rho < 0 && qmax < max_trials);
+        } while (rho < 0 && qmax < o.max_trials);
         ++its;
-        if (qmax == max_trials || rho == 0 || !std::isfinite(lam)) break; // Terminate
+        if (qmax == o.max_trials || rho == 0 || !std::isfinite(lam)) break; // Terminate
     }
-    evaluate(false, RB_TRY);
+    evaluate(false, q.RB_TRY);
     ORB_TRY(hipGetLastError());
     out->iterations = its, out->trials = trials_total, out->lambda = lam, out->chi_initial = chi_initial;
     return ORBX_OK;
 }
-} // namespace
 
-extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o, orbba_lm_result *r, int device)
+// ---- what the two host-pointer LM entry points share around their loops.  The staging block mirrors the arena up to q.in_end.
+// The ONE copy up: the estimates, the problem, the mask if there is one, and the index structures
+int lm_upload(const LmPlan &q, const Arena &a, const Arena &h, const orbba_problem *p, const uint8_t *edge_active, const BaIndex &ix, hipStream_t s)
 {
-    if (!p || !o || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
-    if (p->n_poses < 1 || p->n_points < 1 || p->n_edges < 1) return orbx_set_error(ORBX_E_ARG, "bad sizes");
-    if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || !p->edge_pose || !p->edge_point || !p->edge_z ||
-        !p->edge_inv_sigma2)
-        return orbx_set_error(ORBX_E_ARG, "null input array");
-    if (o->max_iterations < 0) return orbx_set_error(ORBX_E_ARG, "negative iteration count");
-    if (int rc = orb_need_device(&device)) return rc;
-    ORB_TRY(hipSetDevice(device));
-    const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
-    // ---- index structures (the device form builds the same ones with k_lmi_*, below)
-    std::vector<int> pose_off(NP + 1, 0), pose_edges(NE), point_off(NL + 1, 0), free_pose, pose_slot(NP, -1);
-    for (int i = 0; i < NP; ++i)
-        if (!p->pose_fixed[i]) { pose_slot[i] = (int)free_pose.size(); free_pose.push_back(i); }
-    const int NF = (int)free_pose.size();
-    if (NF < 1) return orbx_set_error(ORBX_E_ARG, "every pose is fixed: nothing to optimise");
-    if ((size_t)NF * NL > (size_t)1 << 28) return orbx_set_error(ORBX_E_UNSUPPORTED, "free poses x points table too large");
-    std::vector<int> edge_of((size_t)NF * NL, -1);
-    for (int e = 0; e < NE; ++e) {
-        const int ip = p->edge_pose[e], il = p->edge_point[e];
-        if (ip < 0 || ip >= NP || il < 0 || il >= NL) return orbx_set_error(ORBX_E_ARG, "edge index out of range");
-        if (e && il < p->edge_point[e - 1]) return orbx_set_error(ORBX_E_ARG, "edges must be grouped by point");
-        pose_off[ip + 1]++;
-        point_off[il + 1]++;
-        if (pose_slot[ip] >= 0) {
-            int &slot = edge_of[(size_t)pose_slot[ip] * NL + il];
-            if (slot >= 0) return orbx_set_error(ORBX_E_ARG, "a point is observed twice by the same key frame");
-            slot = e;
-        }
-    }
-    for (int i = 0; i < NP; ++i) pose_off[i + 1] += pose_off[i];
-    for (int i = 0; i < NL; ++i) point_off[i + 1] += point_off[i];
-    {
-        std::vector<int> fill(pose_off.begin(), pose_off.end() - 1);
-        for (int e = 0; e < NE; ++e) pose_edges[fill[p->edge_pose[e]]++] = e;
-    }
-    const LmPlan q = lm_plan(NP, NL, NE, NF);
-    // page-locked block: [read-back][inputs up / results down]
-    Layout HL;
-    const size_t hrb = HL.add(8 * (size_t)q.RB_N), hio = HL.add(std::max(q.in_bytes, q.est_bytes + 8 * (size_t)NE + 256));
-    Lease<BaWork> lease(g_work);
-    ORB_TRY(lease.acquire(device));
-    BaWork *w = lease.w;
-    ORB_TRY(w->need(q.bytes, HL.n));
-    hipStream_t s = w->stream;
-    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>() + hio;
-    double *const rb = reinterpret_cast<double *>(w->h.as<uint8_t>() + hrb);
-    put(h, q.oR, p->pose_R, 72 * (size_t)NP); put(h, q.ot, p->pose_t, 24 * (size_t)NP); put(h, q.oP, p->points, 24 * (size_t)NL);
-    put(h, q.ofix, p->pose_fixed, NP); put(h, q.oep, p->edge_pose, 4 * (size_t)NE); put(h, q.oel, p->edge_point, 4 * (size_t)NE);
-    put(h, q.oz, p->edge_z, 16 * (size_t)NE); put(h, q.ow, p->edge_inv_sigma2, 8 * (size_t)NE);
-    if (o->edge_active) put(h, q.oact, o->edge_active, NE);
-    put(h, q.opo, pose_off.data(), 4 * (size_t)(NP + 1)); put(h, q.ope, pose_edges.data(), 4 * (size_t)NE);
-    put(h, q.olo, point_off.data(), 4 * (size_t)(NL + 1)); put(h, q.ofree, free_pose.data(), 4 * (size_t)NF);
-    put(h, q.oslot, pose_slot.data(), 4 * (size_t)NP); put(h, q.oeo, edge_of.data(), (size_t)4 * NF * NL);
-    ORB_TRY(hipMemcpyAsync(d, h, q.in_bytes, hipMemcpyHostToDevice, s));
-    const uint8_t *d_active = o->edge_active ? d + q.oact : nullptr;
-    const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
-    ORB_TRY(hipEventRecord(w->e0, s));
-    LmOutcome out = {};
-    if (int rc = lm_loop(q, d, rb, s, cam, d_active, lm_knobs(o), &out)) return rc;
-    ORB_TRY(hipEventRecord(w->e1, s));
-    ORB_TRY(hipMemcpyAsync(rb, d + q.orb, 8 * (size_t)q.RB_N, hipMemcpyDeviceToHost, s));
-    ORB_TRY(hipMemcpyAsync(h, d, q.est_bytes, hipMemcpyDeviceToHost, s));
-    if (r->chi2) ORB_TRY(hipMemcpyAsync(h + q.est_bytes, d + q.ochi, 8 * (size_t)NE, hipMemcpyDeviceToHost, s));
-    ORB_TRY(hipStreamSynchronize(s));
-    const double final_chi = lm_sum(rb, q.RB_TRY, q.EB);
+    const size_t NP = q.NP, NL = q.NL, NE = q.NE, NF = q.NF;
+    h.put(q.oR, p->pose_R, 72 * NP); h.put(q.ot, p->pose_t, 24 * NP); h.put(q.oP, p->points, 24 * NL);
+    h.put(q.ofix, p->pose_fixed, NP); h.put(q.oep, p->edge_pose, 4 * NE); h.put(q.oel, p->edge_point, 4 * NE);
+    h.put(q.oz, p->edge_z, 16 * NE); h.put(q.ow, p->edge_inv_sigma2, 8 * NE);
+    if (edge_active) h.put(q.oact, edge_active, NE);
+    h.put(q.opo, ix.pose_off.data(), 4 * (NP + 1)); h.put(q.ope, ix.pose_edges.data(), 4 * NE);
+    h.put(q.olo, ix.point_off.data(), 4 * (NL + 1)); h.put(q.ofree, ix.free_pose.data(), 4 * NF);
+    h.put(q.oslot, ix.pose_slot.data(), 4 * NP); h.put(q.oeo, ix.edge_of.data(), 4 * NF * NL);
+    ORB_TRY(hipMemcpyAsync(a.at(q.oR), h.at(q.oR), q.in_end - q.oR, hipMemcpyHostToDevice, s));
+    return ORBX_OK;
+}
+// behind a call's last wait: the scalars the loops left in `out`, chi2_final from the last evaluation's partial sums in the read-back
+// block, the time between the workspace's two events
+int lm_report(const LmPlan &q, const double *rb, const BaWork *w, const LmOutcome &out, orbba_lm_result *r)
+{
     float ms = 0;
     ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
     r->iterations = out.iterations;
     r->trials = out.trials;
     r->lambda = out.lambda;
-    r->chi2_initial = o->max_iterations > 0 ? out.chi_initial : final_chi;
-    r->chi2_final = final_chi;
+    r->chi2_initial = out.chi_initial;
+    r->chi2_final = lm_sum(rb, q.RB_TRY, q.EB);
     r->device_ms = ms;
-    if (r->pose_R) memcpy(r->pose_R, h + q.oR, 72 * (size_t)NP);
-    if (r->pose_t) memcpy(r->pose_t, h + q.ot, 24 * (size_t)NP);
-    if (r->points) memcpy(r->points, h + q.oP, 24 * (size_t)NL);
-    if (r->chi2) memcpy(r->chi2, h + q.est_bytes, 8 * (size_t)NE);
     return ORBX_OK;
 }
-
-// The optimisation part of Optimize::localBundleAdjustment (Optimize.cpp:892-922)
-extern "C" int orbba_local_bundle_adjustment(const orbba_problem *p, orbba_lm_result *r, uint8_t *outlier, int device)
+// The ONE copy down, from `from` (q.ochio, q.oout or q.orb: the first block the caller wants) to the end of the estimates, the wait,
+// and the copy-out: the scalars, and the estimates and chi2 into whichever of r's arrays are not NULL
+int lm_download(const LmPlan &q, const Arena &a, const Arena &h, size_t from, hipStream_t s, const BaWork *w, const LmOutcome &out, orbba_lm_result *r)
 {
-    if (!p || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
-    const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
-    if (NP < 1 || NL < 1 || NE < 1) return orbx_set_error(ORBX_E_ARG, "bad sizes");
-    std::vector<double> R1((size_t)9 * NP), t1((size_t)3 * NP), P1((size_t)3 * NL), chi((size_t)NE);
-    orbba_lm_options o1 = {};
-    o1.max_iterations = 5; // optimizer.optimize(5), :893
-    orbba_lm_result r1 = {};
-    r1.pose_R = R1.data(); r1.pose_t = t1.data(); r1.points = P1.data(); r1.chi2 = chi.data();
-    int rc = orbba_optimize(p, &o1, &r1, device);
-    if (rc) return rc;
-    std::vector<uint8_t> active((size_t)NE);
-    for (int e = 0; e < NE; ++e) active[e] = !(chi[e] > 5.991); // :899-902
-    orbba_problem p2 = *p;
-    p2.pose_R = R1.data(); p2.pose_t = t1.data(); p2.points = P1.data();
-    p2.huber_delta = 0.0; // setRobustKernel(nullptr), :904
-    orbba_lm_options o2 = {};
-    o2.max_iterations = 10; // :909
-    o2.edge_active = active.data();
-    std::vector<double> chi2v((size_t)NE);
-    double *user_chi = r->chi2;
-    r->chi2 = chi2v.data();
-    rc = orbba_optimize(&p2, &o2, r, device);
-    r->chi2 = user_chi;
-    if (rc) return rc;
-    r->device_ms += r1.device_ms;
-    r->iterations += r1.iterations;
-    r->trials += r1.trials;
-    r->chi2_initial = r1.chi2_initial;
-    // An edge demoted to level 1 at :899-902 is not part of optimize(10)'s active set: g2o never calls computeError()
-    // on it again, so e->chi2() at :919 still evaluates the error vector of the first round -- above 5.991 by
-    // construction -- and the observation is always erased, whatever its residual at the final estimate would be
-    // (poseOptimize has an explicit computeError() for exactly that reason, Optimize.cpp:510; this loop has none).
-    for (int e = 0; e < NE; ++e)
-        if (!active[e]) chi2v[e] = chi[e];
-    if (user_chi) std::copy(chi2v.begin(), chi2v.end(), user_chi);
-    if (outlier)
-        for (int e = 0; e < NE; ++e) outlier[e] = !active[e] || chi2v[e] > 5.991; // :917-921
+    const size_t NP = q.NP, NL = q.NL, NE = q.NE;
+    ORB_TRY(hipMemcpyAsync(h.at(from), a.at(from), q.est_end - from, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipStreamSynchronize(s));
+    h.get(r->pose_R, q.oR, 72 * NP); h.get(r->pose_t, q.ot, 24 * NP); h.get(r->points, q.oP, 24 * NL); h.get(r->chi2, q.ochio, 8 * NE);
+    return lm_report(q, h.D(q.orb), w, out, r);
+}
+
+} // namespace
+
+extern "C" int orbba_optimize(const orbba_problem *p, const orbba_lm_options *o, orbba_lm_result *r, int device)
+{
+    if (!p || !o || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (BaVerdict v = ba_check_problem(p, 1); v.code) return ba_refuse(v);
+    if (o->max_iterations < 0) return orbx_set_error(ORBX_E_ARG, "negative iteration count");
+    BaIndex ix;                          // (the device form builds the same structures with k_lmi_*, below)
+    if (BaVerdict v = ba_build_index(p, true, &ix); v.code) return ba_refuse(v);
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
+    const LmPlan q = lm_plan(p->n_poses, p->n_points, p->n_edges, (int)ix.free_pose.size());
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
+    BaWork *w = lease.w;
+    ORB_TRY(w->need(q.bytes, q.in_end));
+    hipStream_t s = w->stream;
+    const Arena a = {w->d.as<uint8_t>()}, h = {w->h.as<uint8_t>()};
+    if (int rc = lm_upload(q, a, h, p, o->edge_active, ix, s)) return rc;
+    const BaCam cam = make_cam(p);
+    ORB_TRY(hipEventRecord(w->e0, s));
+    LmOutcome out = {};
+    if (int rc = lm_loop(q, a, h.D(q.orb), s, cam, o->edge_active ? a.at(q.oact) : nullptr, lm_knobs(o), &out)) return rc;
+    ORB_TRY(hipEventRecord(w->e1, s));
+    if (r->chi2) ORB_TRY(hipMemcpyAsync(a.at(q.ochio), a.at(q.ochi), 8 * (size_t)q.NE, hipMemcpyDeviceToDevice, s)); // chi2 at the final estimate
+    if (int rc = lm_download(q, a, h, r->chi2 ? q.ochio : q.orb, s, w, out, r)) return rc;
+    if (o->max_iterations == 0) r->chi2_initial = r->chi2_final; // no trial has set it
     return ORBX_OK;
 }
 
 // =====================================================================================================================
 // The same on a problem that lies in DEVICE memory (include/orbba.h: orbba_local_bundle_adjustment_device), as
-// orbm_local_ba_problem_device leaves it.  The index structures orbba_optimize builds on the host are built here by the k_lmi_*
-// kernels, with its checks; both rounds then run lm_loop on them, and the demotion between the rounds and the outlier rule behind
-// them are two small kernels.  Every structure is a function of the edge arrays alone -- counts are sums, a cell of edge_of has one
+// orbm_local_ba_problem_device leaves it.  The index structures the host forms build on the host (orbba_problem.h) are built here by
+// the k_lmi_* kernels, with their checks; both rounds then run lm_loop on them, and the demotion between the rounds and the outlier
+// rule behind them are two small kernels (lba_rounds: the host form runs the same function).  Every structure is a function of the edge arrays alone -- counts are sums, a cell of edge_of has one
 // writer in a problem that passes the checks, pose_edges is placed in edge order by a block scan -- so the bytes equal the host's.
 //   k_lmi_count   thread = edge: index ranges, edges grouped by point; edges per pose into pose_off[pose + 1]
 //   k_lmi_poses   one workgroup: pose_off scanned in place; free_pose / pose_slot / the number of free poses by a scan of the flags
@@ -1128,13 +1053,66 @@ __global__ __launch_bounds__(256) void k_lba_outliers(int NE, const double *__re
     outlier[e] = !active[e] || c > 5.991;
 }
 
+namespace {
+// Optimize.cpp:892-922 on a problem that lies in the arena, index structures included: optimize(5), the demotion of the chi2 > 5.991
+// edges, optimize(10) without the robust kernel, the outlier rule.  Both local-BA entry points run it; d_chi2 and d_outlier are device
+// addresses, the caller's arrays or slots of the arena.  *out: iterations and trials of both rounds, lambda of the second,
+// chi_initial of the first.
+int lba_rounds(const LmPlan &q, const Arena &a, double *rb, hipStream_t s, BaCam cam, double *d_chi2, uint8_t *d_outlier, LmOutcome *out)
+{
+    orbba_lm_options o1 = {}, o2 = {};
+    o1.max_iterations = 5;               // optimizer.optimize(5), :893
+    o2.max_iterations = 10;              // :909
+    LmOutcome out1 = {};
+    if (int rc = lm_loop(q, a, rb, s, cam, nullptr, lm_knobs(&o1), &out1)) return rc;
+    hipLaunchKernelGGL(k_lba_demote, dim3(q.EB), dim3(256), 0, s, q.NE, a.D(q.ochi), a.at(q.oact), a.D(q.ochi1));   // :899-902
+    cam.delta = 0.0;                     // setRobustKernel(nullptr), :904
+    if (int rc = lm_loop(q, a, rb, s, cam, a.at(q.oact), lm_knobs(&o2), out)) return rc;
+    // An edge demoted to level 1 at :899-902 is not part of optimize(10)'s active set: g2o never calls computeError()
+    // on it again, so e->chi2() at :919 still evaluates the error vector of the first round -- above 5.991 by
+    // construction -- and the observation is always erased, whatever its residual at the final estimate would be
+    // (poseOptimize has an explicit computeError() for exactly that reason, Optimize.cpp:510; this loop has none).
+    hipLaunchKernelGGL(k_lba_outliers, dim3(q.EB), dim3(256), 0, s, q.NE, a.D(q.ochi), a.at(q.oact), a.D(q.ochi1), d_chi2, d_outlier); // :917-921
+    ORB_TRY(hipGetLastError());
+    out->iterations += out1.iterations;
+    out->trials += out1.trials;
+    out->chi_initial = out1.chi_initial;
+    return ORBX_OK;
+}
+} // namespace
+
+// The optimisation part of Optimize::localBundleAdjustment (Optimize.cpp:892-922): checks, host index, one copy up, both rounds, one down
+extern "C" int orbba_local_bundle_adjustment(const orbba_problem *p, orbba_lm_result *r, uint8_t *outlier, int device)
+{
+    if (!p || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (BaVerdict v = ba_check_problem(p, 1); v.code) return ba_refuse(v);
+    BaIndex ix;
+    if (BaVerdict v = ba_build_index(p, true, &ix); v.code) return ba_refuse(v);
+    if (int rc = orb_need_device(&device)) return rc;
+    ORB_TRY(hipSetDevice(device));
+    const LmPlan q = lm_plan(p->n_poses, p->n_points, p->n_edges, (int)ix.free_pose.size());
+    Lease<BaWork> lease(g_work);
+    ORB_TRY(lease.acquire(device));
+    BaWork *w = lease.w;
+    ORB_TRY(w->need(q.bytes, q.in_end));
+    hipStream_t s = w->stream;
+    const Arena a = {w->d.as<uint8_t>()}, h = {w->h.as<uint8_t>()};
+    if (int rc = lm_upload(q, a, h, p, nullptr, ix, s)) return rc;
+    ORB_TRY(hipEventRecord(w->e0, s));
+    LmOutcome out = {};
+    if (int rc = lba_rounds(q, a, h.D(q.orb), s, make_cam(p), a.D(q.ochio), a.at(q.oout), &out)) return rc;
+    ORB_TRY(hipEventRecord(w->e1, s));
+    if (int rc = lm_download(q, a, h, r->chi2 ? q.ochio : outlier ? q.oout : q.orb, s, w, out, r)) return rc;
+    h.get(outlier, q.oout, (size_t)q.NE);
+    return ORBX_OK;
+}
+
 extern "C" int orbba_local_bundle_adjustment_device(const orbba_problem *p, orbba_lm_result *r, uint8_t *d_outlier, void *stream)
 {
     if (!p || !r) return orbx_set_error(ORBX_E_ARG, "null argument");
     const int NP = p->n_poses, NL = p->n_points, NE = p->n_edges;
-    if (NP < 1 || NL < 1 || NE < 1) return orbx_set_error(ORBX_E_ARG, "bad sizes");
-    if (!p->pose_R || !p->pose_t || !p->pose_fixed || !p->points || !p->edge_pose || !p->edge_point || !p->edge_z || !p->edge_inv_sigma2 ||
-        !r->pose_R || !r->pose_t || !r->points || !r->chi2 || !d_outlier)
+    if (!ba_sizes_ok(p, 1)) return orbx_set_error(ORBX_E_ARG, "bad sizes");
+    if (!ba_arrays_ok(p) || !r->pose_R || !r->pose_t || !r->points || !r->chi2 || !d_outlier)
         return orbx_set_error(ORBX_E_ARG, "null array (every pointer is device memory here, chi2 and outlier included)");
     // the number of free poses is not known yet: the arena is sized for every pose free
     if ((size_t)NP * NL > (size_t)1 << 28) return orbx_set_error(ORBX_E_UNSUPPORTED, "poses x points table too large");
@@ -1144,31 +1122,30 @@ extern "C" int orbba_local_bundle_adjustment_device(const orbba_problem *p, orbb
     const LmPlan q0 = lm_plan(NP, NL, NE, NP);
     Lease<BaWork> lease(g_work);
     ORB_TRY(lease.acquire(device));
-    BaWork *w = lease.w;                 // its arena, staging block and events; the stream is the caller's
+    lease.stream = s;                    // the call runs on the caller's stream: that one is waited on before the arena goes back
+    BaWork *w = lease.w;                 // its arena, staging block and events
     ORB_TRY(w->need(q0.bytes, 8 * (size_t)q0.RB_N + 256));
-    uint8_t *d = w->d.as<uint8_t>();
+    const Arena a = {w->d.as<uint8_t>()};
     double *const rb = w->h.as<double>();
-    auto I = [&](size_t off) { return reinterpret_cast<int *>(d + off); };
-    auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
-    auto copy = [&](size_t off, const void *src, size_t bytes) { return hipMemcpyAsync(d + off, src, bytes, hipMemcpyDeviceToDevice, s); };
+    auto copy = [&](size_t off, const void *src, size_t bytes) { return hipMemcpyAsync(a.at(off), src, bytes, hipMemcpyDeviceToDevice, s); };
     ORB_TRY(copy(q0.oR, p->pose_R, 72 * (size_t)NP)); ORB_TRY(copy(q0.ot, p->pose_t, 24 * (size_t)NP)); ORB_TRY(copy(q0.oP, p->points, 24 * (size_t)NL));
     ORB_TRY(copy(q0.ofix, p->pose_fixed, NP)); ORB_TRY(copy(q0.oep, p->edge_pose, 4 * (size_t)NE)); ORB_TRY(copy(q0.oel, p->edge_point, 4 * (size_t)NE));
     ORB_TRY(copy(q0.oz, p->edge_z, 16 * (size_t)NE)); ORB_TRY(copy(q0.ow, p->edge_inv_sigma2, 8 * (size_t)NE));
     // ---- index structures and the host form's checks, on the device
-    ORB_TRY(hipMemsetAsync(d + q0.opo, 0, 4 * (size_t)(NP + 1), s));
-    ORB_TRY(hipMemsetAsync(d + q0.oix, 0, 64, s));
+    ORB_TRY(hipMemsetAsync(a.at(q0.opo), 0, 4 * (size_t)(NP + 1), s));
+    ORB_TRY(hipMemsetAsync(a.at(q0.oix), 0, 64, s));
     const int EB = q0.EB;
     const int fill_cap = (int)std::min<size_t>((size_t)NP * NL, (size_t)1 << 28);
-    hipLaunchKernelGGL(k_lmi_count, dim3(EB), dim3(256), 0, s, NP, NL, NE, I(q0.oep), I(q0.oel), I(q0.opo), I(q0.oix));
-    hipLaunchKernelGGL(k_lmi_poses, dim3(1), dim3(1024), 0, s, NP, d + q0.ofix, I(q0.opo), I(q0.ofree), I(q0.oslot), I(q0.oix));
-    hipLaunchKernelGGL(k_lmi_place, dim3(NP), dim3(256), 0, s, NE, I(q0.oep), I(q0.opo), I(q0.ope));
-    hipLaunchKernelGGL(k_lmi_fill, dim3(std::min((fill_cap + 255) / 256, 1024)), dim3(256), 0, s, NL, I(q0.oix), fill_cap, I(q0.oeo));
-    hipLaunchKernelGGL(k_lmi_cells, dim3(EB), dim3(256), 0, s, NP, NL, NE, I(q0.oep), I(q0.oel), I(q0.oslot), I(q0.oeo), I(q0.oix));
-    hipLaunchKernelGGL(k_lmi_points, dim3((NL + 256) / 256), dim3(256), 0, s, NL, NE, I(q0.oel), I(q0.olo));
+    hipLaunchKernelGGL(k_lmi_count, dim3(EB), dim3(256), 0, s, NP, NL, NE, a.I(q0.oep), a.I(q0.oel), a.I(q0.opo), a.I(q0.oix));
+    hipLaunchKernelGGL(k_lmi_poses, dim3(1), dim3(1024), 0, s, NP, a.at(q0.ofix), a.I(q0.opo), a.I(q0.ofree), a.I(q0.oslot), a.I(q0.oix));
+    hipLaunchKernelGGL(k_lmi_place, dim3(NP), dim3(256), 0, s, NE, a.I(q0.oep), a.I(q0.opo), a.I(q0.ope));
+    hipLaunchKernelGGL(k_lmi_fill, dim3(std::min((fill_cap + 255) / 256, 1024)), dim3(256), 0, s, NL, a.I(q0.oix), fill_cap, a.I(q0.oeo));
+    hipLaunchKernelGGL(k_lmi_cells, dim3(EB), dim3(256), 0, s, NP, NL, NE, a.I(q0.oep), a.I(q0.oel), a.I(q0.oslot), a.I(q0.oeo), a.I(q0.oix));
+    hipLaunchKernelGGL(k_lmi_points, dim3((NL + 256) / 256), dim3(256), 0, s, NL, NE, a.I(q0.oel), a.I(q0.olo));
     ORB_TRY(hipGetLastError());
     // the first read-back: the checks' verdict and the number of free poses, which sizes the reduced system
     int *const ix = reinterpret_cast<int *>(rb);
-    ORB_TRY(hipMemcpyAsync(ix, d + q0.oix, 64, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(ix, a.at(q0.oix), 64, hipMemcpyDeviceToHost, s));
     ORB_TRY(hipStreamSynchronize(s));
     const int flag = ix[LMI_FLAG], NF = ix[LMI_NF];
     if (flag & LMI_E_RANGE) return orbx_set_error(ORBX_E_ARG, "edge index out of range");
@@ -1176,35 +1153,17 @@ extern "C" int orbba_local_bundle_adjustment_device(const orbba_problem *p, orbb
     if (flag & LMI_E_ALL_FIXED || NF < 1 || NF > NP) return orbx_set_error(ORBX_E_ARG, "every pose is fixed: nothing to optimise");
     if (flag & LMI_E_TWICE) return orbx_set_error(ORBX_E_ARG, "a point is observed twice by the same key frame");
     const LmPlan q = lm_plan(NP, NL, NE, NF);                      // the same offsets up to edge_of; the scratch behind it is smaller
-    BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
     ORB_TRY(hipEventRecord(w->e0, s));
-    orbba_lm_options o1 = {}, o2 = {};
-    o1.max_iterations = 5;               // optimizer.optimize(5), :893
-    o2.max_iterations = 10;              // :909
-    LmOutcome out1 = {}, out2 = {};
-    if (int rc = lm_loop(q, d, rb, s, cam, nullptr, lm_knobs(&o1), &out1)) return rc;
-    hipLaunchKernelGGL(k_lba_demote, dim3(EB), dim3(256), 0, s, NE, D(q.ochi), d + q.oact, D(q.ochi1));   // :899-902
-    cam.delta = 0.0;                     // setRobustKernel(nullptr), :904
-    if (int rc = lm_loop(q, d, rb, s, cam, d + q.oact, lm_knobs(&o2), &out2)) return rc;
-    hipLaunchKernelGGL(k_lba_outliers, dim3(EB), dim3(256), 0, s, NE, D(q.ochi), d + q.oact, D(q.ochi1), r->chi2, d_outlier);
-    ORB_TRY(hipGetLastError());
-    ORB_TRY(hipMemcpyAsync(r->pose_R, d + q.oR, 72 * (size_t)NP, hipMemcpyDeviceToDevice, s));
-    ORB_TRY(hipMemcpyAsync(r->pose_t, d + q.ot, 24 * (size_t)NP, hipMemcpyDeviceToDevice, s));
-    ORB_TRY(hipMemcpyAsync(r->points, d + q.oP, 24 * (size_t)NL, hipMemcpyDeviceToDevice, s));
+    LmOutcome out = {};
+    if (int rc = lba_rounds(q, a, rb, s, make_cam(p), r->chi2, d_outlier, &out)) return rc;
+    ORB_TRY(hipMemcpyAsync(r->pose_R, a.at(q.oR), 72 * (size_t)NP, hipMemcpyDeviceToDevice, s));
+    ORB_TRY(hipMemcpyAsync(r->pose_t, a.at(q.ot), 24 * (size_t)NP, hipMemcpyDeviceToDevice, s));
+    ORB_TRY(hipMemcpyAsync(r->points, a.at(q.oP), 24 * (size_t)NL, hipMemcpyDeviceToDevice, s));
     ORB_TRY(hipEventRecord(w->e1, s));
-    ORB_TRY(hipMemcpyAsync(rb, d + q.orb, 8 * (size_t)q.RB_N, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(rb, a.at(q.orb), 8 * (size_t)q.RB_N, hipMemcpyDeviceToHost, s));
     ORB_TRY(hipStreamSynchronize(s));    // the arena goes back to the pool: nothing of this call may still be running
-    float ms = 0;
-    ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
-    r->iterations = out1.iterations + out2.iterations;
-    r->trials = out1.trials + out2.trials;
-    r->lambda = out2.lambda;
-    r->chi2_initial = out1.chi_initial;
-    r->chi2_final = lm_sum(rb, q.RB_TRY, q.EB);
-    r->device_ms = ms;
-    return ORBX_OK;
+    return lm_report(q, rb, w, out, r);
 }
-
 
 // =====================================================================================================================
 // Optimize::poseOptimize (modules/Backend/Optimize.cpp:444-545) for a batch of frames: one workgroup runs one frame's
@@ -1521,33 +1480,29 @@ extern "C" int orbba_pose_optimize_batch(const orbba_pose_problem *p, orbba_pose
     BaWork *w = lease.w;
     ORB_TRY(w->need(L.n, std::max(in_bytes, out_end - in_bytes)));
     hipStream_t s = w->stream;
-    uint8_t *d = w->d.as<uint8_t>(), *h = w->h.as<uint8_t>();
-    put(h, ooff, p->edge_off, 4 * (size_t)(B + 1)); put(h, oR0, p->pose_R, 72 * (size_t)B); put(h, ot0, p->pose_t, 24 * (size_t)B);
-    if (NE) { put(h, oP, p->points, 24 * (size_t)NE); put(h, oz, p->edge_z, 16 * (size_t)NE); put(h, ow, p->edge_inv_sigma2, 8 * (size_t)NE); }
-    ORB_TRY(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
-    const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
-    auto D = [&](size_t off) { return reinterpret_cast<double *>(d + off); };
+    const Arena a = {w->d.as<uint8_t>()}, h = {w->h.as<uint8_t>()};
+    h.put(ooff, p->edge_off, 4 * (size_t)(B + 1)); h.put(oR0, p->pose_R, 72 * (size_t)B); h.put(ot0, p->pose_t, 24 * (size_t)B);
+    h.put(oP, p->points, 24 * (size_t)NE); h.put(oz, p->edge_z, 16 * (size_t)NE); h.put(ow, p->edge_inv_sigma2, 8 * (size_t)NE);
+    ORB_TRY(hipMemcpyAsync(a.base, h.base, in_bytes, hipMemcpyHostToDevice, s));
+    const BaCam cam = make_cam(p);
     ORB_TRY(hipEventRecord(w->e0, s));
     int max_n = 0;
     for (int f = 0; f < B; ++f) max_n = std::max(max_n, p->edge_off[f + 1] - p->edge_off[f]);
     const int cap = std::min(pose_lds_cap(), max_n); // (no more LDS than the largest frame needs: more workgroups per CU for a big batch)
     ORB_TRY(pose_lds_configure(cap));
     hipLaunchKernelGGL(k_pose_optimize, dim3(B), dim3(256), pose_lds_bytes(cap), s, cam, p->rounds > 0 ? p->rounds : 4,
-                       p->iterations > 0 ? p->iterations : 10, cap, reinterpret_cast<int *>(d + ooff), D(oR0), D(ot0), D(oP), D(oz), D(ow),
-                       D(oR), D(ot), d + oin, reinterpret_cast<int *>(d + oni), D(ochi));
+                       p->iterations > 0 ? p->iterations : 10, cap, a.I(ooff), a.D(oR0), a.D(ot0), a.D(oP), a.D(oz), a.D(ow), a.D(oR), a.D(ot),
+                       a.at(oin), a.I(oni), a.D(ochi));
     ORB_TRY(hipEventRecord(w->e1, s));
     ORB_TRY(hipGetLastError());
-    ORB_TRY(hipMemcpyAsync(h, d + in_bytes, out_end - in_bytes, hipMemcpyDeviceToHost, s));
+    ORB_TRY(hipMemcpyAsync(h.base, a.at(in_bytes), out_end - in_bytes, hipMemcpyDeviceToHost, s));
     ORB_TRY(hipStreamSynchronize(s));
     float ms = 0;
     ORB_TRY(hipEventElapsedTime(&ms, w->e0, w->e1));
     r->kernel_ms = ms;
-    auto O = [&](size_t off) { return h + (off - in_bytes); }; // a result's place in the staging block
-    memcpy(r->pose_R, O(oR), 72 * (size_t)B);
-    memcpy(r->pose_t, O(ot), 24 * (size_t)B);
-    memcpy(r->n_inliers, O(oni), 4 * (size_t)B);
-    if (NE) memcpy(r->inlier, O(oin), NE);
-    if (NE && r->chi2) memcpy(r->chi2, O(ochi), 8 * (size_t)NE);
+    // a result's place in the staging block is its place in the arena behind the inputs
+    h.get(r->pose_R, oR - in_bytes, 72 * (size_t)B); h.get(r->pose_t, ot - in_bytes, 24 * (size_t)B); h.get(r->n_inliers, oni - in_bytes, 4 * (size_t)B);
+    h.get(r->inlier, oin - in_bytes, NE); h.get(r->chi2, ochi - in_bytes, 8 * (size_t)NE);
     return ORBX_OK;
 }
 
@@ -1596,6 +1551,7 @@ extern "C" int orbba_pose_edges_device(int n2, int nq, const int32_t *d_frame_mp
 {
     if (n2 < 0 || nq < 0 || !d_frame_mp || !d_kps || !d_q_points || !d_edge_off || !d_points || !d_edge_z || !d_edge_inv_sigma2)
         return orbx_set_error(ORBX_E_ARG, "bad argument");
+    if (int rc = orb_need_device()) return rc;
     hipLaunchKernelGGL(k_pose_edges, dim3(1), dim3(1024), 0, (hipStream_t)stream, n2, nq, d_frame_mp, (const orbx_kp *)d_kps,
                        d_q_points, d_edge_off, d_points, d_edge_z, d_edge_inv_sigma2, d_edge_kp);
     ORB_TRY(hipGetLastError());
@@ -1629,7 +1585,8 @@ extern "C" int orbba_pose_optimize_batch_device(const orbba_pose_problem *p, orb
     if (p->n_frames < 1 || !p->edge_off || !p->pose_R || !p->pose_t || !p->points || !p->edge_z || !p->edge_inv_sigma2 ||
         !r->pose_R || !r->pose_t || !r->n_inliers || !r->inlier || !r->chi2)
         return orbx_set_error(ORBX_E_ARG, "null array (every pointer is device memory here, chi2 included)");
-    const BaCam cam = make_cam(p->fx, p->fy, p->cx, p->cy, p->huber_delta, p->camera_model, p->fisheye_k);
+    if (int rc = orb_need_device()) return rc;
+    const BaCam cam = make_cam(p);
     const int cap = pose_lds_cap(); // (the edge counts are on the device: the full capacity, one workgroup per CU)
     ORB_TRY(pose_lds_configure(cap));
     hipLaunchKernelGGL(k_pose_optimize, dim3(p->n_frames), dim3(256), pose_lds_bytes(cap), (hipStream_t)stream, cam, p->rounds > 0 ? p->rounds : 4,

@@ -170,6 +170,61 @@ def test_gpu_local_bundle_adjustment_rejects_outliers():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("chol", ["lds", "global"])
+@pytest.mark.parametrize("scene", ["easy", "first_round_rejects"])
+def test_gpu_local_bundle_adjustment_equals_its_composition(scene, chol):
+    """orbba_local_bundle_adjustment runs both rounds of Optimize.cpp:892-922 in one arena behind one upload.  What it returns equals,
+    BYTE FOR BYTE, the same rounds composed through the public API: optimize(5); the mask !(chi2 > 5.991); optimize(10) without the robust
+    kernel on that mask, from the first round's estimates; the first round's chi2 kept for the demoted edges; the outlier rule; iterations
+    and trials summed; chi2_initial of the first round.  No tolerance: the same kernels run in the same order on the same index arrays."""
+    from monoorbslam3_amd import ba
+    if scene == "easy":
+        args = _perturbed(4, 40, 3, outliers=4)[1]
+    else:
+        from test_ba_lm_paths import _local_ba_args
+        args = _local_ba_args()
+    ba.set_variant("chol", chol)  # read per call
+    try:
+        got = ba.local_bundle_adjustment(*args)
+        r1 = ba.optimize(*args, iterations=5)
+        mask = ~(r1["chi2"] > 5.991)
+        r2 = ba.optimize(args[0], r1["pose_R"], r1["pose_t"], args[3], r1["points"], *args[5:], huber_delta=0.0, iterations=10, edge_active=mask)
+    finally:
+        ba.set_variant("chol", "lds")
+    chi2 = np.where(mask, r2["chi2"], r1["chi2"])
+    print("%s %s: rounds %d / %d and %d / %d, %d demoted, %d outliers" % (scene, chol, r1["iterations"], r1["trials"], r2["iterations"], r2["trials"],
+                                                                       (~mask).sum(), got["outlier"].sum()))
+    assert (~mask).any() and mask.any()
+    if scene == "first_round_rejects":
+        assert r1["trials"] > r1["iterations"]
+    for k in ("pose_R", "pose_t", "points"):
+        assert got[k].tobytes() == r2[k].tobytes(), k
+    assert got["chi2"].tobytes() == chi2.tobytes()
+    assert np.array_equal(got["outlier"], ~mask | (chi2 > 5.991))
+    assert (got["iterations"], got["trials"]) == (r1["iterations"] + r2["iterations"], r1["trials"] + r2["trials"])
+    for k, want in (("lam", r2["lam"]), ("chi2_initial", r1["chi2_initial"]), ("chi2_final", r2["chi2_final"])):
+        assert np.float64(got[k]).tobytes() == np.float64(want).tobytes(), k
+
+
+@pytest.mark.gpu
+def test_gpu_local_bundle_adjustment_takes_null_outputs():
+    """the C call with outlier, r->chi2 and r->pose_R NULL: OK, and pose_t, points and the scalars are the full call's bytes"""
+    import ctypes as C
+    from monoorbslam3_amd import ba
+    _, args = _perturbed(3, 10, 1)
+    full = ba.local_bundle_adjustment(*args)
+    prob, keep = ba._problem(*args, ba.HUBER_MONO)
+    out, res = ba._lm_out(prob)
+    res.pose_R = res.chi2 = None
+    assert ba._L().orbba_local_bundle_adjustment(C.byref(prob), C.byref(res), None, -1) == 0
+    assert out["pose_t"].tobytes() == full["pose_t"].tobytes() and out["points"].tobytes() == full["points"].tobytes()
+    assert not out["pose_R"].any() and not out["chi2"].any()      # as passed
+    assert (res.iterations, res.trials) == (full["iterations"], full["trials"])
+    for k in ("lam", "chi2_initial", "chi2_final"):
+        assert np.float64(getattr(res, k)).tobytes() == np.float64(full[k]).tobytes(), k
+
+
+@pytest.mark.gpu
 def test_gpu_lm_argument_errors():
     from monoorbslam3_amd import ba
     pr, args = _perturbed(4, 30, 2)

@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 rm -rf /tmp/ktb
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktb -o r -- python3 tools/ba_latency.py > /tmp/ba.out 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ktb -o r -- python3 tools/ba_latency.py /tmp/ba_latency.txt > /tmp/ba.out 2>&1
 tail -3 /tmp/ba.out
 python3 - <<EOF
 import csv,glob
