@@ -51,8 +51,7 @@
  *
  * The edge.  The pose derivation from (R_wb, t_wb), Pc, the error, chi2, project / getProjJacobian (csrc/orbba_camera.h), the float
  * t_bc and the 2 x 6 pose Jacobian J_p are EXACTLY those of orbvi.h ("Arithmetic": the pose, the edge, Jacobian), evaluated per edge.
- * They are restated in csrc/orbvw.hip, not shared through a header: k_vi_linearize's 126 VGPRs of 128 rest on the exact shape of its
- * loops, and moving its text would put the figures orbvi.h states at risk.  The point Jacobian is
+ * Both kernels take them from one internal header, csrc/orbi_graph_device.h.  The point Jacobian is
  *   J_l = (-Jp)*R_cw,  (J_l)_rc = ((-Jp_r0)*R_0c + (-Jp_r1)*R_1c) + (-Jp_r2)*R_2c.
  * Huber is the one of orbi.h (huber_delta > 0; chi2 > delta*delta: rho = (2*sqrt(chi2))*delta - delta*delta, w = delta/sqrt(chi2); else rho =
  * chi2, w = 1).  W = w*inv_sigma2, We = (W*ex, W*ey).  With A, B each J_p or J_l: (A^T W B)_ab = A_0a*(W*B_0b) + A_1a*(W*B_1b) and

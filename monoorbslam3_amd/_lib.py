@@ -25,13 +25,24 @@ class OrbxError(RuntimeError):
         self.code = code
 
 
-_lib = None
+def binder(sigs, load=None):
+    """The bind-once accessor of a module's entry points: sigs maps a name to its argtypes (restype c_int) or to (restype, argtypes).
+    The first call loads the library (`load`, by default lib()) and sets every signature -- a name the library does not export raises
+    AttributeError there, and the next call tries again; every later call returns the same library and sets nothing."""
+    bound = []
+
+    def get():
+        if not bound:
+            L = (load or lib)()
+            for name, sig in sigs.items():
+                fn = getattr(L, name)  # AttributeError if the library does not export it
+                fn.restype, fn.argtypes = sig if isinstance(sig, tuple) else (C.c_int, sig)
+            bound.append(L)
+        return bound[0]
+    return get
 
 
-def lib():
-    global _lib
-    if _lib is not None:
-        return _lib
+def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(there is no CPU fallback)" % LIB_PATH)
@@ -41,41 +52,38 @@ def lib():
         import torch  # noqa: F401
     except Exception:  # a pure C/C++ consumer without torch is fine
         pass
-    L = C.CDLL(LIB_PATH)
-    vp, i32, f32, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    sigs = {
-        "orbx_create": (i32, [C.POINTER(OrbxCfg), C.POINTER(vp)]),
-        "orbx_create_requota": (i32, [vp, i32, C.POINTER(vp)]),
-        "orbx_destroy": (None, [vp]),
-        "orbx_tables": (i32, [vp, C.POINTER(i32), vp, vp, vp, vp, C.POINTER(f32), vp, vp]),
-        "orbx_level_size": (i32, [vp, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
-        "orbx_max_keypoints": (i32, [vp, i32, i32]),
-        "orbx_extract": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, C.POINTER(i32)]),
-        "orbx_extract_batch": (i32, [vp, vp, i32, i32, i32, i32, sz, vp, vp, i32, vp]),
-        "orbx_extract_batch_device": (i32, [vp, vp, i32, i32, i32, i32, sz, vp, vp, i32, vp, vp]),
-        "orbx_synchronize": (i32, [vp]),
-        "orbx_host_register": (i32, [vp, sz]),
-        "orbx_host_unregister": (i32, [vp]),
-        "orbx_stream_wait_fast": (i32, [vp, vp]),
-        "orbx_tap_level": (i32, [vp, i32, i32, i32, vp, sz]),
-        "orbx_tap_candidates": (i32, [vp, i32, i32, vp, vp, vp, i32, C.POINTER(i32)]),
-        "orbx_tap_level_counts": (i32, [vp, i32, vp]),
-        "orbx_tap_sincos": (i32, [vp, vp, i32, vp]),
-        "orbx_set_variant": (i32, [vp, i32, i32]),
-        "orbx_get_variant": (i32, [vp, i32, C.POINTER(i32)]),
-        "orbx_set_stage_timing": (i32, [vp, i32]),
-        "orbx_fast_times_in_step_ms": (i32, [vp, C.POINTER(f32), C.POINTER(i32)]),
-        "orbx_stage_times_ms": (i32, [vp, vp]),
-        "orbx_stage_times_in_step_ms": (i32, [vp, vp]),
-        "orbx_last_error": (C.c_char_p, []),
-        "orbx_version": (C.c_char_p, []),
-    }
-    for name, (res, args) in sigs.items():
-        fn = getattr(L, name)  # AttributeError if the library does not export it
-        fn.restype = res
-        fn.argtypes = args
-    _lib = L
-    return L
+    return C.CDLL(LIB_PATH)
+
+
+_vp, _i32, _f32, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_SIGS = {
+    "orbx_create": (_i32, [C.POINTER(OrbxCfg), C.POINTER(_vp)]),
+    "orbx_create_requota": (_i32, [_vp, _i32, C.POINTER(_vp)]),
+    "orbx_destroy": (None, [_vp]),
+    "orbx_tables": (_i32, [_vp, C.POINTER(_i32), _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _vp]),
+    "orbx_level_size": (_i32, [_vp, _i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "orbx_max_keypoints": (_i32, [_vp, _i32, _i32]),
+    "orbx_extract": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32)]),
+    "orbx_extract_batch": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _sz, _vp, _vp, _i32, _vp]),
+    "orbx_extract_batch_device": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _sz, _vp, _vp, _i32, _vp, _vp]),
+    "orbx_synchronize": (_i32, [_vp]),
+    "orbx_host_register": (_i32, [_vp, _sz]),
+    "orbx_host_unregister": (_i32, [_vp]),
+    "orbx_stream_wait_fast": (_i32, [_vp, _vp]),
+    "orbx_tap_level": (_i32, [_vp, _i32, _i32, _i32, _vp, _sz]),
+    "orbx_tap_candidates": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _i32, C.POINTER(_i32)]),
+    "orbx_tap_level_counts": (_i32, [_vp, _i32, _vp]),
+    "orbx_tap_sincos": (_i32, [_vp, _vp, _i32, _vp]),
+    "orbx_set_variant": (_i32, [_vp, _i32, _i32]),
+    "orbx_get_variant": (_i32, [_vp, _i32, C.POINTER(_i32)]),
+    "orbx_set_stage_timing": (_i32, [_vp, _i32]),
+    "orbx_fast_times_in_step_ms": (_i32, [_vp, C.POINTER(_f32), C.POINTER(_i32)]),
+    "orbx_stage_times_ms": (_i32, [_vp, _vp]),
+    "orbx_stage_times_in_step_ms": (_i32, [_vp, _vp]),
+    "orbx_last_error": (C.c_char_p, []),
+    "orbx_version": (C.c_char_p, []),
+}
+lib = binder(_SIGS, _load)
 
 
 def check(rc):

@@ -158,32 +158,19 @@ class _PoseResult(C.Structure):
                 ("chi2", C.c_void_p), ("kernel_ms", C.c_float)]
 
 
-_sigs_done = False
-
-
-def _L():
-    """the library with the orbba_* signatures set, once (include/orbba.h)"""
-    global _sigs_done
-    L = _lib.lib()
-    if not _sigs_done:
-        vp, i32, ptr = C.c_void_p, C.c_int, C.POINTER
-        sigs = {
-            "orbba_set_variant": [i32, i32],
-            "orbba_linearize": [ptr(_Problem), ptr(_Result), i32],
-            "orbba_optimize": [ptr(_Problem), ptr(_LmOptions), ptr(_LmResult), i32],
-            "orbba_local_bundle_adjustment": [ptr(_Problem), ptr(_LmResult), vp, i32],
-            "orbba_local_bundle_adjustment_device": [ptr(_Problem), ptr(_LmResult), vp, vp],
-            "orbba_pose_optimize_batch": [ptr(_PoseProblem), ptr(_PoseResult), i32],
-            "orbba_pose_optimize_batch_device": [ptr(_PoseProblem), ptr(_PoseResult), vp],
-            "orbba_pose_edges_device": [i32, i32] + [vp] * 9,
-            "orbba_pose_drop_outliers_device": [i32] + [vp] * 5,
-        }
-        for name, args in sigs.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype = i32
-            fn.argtypes = args
-        _sigs_done = True
-    return L
+_vp, _i32, _ptr = C.c_void_p, C.c_int, C.POINTER
+_SIGS = {
+    "orbba_set_variant": [_i32, _i32],
+    "orbba_linearize": [_ptr(_Problem), _ptr(_Result), _i32],
+    "orbba_optimize": [_ptr(_Problem), _ptr(_LmOptions), _ptr(_LmResult), _i32],
+    "orbba_local_bundle_adjustment": [_ptr(_Problem), _ptr(_LmResult), _vp, _i32],
+    "orbba_local_bundle_adjustment_device": [_ptr(_Problem), _ptr(_LmResult), _vp, _vp],
+    "orbba_pose_optimize_batch": [_ptr(_PoseProblem), _ptr(_PoseResult), _i32],
+    "orbba_pose_optimize_batch_device": [_ptr(_PoseProblem), _ptr(_PoseResult), _vp],
+    "orbba_pose_edges_device": [_i32, _i32] + [_vp] * 9,
+    "orbba_pose_drop_outliers_device": [_i32] + [_vp] * 5,
+}
+_L = _lib.binder(_SIGS)   # the library with the orbba_* signatures set, once (include/orbba.h)
 
 
 def pose_optimize_batch(cam, pose_R, pose_t, edge_off, points, edge_z, edge_inv_sigma2, huber_delta=HUBER_MONO, device=-1):

@@ -66,6 +66,25 @@ __device__ __forceinline__ void block_add(int *s_count, int slot, int v)
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_count[slot], v);
 }
 
+// N per-thread floating-point sums over a workgroup of WAVES waves in a fixed order, so that the same input gives the same bytes and no
+// floating-point atomic is needed.  block_sums_put: the butterfly over the wave, then lane 0 leaves sum k of [first, last) (uniform) in
+// s_part[wave][k]; the caller's barrier follows; block_sums_get: sum k of the workgroup, the wave slots added in ascending order
+template <int WAVES, int N> __device__ __forceinline__ void block_sums_put(const double (&acc)[N], double (&s_part)[WAVES][N], int first = 0, int last = N)
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if (k < first || k >= last) continue;
+        const double v = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6][k] = v;
+    }
+}
+template <int WAVES, int N> __device__ __forceinline__ double block_sums_get(const double (&s_part)[WAVES][N], int k)
+{
+    double s = 0.0;
+    for (int w = 0; w < WAVES; ++w) s = s + s_part[w][k];
+    return s;
+}
+
 // Lanes of ONE wave write LDS that other lanes of the same wave read in the next step.  The LDS pipe serves a wave's accesses in
 // issue order, so the hardware needs nothing; this keeps the COMPILER from moving a later lane's read above an earlier lane's write
 // (a fence at wavefront scope and a wave barrier emit no instruction).

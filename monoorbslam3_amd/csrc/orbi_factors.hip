@@ -26,6 +26,7 @@
 #include "../../include/orbx.h"
 #include "orb_host.h"
 #include "orb_math.h"
+#include "orbi_graph_device.h"
 #include "orbi_so3.h"
 
 #pragma clang fp contract(off)
@@ -35,7 +36,6 @@ static_assert(sizeof(orbi_edge) == 16 && sizeof(orbi_prior) == 144 && sizeof(orb
 
 namespace {
 
-__device__ __forceinline__ double dsum3(double p0, double p1, double p2) { return ORB_DADD(ORB_DADD(p0, p1), p2); }
 __device__ __forceinline__ double dmul(double a, double b) { return ORB_DMUL(a, b); }
 // entries (i, j) of A*B, A^T*B, A*B^T, A^T*B^T and (s*hat(x,y,z))*hat(x,y,z); matrices row-major
 __device__ __forceinline__ double dm3(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[3 * i], B[j]), dmul(A[3 * i + 1], B[3 + j]), dmul(A[3 * i + 2], B[6 + j])); }
@@ -455,8 +455,6 @@ __device__ __forceinline__ double jac_entry(const double *S, double dt, int r, i
     if (cb == 6) return S[D_RR + 3 * i + j];                           // Rb1w*R2
     return 0.0;
 }
-
-__device__ __forceinline__ bool dof_fixed(int fixed, int dof) { return (fixed >> (dof < 6 ? 0 : dof / 3 - 1)) & 1; }
 
 __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
 {

@@ -4,7 +4,7 @@
 //   orbvi_solve_device       (H + lambda*I)*dx = b of g2o's BlockSolverX with nothing marginalised                  Optimize.cpp:613-615
 //
 // Everything is IEEE double in the header's orders without fused multiply-add; the camera is csrc/orbba_camera.h, the one orbba.hip
-// evaluates.
+// evaluates; the edge's pose path, quadratic form and host checks are csrc/orbi_graph_device.h's.
 //
 // Shape: both calls are latency-bound.  A group of edges (the tracker has one, of a few hundred to 2000) is ONE 1024-thread workgroup,
 // like k_project and k_triangulate: a thread takes the edges t, t + 1024, ... and keeps its 21 + 6 + 2 partial sums in registers; a
@@ -23,15 +23,13 @@
 #include "orb_host.h"
 #include "orb_math.h"
 #include "orbba_camera.h"
+#include "orbi_graph_device.h"
 
 #pragma clang fp contract(off)
 
 static_assert(sizeof(orbvi_camera) == 72, "orbvi.h fixes this layout");
 
 namespace {
-
-__device__ __forceinline__ double dsum3(double p0, double p1, double p2) { return (p0 + p1) + p2; }
-__device__ __forceinline__ bool dof_fixed(int fixed, int dof) { return (fixed >> (dof < 6 ? 0 : dof / 3 - 1)) & 1; }
 
 // per-workgroup counters -> d_result: one workgroup writes, several add to what k_vi_clear zeroed ahead of them on the stream
 __global__ void k_vi_clear(int32_t *__restrict__ result)
@@ -41,7 +39,7 @@ __global__ void k_vi_clear(int32_t *__restrict__ result)
 
 // ---- orbvi_linearize_device: a 1024-thread workgroup per group ---------------------------------------------------------------------------
 constexpr int VI_T = 1024, VI_WAVES = VI_T / 64;
-enum { S_H = 0, S_G = 21, S_PLAIN = 27, S_ROBUST = 28, VI_SUMS = 29 };
+enum { S_PLAIN = 27, S_ROBUST = 28, VI_SUMS = 29 };    // behind quad_accumulate's 21 + 6
 enum { P_RCW = 0, P_TCW = 9, P_RCB = 12, P_TBC = 21, P_WORDS = 24 };
 enum { W_J = 0, W_W = 12, W_WE = 13, W_USED = 15 };   // an edge's workspace: J (2 x 6), w*Omega, (w*Omega)*e, 1.0 when the edge takes part
 static_assert(W_USED + 1 == ORBVI_EDGE_WORK, "orbvi.h states the workspace of an edge");
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(VI_T) void k_vi_linearize(const ViArgs a)
     __shared__ double s_pose[P_WORDS];
     __shared__ int s_cnt[8];
     __shared__ int s_i[I_WORDS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, g = blockIdx.x;
+    const int t = threadIdx.x, lane = t & 63, g = blockIdx.x;
     if (t < 8) s_cnt[t] = 0;
     if (t < I_WORDS) s_i[t] = 0;
     __syncthreads();
@@ -102,23 +100,13 @@ __global__ __launch_bounds__(VI_T) void k_vi_linearize(const ViArgs a)
     }
     // the pose the edges hang on, derived from (R_wb, t_wb) on every call, and the calibration widened
     if (t < 9) {
-        const int i = t / 3, j = t - 3 * i;
-        const double *Rwb = a.g.Rwb + 9 * (size_t)st;
-        s_pose[P_RCW + t] = dsum3((double)a.cal.Rcb[3 * i] * Rwb[3 * j], (double)a.cal.Rcb[3 * i + 1] * Rwb[3 * j + 1], (double)a.cal.Rcb[3 * i + 2] * Rwb[3 * j + 2]);
+        s_pose[P_RCW + t] = pose_rcw(a.cal, a.g.Rwb + 9 * (size_t)st, t);
         s_pose[P_RCB + t] = (double)a.cal.Rcb[t];
-    } else if (t < 12) {              // t_bc: the float Pose::inverse of T_cb
-        const int i = t - 9;
-        const float p0 = ORB_FMUL(-a.cal.Rcb[i], a.cal.tcb[0]), p1 = ORB_FMUL(-a.cal.Rcb[3 + i], a.cal.tcb[1]), p2 = ORB_FMUL(-a.cal.Rcb[6 + i], a.cal.tcb[2]);
-        s_pose[P_TBC + i] = (double)ORB_FADD(ORB_FADD(p0, p1), p2);
-    }
+    } else if (t < 12) s_pose[P_TBC + t - 9] = pose_tbc(a.cal, t - 9);
     __syncthreads();
-    if (t < 3) {
-        const double *twb = a.g.twb + 3 * (size_t)st;
-        s_pose[P_TCW + t] = (double)a.cal.tcb[t] - dsum3(s_pose[P_RCW + 3 * t] * twb[0], s_pose[P_RCW + 3 * t + 1] * twb[1], s_pose[P_RCW + 3 * t + 2] * twb[2]);
-    }
+    if (t < 3) s_pose[P_TCW + t] = pose_tcw(a.cal, s_pose + P_RCW, a.g.twb + 3 * (size_t)st, t);
     __syncthreads();
     const bool accumulate = a.mode == 0 && !(a.g.fixed[st] & ORBI_FIX_POSE);
-    const double dsqr = a.cam.delta * a.cam.delta;
     double plain = 0.0, robust = 0.0;
     int n_bad = 0, n_in = 0;
     for (int e = lo + t; e < hi; e += VI_T) {
@@ -154,11 +142,8 @@ __global__ __launch_bounds__(VI_T) void k_vi_linearize(const ViArgs a)
             ++n_bad;
             continue;
         }
-        double rho = chi, rw = 1.0;
-        if (cam.delta > 0.0 && chi > dsqr) {
-            const double sq = sqrt(chi);
-            rho = (2.0 * sq) * cam.delta - dsqr, rw = cam.delta / sq;
-        }
+        double rho, rw;
+        huber(chi, cam.delta, rho, rw);
         plain = plain + chi, robust = robust + rho;
         if (!accumulate) continue;
         // left for the next pass: the weights and Pc (in the Jacobian's first slots)
@@ -168,7 +153,7 @@ __global__ __launch_bounds__(VI_T) void k_vi_linearize(const ViArgs a)
     }
     // Three passes, each thread over its own edges and through its own workspace rows: the camera's Jacobian (the Kannala-Brandt one
     // with its atan2 is the largest block of the kernel) is live neither beside the projection nor beside the 27 sums.
-    // linearizeOplus: J = [(-Jp)*(R_cb*Hat(R_bc*Pc + t_bc)), (-Jp)*(-R_cb)]
+    // linearizeOplus, Pc replaced by the Jacobian
     for (int e = lo + t; accumulate && e < hi; e += VI_T) {
         double *work = a.work + (size_t)ORBVI_EDGE_WORK * e;
         if (work[W_USED] == 0.0) continue;
@@ -177,23 +162,9 @@ __global__ __launch_bounds__(VI_T) void k_vi_linearize(const ViArgs a)
         asm volatile("" : "+v"(pose));
         asm volatile("" : "+s"(cam.fx), "+s"(cam.fy), "+s"(cam.cx), "+s"(cam.cy), "+s"(cam.k[0]), "+s"(cam.k[1]), "+s"(cam.k[2]), "+s"(cam.k[3]));
         const double X = work[W_J], Y = work[W_J + 1], Z = work[W_J + 2];
-        const double *C = pose + P_RCB;
         double Jp[6];
         ba_proj_jacobian(cam, X, Y, Z, Jp);
-        const double bx = dsum3(C[0] * X, C[3] * Y, C[6] * Z) + pose[P_TBC];
-        const double by = dsum3(C[1] * X, C[4] * Y, C[7] * Z) + pose[P_TBC + 1];
-        const double bz = dsum3(C[2] * X, C[5] * Y, C[8] * Z) + pose[P_TBC + 2];
-        const double Hb[9] = {0.0, -bz, by, bz, 0.0, -bx, -by, bx, 0.0};
-        double M[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) M[k] = dsum3(C[3 * (k / 3)] * Hb[k % 3], C[3 * (k / 3) + 1] * Hb[3 + k % 3], C[3 * (k / 3) + 2] * Hb[6 + k % 3]);
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                work[W_J + 6 * r + c] = dsum3(-Jp[3 * r] * M[c], -Jp[3 * r + 1] * M[3 + c], -Jp[3 * r + 2] * M[6 + c]);
-                work[W_J + 6 * r + 3 + c] = dsum3(-Jp[3 * r] * -C[c], -Jp[3 * r + 1] * -C[3 + c], -Jp[3 * r + 2] * -C[6 + c]);
-            }
+        pose_jacobian(pose + P_RCB, pose + P_TBC, Jp, X, Y, Z, work + W_J);
     }
     double acc[VI_SUMS];
 #pragma unroll
@@ -203,44 +174,17 @@ __global__ __launch_bounds__(VI_T) void k_vi_linearize(const ViArgs a)
         for (int e = lo + t; e < hi; e += VI_T) {
             const double *work = a.work + (size_t)ORBVI_EDGE_WORK * e;
             if (work[W_USED] == 0.0) continue;
-            double J[12];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) J[k] = work[W_J + k];
-            const double W = work[W_W], wex = work[W_WE], wey = work[W_WE + 1];
-            int k = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = r; c < 6; ++c, ++k) acc[S_H + k] = acc[S_H + k] + (J[r] * (W * J[c]) + J[6 + r] * (W * J[6 + c]));
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[S_G + r] = acc[S_G + r] + (J[r] * wex + J[6 + r] * wey);
+            quad_accumulate(work + W_J, work[W_W], work[W_WE], work[W_WE + 1], acc);
         }
     }
-    // the butterfly over the wave, then the sixteen wave results in ascending order
-#pragma unroll
-    for (int k = 0; k < VI_SUMS; ++k) {
-        if (k < S_PLAIN && !accumulate) continue;
-        const double v = wave_sum(acc[k]);
-        if (lane == 0) s_part[wave][k] = v;
-    }
+    block_sums_put(acc, s_part, accumulate ? 0 : S_PLAIN);
     block_add(s_cnt, ORBVI_R_NONFINITE, n_bad);
     block_add(s_i, I_INLIERS, n_in);
     __syncthreads();
     if (t < VI_SUMS && a.mode != 2 && (t >= S_PLAIN || accumulate)) {
-        double s = 0.0;
-        for (int w = 0; w < VI_WAVES; ++w) s = s + s_part[w][t];
+        const double s = block_sums_get(s_part, t);
         if (t >= S_PLAIN) a.total[2 * (size_t)g + t - S_PLAIN] = s;
-        else if (t >= S_G) {
-            double *b = a.b + 15 * (size_t)st + t - S_G;
-            *b = *b - s;
-        } else {
-            int r = 0, c = t;                      // entry t of the upper triangle, row by row
-            while (c >= 6 - r) c -= 6 - r, ++r;
-            c += r;
-            double *H = a.H + 225 * (size_t)st;
-            H[15 * r + c] = H[15 * r + c] + s;
-            if (r != c) H[15 * c + r] = H[15 * c + r] + s;
-        }
+        else quad_scatter(t, s, a.H + 225 * (size_t)st, a.b + 15 * (size_t)st);
     }
     if (t == 0 && a.mode == 2) a.n_inliers[g] = s_i[I_INLIERS];
     if (t < 8) {
@@ -272,8 +216,8 @@ __global__ __launch_bounds__(SV_T) void k_vi_solve(int n, const uint8_t *__restr
     }
     __syncthreads();
     for (int e = 0; e < n_edges; ++e) {          // ascending: several edges on one pair add up in edge order
-        const int i = edges[e].i, j = edges[e].j, rec = edges[e].rec;
-        if (i < 0 || i >= n || j < 0 || j >= n || i == j || rec < 0 || rec >= cap) {   // uniform
+        const int i = edges[e].i, j = edges[e].j;
+        if (!edge_valid(i, j, edges[e].rec, n, cap)) {   // uniform
             if (t == 0) ++s_cnt[ORBI_R_RANGE];
             continue;
         }
@@ -353,13 +297,10 @@ extern "C" int orbvi_linearize_device(orbi_graph graph, orbi_calib calib, orbvi_
                                       uint8_t *d_active, double huber_delta, double chi2_threshold, int mode, double *d_work, double *d_err,
                                       double *d_chi2, double *d_total, double *d_H_diag, double *d_b, int32_t *d_n_inliers, int32_t *d_result, void *stream)
 {
-    if (!graph.Rwb || !graph.twb || !graph.v || !graph.bg || !graph.ba || !graph.fixed || graph.n_states < 0 || !d_result)
-        return orbx_set_error(ORBX_E_ARG, "null graph array or result, or a negative state count");
+    const char *own = nullptr;
     if (n_groups < 0 || cap_edges < 0 || !d_group_state || !d_edge_off || !d_points || !d_edge_z || !d_edge_inv_sigma2 || !d_err || !d_chi2)
-        return orbx_set_error(ORBX_E_ARG, "null group list, edge array, d_err or d_chi2, or a negative count");
-    if (mode < 0 || mode > 2) return orbx_set_error(ORBX_E_ARG, "mode is 0 (linearise), 1 (errors only) or 2 (classify)");
-    if (!(huber_delta == huber_delta) || !(chi2_threshold == chi2_threshold)) return orbx_set_error(ORBX_E_ARG, "huber_delta or chi2_threshold is not a number");
-    if (camera.camera_model != 0 && camera.camera_model != 1) return orbx_set_error(ORBX_E_ARG, "camera_model is 0 (Pinhole) or 1 (Kannala-Brandt)");
+        own = "null group list, edge array, d_err or d_chi2, or a negative count";
+    if (int rc = graph_check_linearize(graph, d_result, own, mode, huber_delta, chi2_threshold, camera)) return rc;
     if (mode == 0 && (!d_work || !d_H_diag || !d_b)) return orbx_set_error(ORBX_E_ARG, "mode 0 needs d_work, d_H_diag and d_b");
     if (mode != 2 && !d_total) return orbx_set_error(ORBX_E_ARG, "modes 0 and 1 need d_total");
     if (mode == 2 && (!d_active || !d_n_inliers)) return orbx_set_error(ORBX_E_ARG, "mode 2 needs d_active and d_n_inliers");
@@ -368,7 +309,7 @@ extern "C" int orbvi_linearize_device(orbi_graph graph, orbi_calib calib, orbvi_
     hipStream_t s = (hipStream_t)stream;
     ViArgs a = {};
     a.g = graph, a.cal = calib;
-    a.cam = {camera.fx, camera.fy, camera.cx, camera.cy, huber_delta, camera.camera_model, {camera.fisheye_k[0], camera.fisheye_k[1], camera.fisheye_k[2], camera.fisheye_k[3]}};
+    a.cam = graph_camera(camera, huber_delta);
     a.n_groups = n_groups, a.cap_edges = cap_edges, a.group_state = d_group_state, a.edge_off = d_edge_off, a.points = d_points, a.z = d_edge_z;
     a.w = d_edge_inv_sigma2, a.active = d_active, a.threshold = chi2_threshold, a.mode = mode, a.work = d_work, a.err = d_err, a.chi2 = d_chi2, a.total = d_total;
     a.H = d_H_diag, a.b = d_b, a.n_inliers = d_n_inliers, a.result = d_result;

@@ -5,9 +5,8 @@
 //   orbvw_solve_device       the reduced system, by orbvi.h's ordered Cholesky, for up to 480 unknowns
 //   orbvw_backsub_device     the points' step and their share of computeScale
 //
-// Everything is IEEE double in the header's orders without fused multiply-add; the camera is csrc/orbba_camera.h.  The pose derivation
-// and the pose Jacobian restate k_vi_linearize's (csrc/orbvi.hip) line by line: that kernel's register budget rests on the shape of its
-// loops, so its text stays where it is (include/orbvw.h).
+// Everything is IEEE double in the header's orders without fused multiply-add; the camera is csrc/orbba_camera.h; the pose derivation,
+// the pose Jacobian, the quadratic form on a pose and the host checks are the ones k_vi_linearize uses, from csrc/orbi_graph_device.h.
 //
 // Shape: every call is latency-bound.  An edge is a thread; a point is a thread that walks its edges in order; a state's 6 x 6 block and
 // a pair's Schur block are ONE workgroup each with k_vi_linearize's register partials, wave butterfly and ordered wave slots, so no
@@ -25,13 +24,12 @@
 #include "orb_host.h"
 #include "orb_math.h"
 #include "orbba_camera.h"
+#include "orbi_graph_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ double dsum3(double p0, double p1, double p2) { return (p0 + p1) + p2; }
-__device__ __forceinline__ bool dof_fixed(int fixed, int dof) { return (fixed >> (dof < 6 ? 0 : dof / 3 - 1)) & 1; }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // ---- orbvw_linearize_device ------------------------------------------------------------------------------------------------------------
@@ -118,17 +116,13 @@ __global__ __launch_bounds__(256) void k_vw_edge(const VwArgs a)
             if (a.mode == 2) a.outlier[e] = 0;
         } else {
             n_done = 1;
-            // the pose the edge hangs on, derived from (R_wb, t_wb), and the calibration widened: k_vi_linearize's lines
+            // the pose the edge hangs on, derived from (R_wb, t_wb), and the calibration widened
             const double *Rwb = a.g.Rwb + 9 * (size_t)st, *twb = a.g.twb + 3 * (size_t)st;
             double R[9], C[9], tcw[3];
 #pragma unroll
-            for (int k = 0; k < 9; ++k) {
-                const int i = k / 3, j = k - 3 * i;
-                R[k] = dsum3((double)a.cal.Rcb[3 * i] * Rwb[3 * j], (double)a.cal.Rcb[3 * i + 1] * Rwb[3 * j + 1], (double)a.cal.Rcb[3 * i + 2] * Rwb[3 * j + 2]);
-                C[k] = (double)a.cal.Rcb[k];
-            }
+            for (int k = 0; k < 9; ++k) R[k] = pose_rcw(a.cal, Rwb, k), C[k] = (double)a.cal.Rcb[k];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) tcw[i] = (double)a.cal.tcb[i] - dsum3(R[3 * i] * twb[0], R[3 * i + 1] * twb[1], R[3 * i + 2] * twb[2]);
+            for (int i = 0; i < 3; ++i) tcw[i] = pose_tcw(a.cal, R, twb, i);
             const double Px = a.points[3 * (size_t)l], Py = a.points[3 * (size_t)l + 1], Pz = a.points[3 * (size_t)l + 2];
             const double X = dsum3(R[0] * Px, R[1] * Py, R[2] * Pz) + tcw[0];
             const double Y = dsum3(R[3] * Px, R[4] * Py, R[5] * Pz) + tcw[1];
@@ -150,8 +144,8 @@ __global__ __launch_bounds__(256) void k_vw_edge(const VwArgs a)
                 used = finite;
             }
             if (a.mode == 0 && used) {
-                double rw = 1.0;
-                if (a.cam.delta > 0.0 && chi > a.cam.delta * a.cam.delta) rw = a.cam.delta / sqrt(chi);
+                double rho, rw;
+                huber(chi, a.cam.delta, rho, rw);
                 const double W = rw * om;
                 const bool pose_free = st < a.n_solve && !(a.g.fixed[st] & ORBI_FIX_POSE);
                 double Jp[6], Jl[6], J[12];
@@ -162,27 +156,11 @@ __global__ __launch_bounds__(256) void k_vw_edge(const VwArgs a)
                     for (int c = 0; c < 3; ++c) Jl[3 * r + c] = dsum3(-Jp[3 * r] * R[c], -Jp[3 * r + 1] * R[3 + c], -Jp[3 * r + 2] * R[6 + c]);
 #pragma unroll
                 for (int k = 0; k < 12; ++k) J[k] = 0.0;
-                if (pose_free) {            // linearizeOplus: J = [(-Jp)*(R_cb*Hat(R_bc*Pc + t_bc)), (-Jp)*(-R_cb)]
+                if (pose_free) {            // linearizeOplus on the pose
                     double tbc[3];
 #pragma unroll
-                    for (int i = 0; i < 3; ++i) {   // t_bc: the float Pose::inverse of T_cb
-                        const float p0 = ORB_FMUL(-a.cal.Rcb[i], a.cal.tcb[0]), p1 = ORB_FMUL(-a.cal.Rcb[3 + i], a.cal.tcb[1]), p2 = ORB_FMUL(-a.cal.Rcb[6 + i], a.cal.tcb[2]);
-                        tbc[i] = (double)ORB_FADD(ORB_FADD(p0, p1), p2);
-                    }
-                    const double bx = dsum3(C[0] * X, C[3] * Y, C[6] * Z) + tbc[0];
-                    const double by = dsum3(C[1] * X, C[4] * Y, C[7] * Z) + tbc[1];
-                    const double bz = dsum3(C[2] * X, C[5] * Y, C[8] * Z) + tbc[2];
-                    const double Hb[9] = {0.0, -bz, by, bz, 0.0, -bx, -by, bx, 0.0};
-                    double M[9];
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) M[k] = dsum3(C[3 * (k / 3)] * Hb[k % 3], C[3 * (k / 3) + 1] * Hb[3 + k % 3], C[3 * (k / 3) + 2] * Hb[6 + k % 3]);
-#pragma unroll
-                    for (int r = 0; r < 2; ++r)
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            J[6 * r + c] = dsum3(-Jp[3 * r] * M[c], -Jp[3 * r + 1] * M[3 + c], -Jp[3 * r + 2] * M[6 + c]);
-                            J[6 * r + 3 + c] = dsum3(-Jp[3 * r] * -C[c], -Jp[3 * r + 1] * -C[3 + c], -Jp[3 * r + 2] * -C[6 + c]);
-                        }
+                    for (int i = 0; i < 3; ++i) tbc[i] = pose_tbc(a.cal, i);
+                    pose_jacobian(C, tbc, Jp, X, Y, Z, J);
                 }
 #pragma unroll
                 for (int k = 0; k < 12; ++k) work[W_JP + k] = J[k];
@@ -240,20 +218,19 @@ __global__ __launch_bounds__(256) void k_vw_point(const VwArgs a)
 __global__ __launch_bounds__(ST_T) void k_vw_state(const VwArgs a, int n_state_blocks)
 {
     __shared__ double s_part[ST_WAVES][ST_SUMS];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, s = blockIdx.x;
+    const int t = threadIdx.x, s = blockIdx.x;
     const bool totals = s == n_state_blocks;
     if (!totals && (a.g.fixed[s] & ORBI_FIX_POSE)) return;    // uniform
     double acc[ST_SUMS];
 #pragma unroll
     for (int k = 0; k < ST_SUMS; ++k) acc[k] = 0.0;
     if (totals) {
-        const double dsqr = a.cam.delta * a.cam.delta;
         for (int e = t; e < a.n_edges; e += ST_T) {
             if (a.active && !a.active[e]) continue;
             const double chi = a.chi2[e], ex = a.err[2 * (size_t)e], ey = a.err[2 * (size_t)e + 1];
             if (!(isfinite(ex) && isfinite(ey) && isfinite(chi))) continue;
-            double rho = chi;
-            if (a.cam.delta > 0.0 && chi > dsqr) rho = (2.0 * sqrt(chi)) * a.cam.delta - dsqr;
+            double rho, rw;
+            huber(chi, a.cam.delta, rho, rw);
             acc[0] = acc[0] + chi, acc[1] = acc[1] + rho;
         }
     } else {
@@ -261,41 +238,15 @@ __global__ __launch_bounds__(ST_T) void k_vw_state(const VwArgs a, int n_state_b
             if (a.edge_state[e] != s) continue;
             const double *work = a.work + (size_t)ORBVW_EDGE_WORK * e;
             if (work[W_USED] == 0.0) continue;
-            double J[12];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) J[k] = work[W_JP + k];
-            const double W = work[W_W], wex = work[W_WE], wey = work[W_WE + 1];
-            int k = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = r; c < 6; ++c, ++k) acc[k] = acc[k] + (J[r] * (W * J[c]) + J[6 + r] * (W * J[6 + c]));
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[21 + r] = acc[21 + r] + (J[r] * wex + J[6 + r] * wey);
+            quad_accumulate(work + W_JP, work[W_W], work[W_WE], work[W_WE + 1], acc);
         }
     }
-#pragma unroll
-    for (int k = 0; k < ST_SUMS; ++k) {
-        if (totals && k >= 2) continue;
-        const double v = wave_sum(acc[k]);
-        if (lane == 0) s_part[wave][k] = v;
-    }
+    block_sums_put(acc, s_part, 0, totals ? 2 : ST_SUMS);
     __syncthreads();
     if (t >= (totals ? 2 : ST_SUMS)) return;
-    double sum = 0.0;
-    for (int w = 0; w < ST_WAVES; ++w) sum = sum + s_part[w][t];
+    const double sum = block_sums_get(s_part, t);
     if (totals) a.total[t] = sum;
-    else if (t >= 21) {
-        double *b = a.b + 15 * (size_t)s + t - 21;
-        *b = *b - sum;
-    } else {
-        int r = 0, c = t;                          // entry t of the upper triangle, row by row
-        while (c >= 6 - r) c -= 6 - r, ++r;
-        c += r;
-        double *H = a.H + 225 * (size_t)s;
-        H[15 * r + c] = H[15 * r + c] + sum;
-        if (r != c) H[15 * c + r] = H[15 * c + r] + sum;
-    }
+    else quad_scatter(t, sum, a.H + 225 * (size_t)s, a.b + 15 * (size_t)s);
 }
 
 // ---- orbvw_reduce_device ------------------------------------------------------------------------------------------------------------------
@@ -363,8 +314,8 @@ __global__ __launch_bounds__(256) void k_vw_base(const RdArgs a)
         else if (si == sj) v = a.H_diag[225 * (size_t)si + 15 * r + c] + (r == c ? *a.lambda : 0.0);
         else
             for (int e = 0; e < a.n_edges; ++e) {     // ascending: several edges on one pair add up in edge order
-                const int i = a.edges[e].i, j = a.edges[e].j, rec = a.edges[e].rec;
-                if (i < 0 || i >= a.n_solve || j < 0 || j >= a.n_solve || i == j || rec < 0 || rec >= a.cap) continue;
+                const int i = a.edges[e].i, j = a.edges[e].j;
+                if (!edge_valid(i, j, a.edges[e].rec, a.n_solve, a.cap)) continue;
                 if (i == si && j == sj) v = v + a.H_off[225 * (size_t)e + 15 * r + c];
                 else if (i == sj && j == si) v = v + a.H_off[225 * (size_t)e + 15 * c + r];
             }
@@ -375,10 +326,7 @@ __global__ __launch_bounds__(256) void k_vw_base(const RdArgs a)
     __syncthreads();
     int n_range = 0, n_sing = 0;
     double h_max = 0.0;
-    for (int e = t; e < a.n_edges; e += 256) {
-        const int i = a.edges[e].i, j = a.edges[e].j, rec = a.edges[e].rec;
-        n_range += i < 0 || i >= a.n_solve || j < 0 || j >= a.n_solve || i == j || rec < 0 || rec >= a.cap;
-    }
+    for (int e = t; e < a.n_edges; e += 256) n_range += !edge_valid(a.edges[e].i, a.edges[e].j, a.edges[e].rec, a.n_solve, a.cap);
     for (int R = t; R < N; R += 256) {
         const int s = R / 15, r = R - 15 * s;
         const bool fre = !dof_fixed(a.fixed[s], r);
@@ -408,7 +356,7 @@ __global__ __launch_bounds__(SC_T) void k_vw_schur(const RdArgs a)
     __shared__ double s_part[SC_WAVES][SC_SUMS];
     int i = 0, rem = blockIdx.x;                   // block index -> (i, j >= i)
     while (rem >= a.n_solve - i) rem -= a.n_solve - i, ++i;
-    const int j = i + rem, t = threadIdx.x, lane = t & 63, wave = t >> 6, N = 15 * a.n_solve;
+    const int j = i + rem, t = threadIdx.x, N = 15 * a.n_solve;
     if ((a.fixed[i] & ORBI_FIX_POSE) || (a.fixed[j] & ORBI_FIX_POSE)) return;     // uniform
     double acc[SC_SUMS];
 #pragma unroll
@@ -441,15 +389,10 @@ __global__ __launch_bounds__(SC_T) void k_vw_schur(const RdArgs a)
             for (int r = 0; r < 6; ++r) acc[36 + r] = acc[36 + r] + dsum3(A[r] * tl[0], A[6 + r] * tl[1], A[12 + r] * tl[2]);
         }
     }
-#pragma unroll
-    for (int k = 0; k < SC_SUMS; ++k) {
-        const double v = wave_sum(acc[k]);
-        if (lane == 0) s_part[wave][k] = v;
-    }
+    block_sums_put(acc, s_part);
     __syncthreads();
     if (t >= SC_SUMS) return;
-    double sum = 0.0;
-    for (int w = 0; w < SC_WAVES; ++w) sum = sum + s_part[w][t];
+    const double sum = block_sums_get(s_part, t);
     if (t < 36) {
         const int r = t / 6, c = t - 6 * r;
         if (i == j && r > c) return;
@@ -612,13 +555,13 @@ constexpr int BS_T = 1024, BS_WAVES = BS_T / 64;
 __global__ __launch_bounds__(BS_T) void k_vw_scale(int n_points, const double *__restrict__ inv, const double *__restrict__ bl, const double *__restrict__ xl,
                                                    const double *__restrict__ lambda, double *__restrict__ out_points, int32_t *__restrict__ result)
 {
-    __shared__ double s_part[BS_WAVES];
+    __shared__ double s_part[BS_WAVES][1];
     __shared__ int s_cnt[8];
     const int t = threadIdx.x;
     if (t < 8) s_cnt[t] = 0;
     __syncthreads();
     const double lam = *lambda;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     int n_done = 0, n_sing = 0;
     for (int l = t; l < n_points; l += BS_T) {
         if (point_skipped(inv + 9 * (size_t)l)) {
@@ -627,17 +570,12 @@ __global__ __launch_bounds__(BS_T) void k_vw_scale(int n_points, const double *_
         }
         ++n_done;
         const double *x = xl + 3 * (size_t)l, *b = bl + 3 * (size_t)l;
-        acc = acc + dsum3(x[0] * (lam * x[0] + b[0]), x[1] * (lam * x[1] + b[1]), x[2] * (lam * x[2] + b[2]));
+        acc[0] = acc[0] + dsum3(x[0] * (lam * x[0] + b[0]), x[1] * (lam * x[1] + b[1]), x[2] * (lam * x[2] + b[2]));
     }
-    acc = wave_sum(acc);
-    if ((t & 63) == 0) s_part[t >> 6] = acc;
+    block_sums_put(acc, s_part);
     block_add(s_cnt, {ORBI_R_DONE, ORBVW_R_POINT_SINGULAR}, {n_done, n_sing});
     __syncthreads();
-    if (t == 0) {
-        double s = 0.0;
-        for (int w = 0; w < BS_WAVES; ++w) s = s + s_part[w];
-        out_points[0] = s;
-    }
+    if (t == 0) out_points[0] = block_sums_get(s_part, 0);
     if (t < 8) result[t] = s_cnt[t];
 }
 
@@ -651,14 +589,11 @@ extern "C" int orbvw_linearize_device(orbi_graph graph, orbi_calib calib, orbvi_
                                       double *d_err, double *d_chi2, double *d_total, double *d_H_diag, double *d_b, double *d_Hll, double *d_bl, double *d_Hlp,
                                       uint8_t *d_outlier, int32_t *d_result, void *stream)
 {
-    if (!graph.Rwb || !graph.twb || !graph.v || !graph.bg || !graph.ba || !graph.fixed || graph.n_states < 0 || !d_result)
-        return orbx_set_error(ORBX_E_ARG, "null graph array or result, or a negative state count");
+    const char *own = nullptr;
     if (n_points < 1 || cap_edges < 0 || !d_points || !d_edge_state || !d_edge_point || !d_edge_z || !d_edge_inv_sigma2 || !d_point_off || !d_err || !d_chi2)
-        return orbx_set_error(ORBX_E_ARG, "null point or edge array, d_point_off, d_err or d_chi2, n_points < 1 or a negative edge count");
-    if (n_solve < 1 || n_solve > graph.n_states) return orbx_set_error(ORBX_E_ARG, "n_solve outside [1, n_states]");
-    if (mode < 0 || mode > 2) return orbx_set_error(ORBX_E_ARG, "mode is 0 (linearise), 1 (errors only) or 2 (classify)");
-    if (!(huber_delta == huber_delta) || !(chi2_threshold == chi2_threshold)) return orbx_set_error(ORBX_E_ARG, "huber_delta or chi2_threshold is not a number");
-    if (camera.camera_model != 0 && camera.camera_model != 1) return orbx_set_error(ORBX_E_ARG, "camera_model is 0 (Pinhole) or 1 (Kannala-Brandt)");
+        own = "null point or edge array, d_point_off, d_err or d_chi2, n_points < 1 or a negative edge count";
+    else if (n_solve < 1 || n_solve > graph.n_states) own = "n_solve outside [1, n_states]";
+    if (int rc = graph_check_linearize(graph, d_result, own, mode, huber_delta, chi2_threshold, camera)) return rc;
     if (mode == 0 && (!d_work || !d_H_diag || !d_b || !d_Hll || !d_bl || !d_Hlp)) return orbx_set_error(ORBX_E_ARG, "mode 0 needs d_work, d_H_diag, d_b, d_Hll, d_bl and d_Hlp");
     if (mode != 2 && !d_total) return orbx_set_error(ORBX_E_ARG, "modes 0 and 1 need d_total");
     if (mode == 2 && !d_outlier) return orbx_set_error(ORBX_E_ARG, "mode 2 needs d_outlier");
@@ -669,7 +604,7 @@ extern "C" int orbvw_linearize_device(orbi_graph graph, orbi_calib calib, orbvi_
     hipStream_t s = (hipStream_t)stream;
     VwArgs a = {};
     a.g = graph, a.cal = calib;
-    a.cam = {camera.fx, camera.fy, camera.cx, camera.cy, huber_delta, camera.camera_model, {camera.fisheye_k[0], camera.fisheye_k[1], camera.fisheye_k[2], camera.fisheye_k[3]}};
+    a.cam = graph_camera(camera, huber_delta);
     a.n_solve = n_solve, a.n_points = n_points, a.n_edges = cap_edges, a.points = d_points, a.edge_state = d_edge_state, a.edge_point = d_edge_point;
     a.z = d_edge_z, a.w = d_edge_inv_sigma2, a.active = d_active, a.threshold = chi2_threshold, a.mode = mode, a.off = d_point_off, a.work = d_work;
     a.err = d_err, a.chi2 = d_chi2, a.total = d_total, a.H = d_H_diag, a.b = d_b, a.Hll = d_Hll, a.bl = d_bl, a.Hlp = d_Hlp, a.outlier = d_outlier, a.result = d_result;

@@ -16,26 +16,15 @@ class OrbfCamera(C.Structure):
                 ("size_scale", C.c_void_p)]
 
 
-_bound = False
-
-
-def _L():
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        vp, i32 = C.c_void_p, C.c_int
-        L.orbf_create.restype = i32
-        L.orbf_create.argtypes = [C.POINTER(OrbfCamera), i32, C.POINTER(vp)]
-        L.orbf_destroy.restype = None
-        L.orbf_destroy.argtypes = [vp]
-        L.orbf_grid_dims.restype = i32
-        L.orbf_grid_dims.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
-        L.orbf_frame_post_device.restype = i32
-        L.orbf_frame_post_device.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp]
-        L.orbf_frame_post.restype = i32
-        L.orbf_frame_post.argtypes = [vp, vp, i32, vp, vp, vp]
-        _bound = True
-    return L
+_vp, _i32 = C.c_void_p, C.c_int
+_SIGS = {
+    "orbf_create": [C.POINTER(OrbfCamera), _i32, C.POINTER(_vp)],
+    "orbf_destroy": (None, [_vp]),
+    "orbf_grid_dims": [_vp, C.POINTER(_i32), C.POINTER(_i32)],
+    "orbf_frame_post_device": [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "orbf_frame_post": [_vp, _vp, _i32, _vp, _vp, _vp],
+}
+_L = _lib.binder(_SIGS)
 
 
 class FramePost:

@@ -76,18 +76,7 @@ _SIGS = {
     "orbi_graph_oplus_device": [Graph, _vp, _vp, _vp, _vp],
     "orbi_graph_recover_device": [Graph, Calib, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
 }
-_bound = None
-
-
-def _L():
-    global _bound
-    if _bound is None:
-        L = _lib.lib()
-        for name, args in _SIGS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype, fn.argtypes = C.c_int, args
-        _bound = L
-    return _bound
+_L = _lib.binder(_SIGS)
 
 
 def _p(t):

@@ -32,18 +32,7 @@ _SIGS = {
     "orbvi_linearize_device": [Graph, Calib, Camera, _i32, _i32] + [_vp] * 6 + [C.c_double, C.c_double, _i32] + [_vp] * 9,
     "orbvi_solve_device": [_i32, _vp, _vp, _i32, _i32] + [_vp] * 8,
 }
-_bound = None
-
-
-def _L():
-    global _bound
-    if _bound is None:
-        L = _lib.lib()
-        for name, args in _SIGS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype, fn.argtypes = C.c_int, args
-        _bound = L
-    return _bound
+_L = _lib.binder(_SIGS)
 
 
 def linearize_device(graph, calib, camera, n_groups, cap_edges, d_group_state, d_edge_off, d_points, d_edge_z, d_edge_inv_sigma2, d_err, d_chi2,

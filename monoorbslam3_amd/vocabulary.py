@@ -9,32 +9,18 @@ from . import _lib
 NO_NODE = 0xFFFFFFFF
 MAX_FEATURES = 8192
 
-_bound = False
-
-
-def _L():
-    global _bound
-    L = _lib.lib()
-    if not _bound:
-        vp, i32 = C.c_void_p, C.c_int
-        L.orbv_create.restype = i32
-        L.orbv_create.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, C.POINTER(vp)]
-        L.orbv_load_text.restype = i32
-        L.orbv_load_text.argtypes = [C.c_char_p, i32, C.POINTER(vp)]
-        L.orbv_destroy.restype = None
-        L.orbv_destroy.argtypes = [vp]
-        L.orbv_info.restype = i32
-        L.orbv_info.argtypes = [vp] + [C.POINTER(i32)] * 6
-        L.orbv_nodes.restype = i32
-        L.orbv_nodes.argtypes = [vp, vp, vp, vp, vp]
-        L.orbv_transform_features_device.restype = i32
-        L.orbv_transform_features_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
-        L.orbv_transform_device.restype = i32
-        L.orbv_transform_device.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.orbv_transform.restype = i32
-        L.orbv_transform.argtypes = [vp, vp, i32, i32, vp, vp, C.POINTER(i32), vp, vp, vp, C.POINTER(i32)]
-        _bound = True
-    return L
+_vp, _i32 = C.c_void_p, C.c_int
+_SIGS = {
+    "orbv_create": [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, C.POINTER(_vp)],
+    "orbv_load_text": [C.c_char_p, _i32, C.POINTER(_vp)],
+    "orbv_destroy": (None, [_vp]),
+    "orbv_info": [_vp] + [C.POINTER(_i32)] * 6,
+    "orbv_nodes": [_vp, _vp, _vp, _vp, _vp],
+    "orbv_transform_features_device": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
+    "orbv_transform_device": [_vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "orbv_transform": [_vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(_i32), _vp, _vp, _vp, C.POINTER(_i32)],
+}
+_L = _lib.binder(_SIGS)
 
 
 class ORBVocabulary:

@@ -27,18 +27,7 @@ _SIGS = {
     "orbvw_solve_device": [_i32] + [_vp] * 8,
     "orbvw_backsub_device": [_i32, _i32, _i32] + [_vp] * 13,
 }
-_bound = None
-
-
-def _L():
-    global _bound
-    if _bound is None:
-        L = _lib.lib()
-        for name, args in _SIGS.items():
-            fn = getattr(L, name)  # AttributeError if the library does not export it
-            fn.restype, fn.argtypes = C.c_int, args
-        _bound = L
-    return _bound
+_L = _lib.binder(_SIGS)
 
 
 def linearize_device(graph, calib, camera, n_solve, n_points, cap_edges, d_points, d_edge_state, d_edge_point, d_edge_z, d_edge_inv_sigma2,

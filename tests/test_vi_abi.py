@@ -45,6 +45,41 @@ def test_every_declared_entry_point_is_exported_and_mirrored(vi):
     assert '#include "orbi.h"' in txt
 
 
+def test_the_binder_binds_once_and_a_missing_symbol_raises(vi):
+    """_lib.binder, which every module's _L() is: nothing is loaded before the first use, the first use sets every signature, a second
+    use neither loads nor binds again, and a name the library lacks raises AttributeError at first use -- with the built library too"""
+    from monoorbslam3_amd import _lib
+
+    class Fn:
+        restype = argtypes = "unset"
+
+    class Lib:
+        def __init__(self):
+            self.orbt_a, self.orbt_b = Fn(), Fn()
+
+    loads = []
+
+    def load():
+        loads.append(Lib())
+        return loads[-1]
+
+    get = _lib.binder({"orbt_a": [C.c_int], "orbt_b": (None, [C.c_void_p])}, load)
+    assert not loads
+    L = get()
+    assert (L.orbt_a.restype, L.orbt_a.argtypes, L.orbt_b.restype, L.orbt_b.argtypes) == (C.c_int, [C.c_int], None, [C.c_void_p])
+    L.orbt_a.argtypes = "kept"
+    assert get() is L and len(loads) == 1 and L.orbt_a.argtypes == "kept"
+    missing = _lib.binder({"orbt_a": [], "orbt_missing": []}, load)
+    for _ in range(2):
+        with pytest.raises(AttributeError):
+            missing()
+    with pytest.raises(AttributeError):
+        _lib.binder({"orbvi_no_such_entry_point": []})()
+    assert vi._L() is _lib.lib() and vi._L() is vi._L()
+    for name, args in vi._SIGS.items():
+        assert getattr(vi._L(), name).argtypes == args and getattr(vi._L(), name).restype is C.c_int, name
+
+
 def test_orbi_h_still_does_not_include_orbvi_h():
     for name in ("orbi.h", "orbi_factors.h", "orbx.h", "orbba.h"):
         assert "orbvi" not in _header(name), name

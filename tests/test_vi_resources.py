@@ -4,6 +4,7 @@ import os
 import re
 
 from test_kernel_resources import _isa, _kernels
+from test_vw_resources import SHARED_DEVICE, SHARED_HOST
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "monoorbslam3_amd", "csrc")
@@ -40,3 +41,18 @@ def test_the_camera_is_written_once():
             assert not re.search(r"__forceinline__ \w+ %s\(" % fn, text) and "struct BaCam" not in text, (src, fn)
     assert "struct BaCam" in shared
     assert "orbvi.hip" in open(os.path.join(CSRC, "Makefile")).read()
+
+
+def test_the_edge_math_on_the_inertial_graph_is_written_once():
+    """orbvi.hip takes dsum3, dof_fixed, the orbi_edge predicate, the pose entries, the pose Jacobian, the Huber kernel, the quadratic
+    form with its scatter and the host checks from csrc/orbi_graph_device.h, which defines each exactly once, and the ordered workgroup
+    finish from csrc/orb_device.h"""
+    shared = open(os.path.join(CSRC, "orbi_graph_device.h")).read()
+    text = open(os.path.join(CSRC, "orbvi.hip")).read()
+    assert '#include "orbi_graph_device.h"' in text and '#include "orb_device.h"' in text
+    for fn in SHARED_DEVICE + SHARED_HOST:
+        assert len(re.findall(r"^(?:__device__ __forceinline__|inline) \w+ %s\(" % fn, shared, re.M)) == 1, fn
+        assert re.search(r"\b%s\(" % fn, text), fn
+        assert not re.search(r"^\s*(?:__device__ |static |inline )[\w ]*\b%s\(" % fn, text, re.M), fn
+    assert "#pragma clang fp contract(off)" in shared and shared.index("#pragma clang fp contract(off)") < shared.index("namespace {")
+    assert "block_sums_put(" in text and "block_sums_get(" in text

@@ -13,6 +13,9 @@ STATED = {"k_vw_off_init": (256, 0), "k_vw_off_first": (256, 0), "k_vw_off_scan"
           "k_vw_backsub": (256, 0), "k_vw_scale": (1024, 160)}
 
 
+# what csrc/orbi_graph_device.h defines once for orbi_factors.hip, orbvi.hip and orbvw.hip
+SHARED_DEVICE = ("dsum3", "dof_fixed", "edge_valid", "pose_rcw", "pose_tcw", "pose_tbc", "pose_jacobian", "huber", "quad_accumulate", "quad_scatter")
+SHARED_HOST = ("graph_camera", "graph_check_linearize")
 # the constant a kernel's __launch_bounds__ names, where it is not a literal
 BOUND = {"k_vw_state": "ST_T", "k_vw_schur": "SC_T", "k_vw_solve": "SW_T", "k_vw_scale": "BS_T"}
 
@@ -40,8 +43,9 @@ def test_the_kernels_use_no_scratch_memory_and_the_lds_the_header_states():
 
 
 def test_the_camera_is_still_written_once_and_orbvi_is_left_alone():
-    """orbvw.hip evaluates csrc/orbba_camera.h like orbba.hip and orbvi.hip and defines neither function itself; it restates the pose
-    derivation of k_vi_linearize instead of moving it, so orbvi.hip does not know about orbvw"""
+    """orbvw.hip evaluates csrc/orbba_camera.h like orbba.hip and orbvi.hip and defines neither function itself; the pose derivation, the
+    pose Jacobian, the Huber kernel and the quadratic form it has in common with k_vi_linearize are defined once, in
+    csrc/orbi_graph_device.h, which the three sources on the inertial graph include, so orbvi.hip still does not know about orbvw"""
     text = open(os.path.join(CSRC, "orbvw.hip")).read()
     for fn in ("ba_project", "ba_proj_jacobian"):
         assert '#include "orbba_camera.h"' in text and re.search(r"\b%s\(" % fn, text), fn
@@ -50,3 +54,17 @@ def test_the_camera_is_still_written_once_and_orbvi_is_left_alone():
     assert "orbvw.hip" in open(os.path.join(CSRC, "Makefile")).read()
     consts = dict(re.findall(r"(ST_T|SC_T|SW_T|BS_T) = (\d+)", text))
     assert consts == {"ST_T": "1024", "SC_T": "256", "SW_T": "512", "BS_T": "1024"}, consts
+    shared = open(os.path.join(CSRC, "orbi_graph_device.h")).read()
+    sources = {src: open(os.path.join(CSRC, src)).read() for src in ("orbvi.hip", "orbvw.hip", "orbi_factors.hip")}
+    for fn in SHARED_DEVICE + SHARED_HOST:
+        assert len(re.findall(r"^(?:__device__ __forceinline__|inline) \w+ %s\(" % fn, shared, re.M)) == 1, fn
+        for src, body in sources.items():
+            assert not re.search(r"^\s*(?:__device__ |static |inline )[\w ]*\b%s\(" % fn, body, re.M), (src, fn)
+    for src, body in sources.items():
+        assert '#include "orbi_graph_device.h"' in body, src
+    for fn in SHARED_DEVICE + SHARED_HOST:                        # and every one serves both of EdgeMono's files
+        assert re.search(r"\b%s\(" % fn, sources["orbvi.hip"]) and re.search(r"\b%s\(" % fn, text), fn
+    workgroup = open(os.path.join(CSRC, "orb_device.h")).read()
+    for fn in ("block_sums_put", "block_sums_get"):
+        assert len(re.findall(r"__forceinline__ \w+ %s\(" % fn, workgroup)) == 1 and text.count(fn + "(") == 3, fn
+    assert "wave_sum(" not in text                                # no kernel of the file finishes its sums by hand
