@@ -9,7 +9,12 @@
  *   orbi_graph_init_device -> orbi_edge_information_device -> orbi_linearize_device -> orbvi_linearize_device ->
  *   orbvi_solve_device -> orbi_graph_oplus_device -> orbi_linearize_device (mode 1) + orbvi_linearize_device (mode 1)
  * and the caller reads back two scalars (the chi2 at the trial point, d_out[0] of the solve) for its accept / reject decision.  THE
- * LOOP ITSELF IS NOT HERE: its decisions are the caller's.  Not here either: EdgeMono (G2oTypes.cpp:59-69), where the
+ * LOOP ITSELF IS NOT HERE: its decisions are the caller's.  A caller that closes it (tests/inertial_loop.py does, as test
+ * code) needs two things no call does for it.  The lambda init: d_out[1], what computeLambdaInit multiplies by tau, is written by
+ * orbvi_solve_device only, so iteration 0 of every optimize() costs one solve whose step is discarded (any *d_lambda; a refused
+ * solve writes d_out[1] all the same).  The pop: g2o pushes CameraImuPose WITH its update counter, so a rejected trial restores d_iter
+ * along with Rwb, twb, v, bg and ba -- a counter left as the trial set it renormalises the rotation at other updates than the
+ * reference.  Not here either: EdgeMono (G2oTypes.cpp:59-69), where the
  * map points are vertices too -- a local window needs the Schur complement over its points, which is a later layer, and this is
  * also why the solve stops at ORBVI_MAX_STATES states.
  *

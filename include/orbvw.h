@@ -13,7 +13,10 @@
  *   orbi_graph_oplus_device -> orbi_linearize_device (mode 1) + orbvw_linearize_device (mode 1, on d_points_out)
  * and the caller reads back four scalars for its accept / reject decision: the two robustified totals at the trial point, d_out[0]
  * of the solve and d_out_points[0] of the back-substitution (their sum is g2o's computeScale without its + 1e-3).  THE LOOP ITSELF
- * IS NOT HERE: its decisions are the caller's.  Not here either: assembling this problem from the device-resident map
+ * IS NOT HERE: its decisions are the caller's.  A caller that closes it (tests/inertial_loop.py does, as test code): an
+ * accepted trial makes d_points_out the next d_points (two buffers that swap), a rejected one restores Rwb, twb, v, bg, ba AND d_iter
+ * (orbvi.h says why) and leaves d_points as it is; a refused solve (ORBI_R_REFUSED) is a rejected trial; without a user lambda init,
+ * d_out[1] comes from one orbvw_reduce_device whose system is discarded.  Not here either: assembling this problem from the device-resident map
  * (getRecentKeyFrames), the setPrioriInformation chaining behind the optimisation (orbi_prior_information_device serves it), and
  * inertialOptimize / fullInertialOptimize.
  *

@@ -485,8 +485,9 @@ def _next_state(cal, rec, src, rng, noise):
     return np.concatenate([R.reshape(9), nxt[9:12] + rng.normal(0, noise, 3), nxt[12:15] + rng.normal(0, noise, 3)]).astype(np.float32)
 
 
-def make_chain(n_edges, seed=7, walks=True, noise=2e-3, cal=None):
-    """n_edges + 1 states in a chain, edge e between states e and e + 1 with record e; sample counts 2, 3, 8, 40, 100 in turn, every second
+def make_chain(n_edges, seed=7, walks=True, noise=2e-3, cal=None, sample_counts=SAMPLE_COUNTS):
+    """n_edges + 1 states in a chain, edge e between states e and e + 1 with record e; sample counts 2, 3, 8, 40, 100 in turn (or
+    `sample_counts` in turn: a closed loop needs the baselines of full records, tests/inertial_loop.py), every second
     record with a non-zero delta_bias.  State e + 1 is what record e predicts from state e, disturbed by `noise`, by a thousandth of it
     and not at all in turn, so that the chi2 of the edges lie on both sides of the Huber threshold.  Returns a dict with the float32 source states, the records, the edges, a prior slot per state
     and the graph as orbi_graph_init_device leaves it."""
@@ -495,7 +496,7 @@ def make_chain(n_edges, seed=7, walks=True, noise=2e-3, cal=None):
     recs, src = [], [np.concatenate([im.rodrigues(rng.normal(0, 0.8, 3)).reshape(9), rng.normal(0, 2.0, 3), rng.normal(0, 0.7, 3)]).astype(np.float32)]
     for e in range(n_edges):
         step = np.array([0.002, -0.003, 0.001, 0.03, -0.02, 0.01]) * (1 + 0.5 * (e % 3)) if e % 2 else None
-        recs.append(make_record(cal, SAMPLE_COUNTS[e % 5], 200 + 31 * seed + e, step, rng))
+        recs.append(make_record(cal, sample_counts[e % len(sample_counts)], 200 + 31 * seed + e, step, rng))
         src.append(_next_state(cal, recs[-1], src[-1], rng, noise * (1.0, 1e-3, 0.0)[e % 3]))
     recs.append(make_record(cal, 5, 999 + seed, None, rng))          # the last state's own record: its biases come from there
     src = np.stack(src)
@@ -506,7 +507,7 @@ def make_chain(n_edges, seed=7, walks=True, noise=2e-3, cal=None):
     res = graph_init(graph, recs, src, jobs)
     assert res[R_DONE] == n_edges + 1
     if n_edges >= 5:
-        assert {len(r.meas) for r in recs[:n_edges]} == set(SAMPLE_COUNTS)
+        assert {len(r.meas) for r in recs[:n_edges]} == set(sample_counts)
     if n_edges >= 2:
         assert not recs[0].delta_bias.any() and recs[1].delta_bias.all()
     return dict(cal=cal, recs=recs, src=src, edges=edges, graph=graph, init_jobs=jobs)
@@ -521,10 +522,10 @@ def make_priors(sc, slots):
     return pri, jobs, clamped
 
 
-def make_tracker_graph(seed=11):
+def make_tracker_graph(seed=11, sample_counts=SAMPLE_COUNTS):
     """poseFullOptimize's inertial part (Optimize.cpp:623-660): two states, the first with a fixed pose, the second without bias
     vertices, one edge without walks, the three priors on the first state"""
-    sc = make_chain(1, seed, walks=False)
+    sc = make_chain(1, seed, walks=False, sample_counts=sample_counts)
     sc["graph"].fixed[:] = [FIX_POSE, FIX_GYRO | FIX_ACC]
     sc["graph"].bg[1] = sc["graph"].ba[1] = 0.0
     sc["init_jobs"][1, 2] = -1

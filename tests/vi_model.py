@@ -330,14 +330,15 @@ def make_edges(cal, cam, Rwb, twb, n_edges, rng):
     return P, z, w
 
 
-def pose_full_scene(n_edges, seed=3, model=0):
+def pose_full_scene(n_edges, seed=3, model=0, sample_counts=fm.SAMPLE_COUNTS):
     """poseFullOptimize's graph: factors_model.make_tracker_graph (two states, state 0's pose fixed, one record, three priors) and
     n_edges map points seen by state 1.  The points are projected through a pose a little off state 1's (2e-3 rad, 2 cm: something for
     an iteration to gain) and stored as floats widened, like orbba_pose_edges_device leaves them; kp.size = 31 * 1.2^level, inv_sigma2 =
     1.f / size / size, and the pixel noise is size * N(0, 1) per axis, so that chi2 is about chi-square with two degrees of freedom:
-    most below huber_delta^2 = 5.991, about 5 % above; OUTLIER_SHARE of the edges get four times the noise."""
+    most below huber_delta^2 = 5.991, about 5 % above; OUTLIER_SHARE of the edges get four times the noise.  sample_counts is
+    factors_model.make_chain's, for the closed-loop scenes of tests/inertial_loop.py; its default gives the scene above, byte for byte."""
     rng = np.random.RandomState(1000 * seed + 7 * model + 1)
-    sc = fm.make_tracker_graph(11)
+    sc = fm.make_tracker_graph(11, sample_counts)
     cam = FISHEYE if model else PINHOLE
     g = sc["graph"]
     off = g.copy()

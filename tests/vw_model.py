@@ -289,15 +289,20 @@ def iterate(sc, lam, graph=None, points=None):
 
 
 # ---- the scene -------------------------------------------------------------------------------------------------------------------------------
-def window_scene(n_solve, n_fixed, n_points, seed=1, model=0):
+def window_scene(n_solve, n_fixed, n_points, seed=1, model=0, min_obs=None, depth=(2.0, 12.0), fixed_offset=0.3, outlier_share=vm.OUTLIER_SHARE,
+                 pixel_noise=1.0, sample_counts=fm.SAMPLE_COUNTS):
     """localFullBundleAdjustment's graph: factors_model.make_chain with walks (n_solve states, all free), the three priors on state 0 with
     the acc prior weighted by gyro_info (Optimize.cpp:1189), n_fixed fixed key frames appended near the chain's states, and n_points map
     points stored as floats widened, point l in front of solve state l mod n_solve and seen by 1 to 6 of the states that have it in view
     (point 0 by exactly one).  The measurements
     come from poses a little off the graph's (2e-3 rad, 2 cm) and points 2 cm off, with pixel noise kp.size * N(0, 1) per axis and
-    vi_model.OUTLIER_SHARE of them four times that: something for an iteration to gain, chi2 on both sides of the Huber threshold."""
+    vi_model.OUTLIER_SHARE of them four times that: something for an iteration to gain, chi2 on both sides of the Huber threshold.
+    The keywords are for the closed-loop scenes of tests/inertial_loop.py; their defaults give the scene above, byte for byte.  min_obs:
+    every point (point 0 too) is seen by at least that many states; depth: the range of the points' depths; fixed_offset: how far the
+    fixed key frames sit from the chain's states (m); outlier_share and pixel_noise (a factor on kp.size * N(0, 1)): the measurements;
+    sample_counts: factors_model.make_chain's."""
     rng = np.random.RandomState(7000 + 100 * seed + 13 * model + n_points)
-    sc = dict(fm.make_chain(n_solve - 1, seed=seed, walks=True))
+    sc = dict(fm.make_chain(n_solve - 1, seed=seed, walks=True, sample_counts=sample_counts))
     sc["priors"], sc["prior_info_jobs"], _ = fm.make_priors(sc, [0])
     sc["pjobs"] = np.array([(0, 0, fm.PRIOR_VELO | fm.PRIOR_GYRO | fm.PRIOR_ACC | fm.PRIOR_ACC_GYRO_INFO)], fm.PRIOR_JOB)
     cam = vm.FISHEYE if model else vm.PINHOLE
@@ -308,7 +313,7 @@ def window_scene(n_solve, n_fixed, n_points, seed=1, model=0):
     for f in range(n_fixed):
         one = fm.Graph(1)
         one.Rwb[0], one.twb[0] = chain.Rwb[f % n_solve], chain.twb[f % n_solve]
-        fm.oplus(one, np.concatenate([rng.normal(0, 0.03, 3), rng.normal(0, 0.3, 3), np.zeros(9)])[None])
+        fm.oplus(one, np.concatenate([rng.normal(0, 0.03, 3), rng.normal(0, fixed_offset, 3), np.zeros(9)])[None])
         g.Rwb[n_solve + f], g.twb[n_solve + f], g.fixed[n_solve + f] = one.Rwb[0], one.twb[0], 15
     truth = g.copy()
     truth.fixed[:] = 0
@@ -317,7 +322,7 @@ def window_scene(n_solve, n_fixed, n_points, seed=1, model=0):
     fm.oplus(truth, step)
     cal = sc["cal"]
     poses = [vm.derive_pose(cal, truth.Rwb[s], truth.twb[s])[:2] for s in range(n)]
-    depth = rng.uniform(2.0, 12.0, n_points)
+    depth = rng.uniform(depth[0], depth[1], n_points)
     span = 0.3 if model == 0 else 0.6
     Pc = np.stack([rng.uniform(-span, span, n_points) * depth, rng.uniform(-span, span, n_points) * depth, depth], 1)
     anchor = np.arange(n_points) % n_solve
@@ -328,21 +333,24 @@ def window_scene(n_solve, n_fixed, n_points, seed=1, model=0):
         cams = [(Rcw @ Pt[l] + tcw) for Rcw, tcw in poses]
         view = [s for s, c in enumerate(cams) if c[2] > 1.0 and abs(c[0]) < 0.9 * c[2] and abs(c[1]) < 0.9 * c[2]]
         assert anchor[l] in view
-        k = 1 if l == 0 else min(int(rng.randint(1, 7)), len(view))
+        if min_obs is None:
+            k = 1 if l == 0 else min(int(rng.randint(1, 7)), len(view))
+        else:
+            k = min(max(int(rng.randint(1, 7)), min_obs), len(view))
         for s in sorted(rng.choice(view, k, replace=False).tolist()):
             size = np.float32(31.0) * np.float32(1.2) ** np.float32(rng.randint(0, 8))
             u, v = vm.project(cam, *cams[s])
-            noise = rng.normal(0.0, 1.0, 2) * float(size) * (4.0 if rng.uniform() < vm.OUTLIER_SHARE else 1.0)
+            noise = rng.normal(0.0, 1.0, 2) * float(size) * (4.0 if rng.uniform() < outlier_share else 1.0) * pixel_noise
             es.append(s), ep.append(l), ws.append(F64(np.float32(1.0) / size / size))
             zs.append((np.array([u, v]) + noise).astype(np.float32).astype(F64))
     sc.update(graph=g, cam=cam, n_solve=n_solve, n_fixed=n_fixed, n_points=n_points, points=P, edge_state=np.array(es, np.int32),
               edge_point=np.array(ep, np.int32), z=np.array(zs, F64).reshape(-1, 2), w=np.array(ws, F64))
     ne = len(es)
     counts = np.bincount(sc["edge_point"], minlength=n_points)
-    assert (counts == 1).any() and counts.min() >= 1 and counts.max() <= 6
+    assert counts.max() <= 6 and ((counts == 1).any() and counts.min() >= 1 if min_obs is None else counts.min() >= min_obs)
     it = iterate(sc, 1.0)
     c2 = it["visual"]["chi2"]
-    if ne >= 100:
+    if ne >= 100 and pixel_noise >= 1.0 and outlier_share > 0:
         assert (c2 > HUBER_MONO ** 2).sum() >= 3 and (c2 <= HUBER_MONO ** 2).sum() > ne // 2       # both Huber branches
         assert (c2 > CHI2_MONO).any() and (c2 <= CHI2_MONO).any()                               # both sides of the classification
     assert it["solve_result"][R_DONE] == 1 and it["pivot"] > 0 and not it["reduce"]["skipped"].any()   # no pivot refused at lambda = 1
