@@ -35,7 +35,10 @@ typedef struct orbf_camera {
     int32_t n_dist;           /* 0..12 coefficients, OpenCV order k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 */
     float dist[ORBF_MAX_DIST];
     int32_t undistort;        /* 1 = Pinhole/RAD_TAN (undistorts unless dist[0] == 0, Pinhole.cpp:62); 0 = Fisheye (copy) */
-    const float *size_scale;  /* NULL (Pinhole), or host height*width f32 map = Fisheye::scale_mat; copied at create */
+    const float *size_scale;  /* NULL (Pinhole), or host height*width f32 map = Fisheye::scale_mat; copied at create.
+                                 It is read at [(int)y * width + (int)x] of the RAW key point (float -> int truncation, as
+                                 scale_mat.at<float>(p.y, p.x) does) WITHOUT a range check, like the reference: every raw key
+                                 point of a camera with a table must satisfy 0 <= x < width and 0 <= y < height */
 } orbf_camera;
 
 typedef struct orbf_ctx orbf_t;
@@ -47,7 +50,11 @@ int orbf_grid_dims(const orbf_t *h, int *cols, int *rows);
 
 /* Device pointers, enqueued on `stream` (hipStream_t; NULL: orbx.h, "Streams").
  *   d_kp_raw  [n_frames][cap]  in/out: orbx_extract_batch_device's records; `size` is scaled in place (:24-26)
- *   d_n       [n_frames]       key-point counts
+ *   d_n       [n_frames]       key-point counts; a count above cap is clamped to cap (orbx_extract_batch_device reports
+ *                              the FULL count of a frame that overflowed its records), 0 is an empty frame
+ * Nothing beyond the counts is written: rows of d_kp_raw and d_kp_un at or after a frame's (clamped) count and entries of
+ * d_cell_items at or after its cell_start[n_cells] keep what they held; cell_start is complete for every frame (all zeros
+ * for an empty one).  Without a size_scale table d_kp_raw is only read.
  *   d_kp_un   [n_frames][cap]  out: copy of raw with pt undistorted (:28)
  *   d_cell_start [n_frames][n_cells + 1], d_cell_items [n_frames][cap]  out: CSR grid, items of a cell in
  *             ascending key-point index (the push_back order of :45-50); key points outside the image are in no cell */

@@ -65,6 +65,13 @@ int orbv_transform_features_device(orbv_t *h, const uint8_t *d_desc, int n, int 
  *   d_fv_nodes [n_frames][cap], d_fv_off [n_frames][cap + 1], d_fv_idx [n_frames][cap], d_n_fv [n_frames]
  *                                                                        FeatureVector as CSR, ascending node id,
  *                                                                        feature indices ascending inside a node
+ * A word's value is the sum of the weights of its features, each feature with the weight of the node ITS descent ended in, added
+ * in ascending feature order (BowVector::addWeight): a childless node without the is_leaf flag keeps Node()'s word id 0 and its
+ * own weight, so word 0 can collect features of different weights.  Features that end above level L - levelsup are grouped under
+ * ORBV_NO_NODE, the largest key and therefore the last row; levelsup >= L groups every feature under node 0.
+ * Per frame only n_words ids and values, n_fv nodes, n_fv + 1 offsets and fv_off[n_fv] indices are written, the rest of each row
+ * keeps what it held; a frame without features, of stopped words only (weight 0), or any frame of a vocabulary without words
+ * (a root-only tree) gives n_words = n_fv = 0 and fv_off[0] = 0.
  * Enqueued on `stream` (NULL: orbx.h, "Streams"); no host synchronisation. */
 int orbv_transform_device(orbv_t *h, int n_frames, const uint8_t *d_desc, const int32_t *d_n, int cap, int levelsup,
                           uint32_t *d_bow_ids, double *d_bow_vals, int32_t *d_n_words, uint32_t *d_fv_nodes,

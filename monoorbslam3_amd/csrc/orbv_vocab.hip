@@ -240,10 +240,11 @@ __global__ __launch_bounds__(256) void k_voc_group(VocDev v, const int32_t *__re
         if (r < R) {
             const int2 h = heads[r];
             const int cnt = (r + 1 < R ? heads[r + 1].x : m) - h.x;
-            const double wt = w[h.y];
-            val = wt;
+            val = w[h.y]; // addIfNotExist: the word's first feature
+            // addWeight, one feature after the other in ascending index, each with the weight of the node ITS descent ended
+            // in: nodes that share a word id (Node(): word_id(0) of a childless non-leaf) need not share a weight
             if (accumulate)
-                for (int j = 1; j < cnt; ++j) val = ORB_DADD(val, wt); // addWeight, one feature after the other
+                for (int j = 1; j < cnt; ++j) val = ORB_DADD(val, w[(uint32_t)keys[h.x + j]]);
         }
         __syncthreads();
         if (r < R) vals[r] = val;

@@ -127,6 +127,194 @@ def test_text_format_round_trip(oracle_mod, tmp_path):
         assert (back["k"], back["L"], back["scoring"], back["weighting"]) == (4, 3, 0, 0)
 
 
+# ---------------------------------------------------------------- trees orbv_create accepts: shared with test_vocabulary_edges_gpu.py
+UNEQUAL_FEATS = np.stack([_bits(200, 201), _bits(0, 1, 2, 3, 60, 61), _bits(200), _bits(0, 1, 2, 3, 4), _bits(0, 1, 2, 3, 60)])
+WEIGHTINGS_AND_SCORINGS = [(s, w) for w in (0, 1, 2, 3) for s in (0, 5)]  # all four weightings, with L1 and with DOT_PRODUCT
+
+
+def unequal_tiny(scoring=0, weighting=0):
+    """_tiny() with A1 (node 4) a childless node that is no leaf: it keeps Node()'s word_id 0 together with its own weight 3.0,
+    so word 0 is shared by B (weight 1.5) and A1 (weight 3.0)"""
+    voc = _tiny(scoring, weighting)
+    voc["is_leaf"][4], voc["weight"][4] = 0, 3.0
+    return voc
+
+
+def cleared_leaves_case(scoring=0, weighting=0):
+    """(vocabulary, 2000 features): a k = 6, L = 3 tree in which about a tenth of the level-3 leaves have lost their is_leaf flag"""
+    voc = synth.make_vocabulary(6, 3, seed=21)
+    desc = synth.make_descriptors_near_words(voc, 2000, seed=22)  # drawn while every leaf still is one
+    depth = np.zeros(len(voc["parent"]), np.int64)
+    for i in range(1, len(depth)):
+        depth[i] = depth[voc["parent"][i]] + 1
+    cleared = (depth == 3) & (np.random.RandomState(23).uniform(size=len(depth)) < 0.1)
+    voc["is_leaf"] = np.where(cleared, 0, voc["is_leaf"]).astype(np.uint8)
+    voc["scoring"], voc["weighting"] = scoring, weighting
+    return voc, desc
+
+
+def check_word_zero_is_mixed(word, weight, at_least):
+    """coverage: word 0 collects `at_least` live features, and they do not all weigh the same"""
+    w0 = weight[(word == 0) & (weight > 0)]
+    assert len(w0) >= at_least and len(np.unique(w0)) >= 3, (len(w0), np.unique(w0))
+
+
+FANOUT = (1, 4, 5, 6, 11, 20)  # children of the six inner nodes; the descent compares siblings five at a time
+
+
+def fanout_tree():
+    """k = 20, L = 2, built by hand: the root's six children have FANOUT children each.  Every child descriptor is its parent's with
+    exactly 32 bits flipped, so two siblings always differ in an even number of bits and a query can sit exactly between them.
+    Returns (vocabulary, first child id of each inner node)."""
+    rng = np.random.RandomState(51)
+    inner = rng.randint(0, 256, (6, 32)).astype(np.uint8)
+    parent, desc, first = [0] + [0] * 6, [np.zeros(32, np.uint8)] + list(inner), []
+    for i, n in enumerate(FANOUT):
+        first.append(len(parent))
+        for _ in range(n):
+            flip = np.zeros(256, bool)
+            flip[rng.choice(256, 32, replace=False)] = True
+            parent.append(1 + i)
+            desc.append(inner[i] ^ np.packbits(flip, bitorder="little"))
+    n_nodes = len(parent)
+    # the pair that only the upper 16 bytes tell apart: children 1 and 2 of the 4-child node share their lower half
+    desc[first[1] + 2][:16] = desc[first[1] + 1][:16]
+    is_leaf = np.array([0] * 7 + [1] * (n_nodes - 7), np.uint8)
+    weight = np.concatenate([np.zeros(7), np.round(rng.uniform(0.5, 12.0, n_nodes - 7), 5)])
+    return dict(k=20, L=2, scoring=0, weighting=0, parent=np.array(parent, np.int32), is_leaf=is_leaf, desc=np.stack(desc),
+                weight=weight), first
+
+
+def _ham(a, b):
+    return int(np.unpackbits(a ^ b).sum())
+
+
+def _between(a, b):
+    """a descriptor at the same distance from a and from b: a with every other bit of a ^ b flipped"""
+    where = np.flatnonzero(np.unpackbits(a ^ b, bitorder="little"))
+    assert len(where) % 2 == 0 and len(where) > 0
+    flip = np.zeros(256, bool)
+    flip[where[::2]] = True
+    return a ^ np.packbits(flip, bitorder="little")
+
+
+# (inner node, tied children): the first two, pairs across every group-of-five boundary, the last child alone in its group of five,
+# the last of a full group with the very first
+TIES = [(5, 0, 1), (5, 4, 5), (5, 9, 10), (5, 14, 15), (5, 18, 19), (5, 0, 19), (4, 0, 1), (4, 4, 5), (4, 9, 10), (3, 4, 5),
+        (3, 0, 5), (2, 3, 4), (1, 0, 3)]
+
+
+def fanout_queries(voc, first):
+    """(queries, the node each must end in), every expectation established here with plain Hamming distances: exact ties that the
+    first child keeps, a pair decided in bytes 16..31 alone, a query equidistant from all 20 children, and the only child."""
+    d = voc["desc"]
+    q, want = [], []
+    for i, a, b in TIES:
+        ca, cb = first[i] + a, first[i] + b
+        q.append(_between(d[ca], d[cb]))
+        want.append(ca)
+    # upper half only: the query agrees with both children in bytes 0..15; the SECOND of the two is nearer in bytes 16..31
+    c1, c2 = first[1] + 1, first[1] + 2
+    assert np.array_equal(d[c1][:16], d[c2][:16]) and not np.array_equal(d[c1][16:], d[c2][16:])
+    hi = d[c2].copy()
+    hi[31] ^= 1
+    q.append(hi)
+    want.append(c2)
+    assert np.array_equal(hi[:16], d[c1][:16]) and _ham(hi, d[c2]) == 1 < _ham(hi, d[c1])
+    q.append(d[6].copy())  # the 20-child node's own descriptor: 32 bits from every child
+    want.append(first[5])
+    q.append(d[1].copy())  # the node with one child
+    want.append(first[0])
+    q = np.stack(q)
+    for f, node in zip(q, want):
+        par = int(voc["parent"][node])
+        top = [_ham(f, d[c]) for c in range(1, 7)]
+        assert top[par - 1] < min(t for c, t in enumerate(top) if c != par - 1)  # level 1 is decided clearly
+        sib = np.flatnonzero(voc["parent"] == par)
+        dist = np.array([_ham(f, d[c]) for c in sib])
+        assert sib[int(np.argmin(dist))] == node  # the first minimum
+    for (i, a, b), f in zip(TIES, q):
+        sib = np.flatnonzero(voc["parent"] == 1 + i)
+        dist = np.array([_ham(f, d[c]) for c in sib])
+        assert dist[a] == dist[b] == dist.min() and (dist == dist.min()).sum() == 2
+    assert len({_ham(q[-2], d[c]) for c in np.flatnonzero(voc["parent"] == 6)}) == 1
+    return q, np.array(want, np.uint32)
+
+
+def deep_tree(k):
+    """L = 10: a chain (k = 1) or a binary tree (2047 nodes)"""
+    if k == 1:
+        voc = synth.make_vocabulary(1, 10, seed=61, p_early_leaf=0.0, p_stop=0.0)
+        assert len(voc["parent"]) == 11
+        desc = np.random.RandomState(62).randint(0, 256, (40, 32)).astype(np.uint8)
+    else:
+        voc = synth.make_vocabulary(2, 10, seed=63, p_early_leaf=0.02, p_stop=0.05)
+        desc = synth.make_descriptors_near_words(voc, 600, seed=64)
+    return voc, desc
+
+
+ROOT_ONLY = dict(k=10, L=4, scoring=0, weighting=0, parent=np.zeros(1, np.int32), is_leaf=np.zeros(1, np.uint8),
+                 desc=np.zeros((1, 32), np.uint8), weight=np.zeros(1))
+
+
+def _same_as_model(oracle_mod, voc, desc, levelsup):
+    bi, bv, (fn, fo, fi) = oracle_mod.Vocabulary(voc).transform(desc, levelsup)
+    keys, vals, fv = _model_transform(voc, desc, levelsup)
+    assert list(bi) == keys and list(bv) == vals  # doubles: identical, not merely close
+    assert list(fn) == list(fv)
+    for r, node in enumerate(fn):
+        assert list(fi[fo[r]:fo[r + 1]]) == fv[int(node)]
+    return bi, bv
+
+
+def test_oracle_adds_each_features_own_weight(oracle_mod):
+    """BowVector::addWeight adds the weight of the feature at hand, not the weight the word was created with."""
+    V = oracle_mod.Vocabulary(unequal_tiny(5, 0))
+    word, _, w = V.transform_features(UNEQUAL_FEATS, 0)
+    assert list(word) == [0, 0, 0, 1, 0] and list(w) == [1.5, 3.0, 1.5, 2.0, 3.0]
+    bi, bv, _ = V.transform(UNEQUAL_FEATS, 1)
+    assert list(bi) == [0, 1] and list(bv) == [(((1.5 + 3.0) + 1.5) + 3.0) / 2, 2.0 / 2] == [4.5, 1.0]
+
+
+@pytest.mark.parametrize("scoring,weighting", WEIGHTINGS_AND_SCORINGS)
+def test_oracle_matches_literal_model_on_shared_words(oracle_mod, scoring, weighting):
+    bi, bv = _same_as_model(oracle_mod, unequal_tiny(scoring, weighting), UNEQUAL_FEATS, 1)
+    assert list(bi) == [0, 1]
+    voc, desc = cleared_leaves_case(scoring, weighting)
+    word, _, w = oracle_mod.Vocabulary(voc).transform_features(desc, 0)
+    check_word_zero_is_mixed(word, w, 100)
+    _same_as_model(oracle_mod, voc, desc, 1)
+
+
+def test_oracle_fanout_tree_ties_and_upper_half(oracle_mod):
+    voc, first = fanout_tree()
+    assert [int((voc["parent"] == 1 + i).sum()) for i in range(6)] == list(FANOUT)
+    q, want = fanout_queries(voc, first)
+    V = oracle_mod.Vocabulary(voc)
+    word, node, w = V.transform_features(q, 0)
+    assert np.array_equal(node, want) and np.array_equal(word, want - 7) and np.array_equal(w, voc["weight"][want])
+    _same_as_model(oracle_mod, voc, q, 1)
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_oracle_matches_literal_model_on_deep_trees(oracle_mod, k):
+    voc, desc = deep_tree(k)
+    for levelsup in (0, 9, 10):
+        _same_as_model(oracle_mod, voc, desc[:150], levelsup)
+    _, node, _ = oracle_mod.Vocabulary(voc).transform_features(desc, 0)
+    if k == 1:
+        assert (node == 10).all()  # the chain's end, ten levels down
+    else:
+        assert (node == NO_NODE).any() and (node != NO_NODE).any()
+
+
+def test_oracle_root_only_tree_gives_empty_maps(oracle_mod):
+    V = oracle_mod.Vocabulary(ROOT_ONLY)
+    assert V.n_words == 0
+    bi, bv, (fn, fo, fi) = V.transform(UNEQUAL_FEATS, 2)
+    assert len(bi) == len(bv) == len(fn) == len(fi) == 0 and list(fo) == [0]
+
+
 # ------------------------------------------------------------------------------------------------------------- GPU
 def _same_transform(got, want):
     (gi, gv, (gn, go, gx)), (wi, wv, (wn, wo, wx)) = got, want
