@@ -1055,6 +1055,119 @@ int orbm_cull_map_points_device(orbm_t *h, int32_t *d_recent, int32_t *d_n_recen
                                 const int32_t *d_obs_off, const int32_t *d_obs_kf, const int32_t *d_obs_kp, int n_obs, int32_t *d_code,
                                 int32_t *d_result, void *stream);
 
+/* ---- The inertial local BA window on the device-resident map ----------------------------------------------------------------------
+ * Optimize::localFullBundleAdjustment (modules/Backend/Optimize.cpp:1064-1310, what every key frame runs once the IMU is initialised)
+ * for a caller whose slot arrays, map-point table, key-frame table, state rows, record bank and priors live in device memory.  Every
+ * numeric stage of it exists: the inertial edges, priors and bias walks (orbi_factors.h), EdgeMono with the Schur complement, the
+ * 480-unknown solve and the back-substitution (the visual-window header).  This section is the piece between the map and those calls:
+ *   orbm_inertial_window_problem_device          :1073-1108, :1129-1244  steps 1 and 3: solve states, local points, fixed key frames
+ *                                                under the reference's cap, the EdgeMono arrays and the inertial side's job lists
+ *   orbm_inertial_window_velocity_prior_device   :1288 (KeyFrame::setVelocity)  velo_priori of the OLDEST key frame, step 7's remainder
+ * and the mapper step after IMU initialisation is one chain on one stream:
+ *   the assembly -> ONE read-back of d_result's first 32 bytes (the sizes are host ints of the calls below)
+ *   orbi_graph_init_device (d_init_jobs) -> orbi_edge_information_device (d_inertial_edges)
+ *   the caller's Levenberg-Marquardt loop over orbi_linearize_device (d_inertial_edges, d_prior_jobs) and the visual-window header's
+ *     calls (d_ba_points, d_edge_state, d_edge_point, d_edge_z, d_edge_inv_sigma2, d_fixed); its per-trial scalars are the only other
+ *     read-backs.  THE LOOP IS NOT HERE: its decisions are the caller's (tests/inertial_loop.py closes it as test code)
+ *   the visual-window linearisation in mode 2 -> d_outlier
+ *   orbi_graph_recover_device (d_recover_jobs; its d_pose_R / d_pose_t are T_cw of the solve states)
+ *   orbm_local_ba_apply_device, UNCHANGED, with n_local = n_solve, d_pose_kf = d_state_kf, those poses, the live point buffer and
+ *     d_outlier: the outlier observations erased with their cascade (:1263-1272), T_cw into the key-frame table (:1287), the
+ *     positions written back (:1301-1307).  The assembly emits its maps in that call's layout for exactly this
+ *   orbi_set_bias_device (d_bias_ids, the recover's d_bias; :1291) -> orbi_prior_information_device (d_prior_info_jobs; :1293-1296)
+ *   orbm_inertial_window_velocity_prior_device
+ *   orbm_build_observations_device -> orbm_refresh_points_device (d_sel = d_point_row; mp->update(), :1305)
+ * (The recover runs ahead of the apply, which reads its poses; the other calls behind the loop are independent of each other.)
+ * localInertialBundleAdjustment, inertialOptimize / fullInertialOptimize and the loop itself are not here.
+ * The two calls follow this header's rules for the map side, as "Local bundle adjustment on the device-resident map" states them:
+ * device pointers only and deliberately NO host-pointer twin; no allocation, handle scratch or host wait; results written, not
+ * accumulated; the same bytes on every run; every index that comes from device memory is distrusted -- dropped and counted, never
+ * dereferenced out of range.  THE SLOT ARRAYS ARE THE TRUTH, the CSR only tells where the slots naming a row are, and LIVE is as there.
+ * This header does not include the headers of the calls above: the job lists are int32 arrays in their documented layouts.
+ *
+ * orbm_inertial_window_problem_device.  The map as orbm_local_ba_problem_device takes it.  d_window [n_window] (device): the slots of
+ * getRecentKeyFrames(numOpt), OLDEST FIRST as Map.cpp:42-53 returns them; the caller computes numOpt = min(n - 2, 10 or 25).  d_kf_imu
+ * [n_kf][3] (device) = per key frame (its row of the 15-float state array, its record of the orbi_record bank, its orbi_prior slot), held
+ * against the host ints n_src, cap_bank, n_priors.  max_fixed: the reference's maxNumFixed, ORBM_IW_MAX_FIXED_DEFAULT.
+ *   Solve states (:1076-1079): state s is d_window[s].  The inertial chain is positional, so NOTHING IS SKIPPED -- where the local BA
+ *     drops an entry of d_local that is out of range, bad or repeated and goes on, here such an entry (outside [0, n_kf), a bad key
+ *     frame, a key frame an earlier entry named; counted in d_result[6]) REFUSES the whole call, bit 8 of d_result[5]: the call stops
+ *     there, d_result[0] = d_result[3] = n_window, every other count is 0 and no output array is written.  A window key frame one of
+ *     whose three d_kf_imu indices is out of range refuses the call as well (bit 32, counted in d_result[7]); the counts are then full.
+ *     n_solve = n_window.
+ *   Local points (:1083-1092): the rows p in [0, cap_points) with d_valid[p] != 0 named by one of the min(max(d_n[k], 0), stride) slots
+ *     of a window key frame, each numbered at its FIRST occurrence in (window position, slot) order -- the reference's BA_local_for_kf
+ *     marking, orbm_local_ba_problem_device's rule.  A row that ends up without an edge is dropped before numbering (d_result[8]).
+ *   Fixed key frames, with the reference's cap (:1095-1108): for every key frame f that is not in the window and not bad, first[f] =
+ *     the smallest local-point number with a LIVE CSR entry on f (d_result[13] counts the key frames that have one).  X = the smallest
+ *     point number at which #{f : first[f] <= X} >= max_fixed, no bound when the count never gets there; the fixed set is {f :
+ *     first[f] <= X}, INCLUSIVE -- the reference pushes every observer of a point and only then breaks.  (The kernel orders rows by
+ *     their first-occurrence keys, which order them as their numbers do, so the set needs no numbering and no order of execution.)
+ *     Fixed states follow the solve states in ASCENDING SLOT ORDER: a stated canonicalisation, the one of the local BA -- the
+ *     reference's order is the order it met them, and a fixed pose has no block in the system, so its position reaches no number.  A
+ *     fixed key frame whose state row is outside [0, n_src) refuses the call (bit 32, d_result[7]).
+ *   Edges (:1218-1244): per local point in order, its LIVE CSR entries in CSR order whose key frame is a solve or a fixed state.  A key
+ *     frame's second entry in one row gives no second edge (d_result[9]; tested first).  An entry on a live key frame that is neither a
+ *     solve nor a fixed state is dropped (d_result[11]); that only happens behind the cap and is the second stated canonicalisation:
+ *     the reference hands g2o a null vertex there.  A point with more than 256 kept edges is emitted and counted (d_result[12]): the
+ *     linearisation drops such a point whole and the caller should know.
+ *   Outputs for the visual window, in the layout its calls and orbm_local_ba_apply_device take: d_ba_points [x][3] = (double) of
+ *     d_points[d_point_row[x]]; d_point_row [x]; d_edge_off [n_points + 1]; for edge e of point x d_edge_point[e] = x (non-decreasing),
+ *     d_edge_state[e] = the state of its key frame, d_edge_z[2e ..] = the orbx_kp record's (x, y) widened, d_edge_inv_sigma2[e] =
+ *     (double)((1.f / size) / size) (:1233), d_edge_kf / d_edge_kp[e] = (key-frame slot, feature); d_state_kf [n_states] = the slots.
+ *   Outputs for the inertial side, ready job lists:
+ *     d_init_jobs [n_states][3]       orbi_graph_init_device: (state, state row, record; record -1 for a fixed state: no bias vertices)
+ *     d_fixed [n_states]              0 for a solve state, ORBI_FIX_POSE | _VELO | _GYRO | _ACC (15) for a fixed one
+ *     d_inertial_edges [n_solve - 1]  orbi_edge (4 x int32) {s, s + 1, record of key frame s, ORBI_EDGE_WALKS (1)}: :1153-1174 takes the
+ *                                     OLDER key frame's pre-integrator, and its C for both walks
+ *     d_prior_jobs [1][3]             orbi_prior_job (state 0, prior slot of the oldest key frame, VELO | GYRO | ACC | ACC_GYRO_INFO = 15), :1176-1191
+ *     d_recover_jobs [n_solve][3]     orbi_graph_recover_device: (s, state row, ORBI_RECOVER_POSE (1))
+ *     d_bias_ids [n_solve]            the records, orbi_set_bias_device's d_ids
+ *     d_prior_info_jobs [n_solve - 1][3]  orbi_prior_information_device, for s >= 1: (prior slot of key frame s, record of key frame s - 1,
+ *                                     state row of key frame s) -- :1293-1296 with bias_priori = the previous key frame's new bias
+ * Capacities: d_state_kf, d_fixed [cap_states], d_init_jobs [cap_states][3]; d_ba_points [cap_local_points][3], d_point_row
+ * [cap_local_points], d_edge_off [cap_local_points + 1]; d_edge_state, d_edge_point, d_edge_inv_sigma2, d_edge_kf, d_edge_kp [cap_edges],
+ * d_edge_z [cap_edges][2]; d_inertial_edges [n_window - 1][4], d_prior_jobs [3], d_recover_jobs [n_window][3], d_bias_ids [n_window],
+ * d_prior_info_jobs [n_window - 1][3] (none may be NULL; with n_window = 1 the two lists of n_window - 1 are not written).  d_work: the
+ * caller's work array of cap_points + 2 * n_kf int32 (contents afterwards unspecified).
+ * d_result (int32 x 16, written; the first eight -- 32 bytes -- are what the caller reads back): [0] n_states, [1] n_points, [2]
+ * n_edges, [3] n_solve, [4] n_fixed, [5] the refusal, a bit mask: 1 more states than cap_states, 2 more points than cap_local_points,
+ * 4 more edges than cap_edges, 8 a window entry unusable, 16 no edge, 32 an imu index out of range; [6] window entries unusable, [7]
+ * key frames with a d_kf_imu index out of range; [8] rows dropped for having no edge, [9] second edges of a key frame in one row,
+ * [10] CSR entries dropped for an index out of range, [11] entries dropped behind the cap, [12] points with more than 256 edges,
+ * [13] key frames that could be fixed without a cap; the rest 0.  On a refusal other than bit 8 the counts are the FULL counts, no
+ * array is written at or past its capacity, the job lists and measurements are not written and what lies below is unspecified.
+ * Shape: ONE launch of ONE workgroup of 1024 threads with barriers between the phases, as orbm_local_ba_problem_device, with which it
+ * shares the slot walk, the live-entry walk and the second-entry test (csrc/orbm_map.h) -- 10-25 key frames x 2000 slots x short lists
+ * are latency.  The cap costs one more walk of the lists (an integer atomicMin per entry) and a counting binary search of at most 18
+ * rounds over the keys.  Integer atomics only.  As compiled for gfx950 -- VGPRs / scratch / static LDS: k_iw_problem 58 / 0 /
+ * 320 B, k_iw_velocity_prior 6 / 0 / 0 B: no scratch memory, at most 64 VGPRs.
+ * Limits (ORBX_E_UNSUPPORTED above): n_window <= ORBM_IW_MAX_SOLVE (the solve's 480 unknowns), stride <= ORBM_MEDIAN_MAX_STRIDE,
+ * cap_points <= 524288.  Arguments are checked first (ORBX_E_ARG: a null pointer, a negative count, n_window, max_fixed and the
+ * capacities >= 1); without a HIP device the call fails with ORBX_E_NO_DEVICE.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+#define ORBM_IW_MAX_SOLVE 32
+#define ORBM_IW_MAX_FIXED_DEFAULT 150
+struct orbi_prior;
+int orbm_inertial_window_problem_device(orbm_t *h, const orbm_kf_table *kf, const int32_t *d_slots, int stride, const uint8_t *d_valid,
+                                        const float *d_points, int cap_points, const int32_t *d_obs_off, const int32_t *d_obs_kf,
+                                        const int32_t *d_obs_kp, int n_obs, const int32_t *d_window, int n_window, const int32_t *d_kf_imu,
+                                        int n_src, int cap_bank, int n_priors, int max_fixed, int cap_states, int cap_local_points,
+                                        int cap_edges, int32_t *d_work, double *d_ba_points, int32_t *d_point_row, int32_t *d_edge_off,
+                                        int32_t *d_edge_state, int32_t *d_edge_point, double *d_edge_z, double *d_edge_inv_sigma2,
+                                        int32_t *d_edge_kf, int32_t *d_edge_kp, int32_t *d_state_kf, int32_t *d_init_jobs, uint8_t *d_fixed,
+                                        int32_t *d_inertial_edges, int32_t *d_prior_jobs, int32_t *d_recover_jobs, int32_t *d_bias_ids,
+                                        int32_t *d_prior_info_jobs, int32_t *d_result, void *stream);
+
+/* orbm_inertial_window_velocity_prior_device.  KeyFrame::setVelocity (KeyFrame.cpp:65-69) also sets velo_priori, and step 7 calls it
+ * for every window key frame; orbi_prior_information_device does that for the key frames s >= 1 (its source state), the OLDEST gets no
+ * setPrioriInformation.  This call: with (s, row, flags) = the FIRST entry of d_recover_jobs and (state, slot, mask) = the FIRST entry
+ * of d_prior_jobs, d_priors[slot].velo_priori = d_src[15 * row + 12 ..), the three floats orbi_graph_recover_device left; bias_priori and
+ * the three information matrices of the slot are not touched.  d_priors: the orbi_prior array (36 floats a slot).  A row outside
+ * [0, n_src) or a slot outside [0, n_priors): nothing is written.  d_result (int32 x 8, written): [0] 1 written, [1] 1 dropped.
+ * One launch of one wave.  ORBX_E_ARG: a null pointer, a negative count; then ORBX_E_NO_DEVICE.  Enqueued on `stream`. */
+int orbm_inertial_window_velocity_prior_device(orbm_t *h, struct orbi_prior *d_priors, int n_priors, const float *d_src, int n_src,
+                                               const int32_t *d_recover_jobs, const int32_t *d_prior_jobs, int32_t *d_result, void *stream);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

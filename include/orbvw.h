@@ -16,9 +16,10 @@
  * IS NOT HERE: its decisions are the caller's.  A caller that closes it (tests/inertial_loop.py does, as test code): an
  * accepted trial makes d_points_out the next d_points (two buffers that swap), a rejected one restores Rwb, twb, v, bg, ba AND d_iter
  * (orbvi.h says why) and leaves d_points as it is; a refused solve (ORBI_R_REFUSED) is a rejected trial; without a user lambda init,
- * d_out[1] comes from one orbvw_reduce_device whose system is discarded.  Not here either: assembling this problem from the device-resident map
- * (getRecentKeyFrames), the setPrioriInformation chaining behind the optimisation (orbi_prior_information_device serves it), and
- * inertialOptimize / fullInertialOptimize.
+ * d_out[1] comes from one orbvw_reduce_device whose system is discarded.  Assembling this problem from the device-resident map
+ * (getRecentKeyFrames) and the job list of the setPrioriInformation chaining behind the optimisation are
+ * orbm_inertial_window_problem_device (orbm.h, "The inertial local BA window on the device-resident map"), which leaves its arrays in
+ * the layout of the calls below.  Not here: inertialOptimize / fullInertialOptimize.
  *
  * This header includes orbvi.h and nothing includes it.  Same rules as there: handle-less `*_device` entry points under the one
  * stream rule of orbx.h ("Streams and threads") -- a call enqueues on exactly the `stream` it is given (a hipStream_t; NULL is stream

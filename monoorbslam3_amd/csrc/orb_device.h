@@ -47,6 +47,23 @@ template <int WAVES> __device__ __forceinline__ int block_scan(int v, int *s_wav
     return before;
 }
 
+// block_scan of the pair (a, b) with one pair of barriers: both exclusive scans and both totals; s_wave is 2 x WAVES ints
+template <int WAVES> __device__ __forceinline__ void block_scan2(int a, int b, int (*s_wave)[WAVES], int &ea, int &eb, int &ta, int &tb)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ia = wave_scan(a), ib = wave_scan(b);
+    if (lane == 63) s_wave[0][wave] = ia, s_wave[1][wave] = ib;
+    __syncthreads();
+    ea = ia - a, eb = ib - b, ta = 0, tb = 0;
+#pragma unroll 1
+    for (int w = 0; w < WAVES; ++w) {
+        const int xa = s_wave[0][w], xb = s_wave[1][w];
+        if (w < wave) ea += xa, eb += xb;
+        ta += xa, tb += xb;
+    }
+    __syncthreads();                                               // read by everyone before the next scan overwrites the totals
+}
+
 // the sums of N per-thread counts over the workgroup into s_count[slot[n]] (LDS, or a result array in device memory): block_add(s_count,
 // {SLOT_A, SLOT_B}, {a, b}).  The wave reductions come first, so that their shuffles overlap; the caller's barrier follows
 template <int N> __device__ __forceinline__ void block_add(int *s_count, const int (&slot)[N], const int (&v)[N])

@@ -54,24 +54,7 @@ enum { A_ERASED = 0, A_POINTS_BAD = 1, A_CLEARED = 2, A_MOVED = 3, A_ROWS = 4, A
 // CSR entry j as an observation of row p; the slot is read with ld, as k_lba_apply's other threads clear slots in the same phase
 template <bool W> __device__ __forceinline__ bool live_entry(const MapViewOf<W> &m, int j, int p, int &k, int &i)
 {
-    return map_entry(m, j, k, i) && map_live<true>(m, k, i, p);
-}
-
-// exclusive scan of (a, b) over the workgroup in thread order and both totals; s_wave is 2 x LB_WAVES ints
-__device__ __forceinline__ void block_scan2(int a, int b, int (*s_wave)[LB_WAVES], int &ea, int &eb, int &ta, int &tb)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int ia = wave_scan(a), ib = wave_scan(b);
-    if (lane == 63) s_wave[0][wave] = ia, s_wave[1][wave] = ib;
-    __syncthreads();
-    ea = ia - a, eb = ib - b, ta = 0, tb = 0;
-#pragma unroll 1
-    for (int w = 0; w < LB_WAVES; ++w) {
-        const int xa = s_wave[0][w], xb = s_wave[1][w];
-        if (w < wave) ea += xa, eb += xb;
-        ta += xa, tb += xb;
-    }
-    __syncthreads();                                               // read by everyone before the next scan overwrites the totals
+    return map_live_entry<true>(m, j, p, k, i);
 }
 
 struct ProblemArgs {
@@ -99,11 +82,9 @@ __device__ __forceinline__ int problem_edges(const ProblemArgs &a, int32_t *work
     int b, e, n = 0;
     map_list(a.m, p, b, e);
     for (int j = b; j < e; ++j) {
-        int k, i, k2, i2;
+        int k, i;
         if (!live_entry(a.m, j, p, k, i)) continue;
-        bool again = false;                                        // a key frame twice: the LM refuses such a problem
-        for (int j2 = b; j2 < j && !again; ++j2) again = live_entry(a.m, j2, p, k2, i2) && k2 == k;
-        if (again) {
+        if (map_second_entry<true>(a.m, b, j, p, k)) {             // a key frame twice: the LM refuses such a problem
             second += !WRITE;
             continue;
         }
@@ -143,39 +124,27 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
     const bool keep = first && !is_bad;
     const int local_dropped = tid < a.n_local && (!in_range || (!is_bad && !first));
     int li, unused, n_loc, n_local_dropped;
-    block_scan2(keep, local_dropped, s_wave, li, unused, n_loc, n_local_dropped);
+    block_scan2<LB_WAVES>(keep, local_dropped, s_wave, li, unused, n_loc, n_local_dropped);
     int skipped_bad, n_local_bad, has_first, n_has_first;
-    block_scan2(is_bad, keep && mine == a.first_kf, s_wave, skipped_bad, has_first, n_local_bad, n_has_first);
+    block_scan2<LB_WAVES>(is_bad, keep && mine == a.first_kf, s_wave, skipped_bad, has_first, n_local_bad, n_has_first);
     if (first) work_kf[mine] = keep ? li : MAP_NONE;               // every read of the first positions lies before the scans' barriers
     if (keep) s_local[li] = mine;
     __syncthreads();
     // ---- 2: the rows named by a slot of a local key frame, and where first (:783-792)
     const int total = n_loc * m.stride;                            // <= 1024 * 8192
-    for (int t = tid; t < total; t += LB_T) {
-        const int l = t / m.stride, i = t - l * m.stride, k = s_local[l];
-        if (i >= map_slots(m, k)) continue;
-        const int p = m.slots[(size_t)k * m.stride + i];
-        if (p >= 0 && p < m.cap_points && m.valid[p]) atomicMin(&work_row[p], l << MAP_KEY_SHIFT | i);
-    }
+    map_mark_first<LB_T>(s_local, n_loc, m, work_row);
     __syncthreads();
     // ---- 3: points and edges in the order of first occurrence (:860-889)
     int n_points = 0, n_edges = 0;                                  // the same in every thread
     for (int t0 = 0; t0 < total; t0 += LB_T) {
-        const int t = t0 + tid;
-        int p = -1, cnt = 0;
-        bool is_first = false;
-        if (t < total) {
-            const int l = t / m.stride, i = t - l * m.stride, k = s_local[l];
-            if (i < map_slots(m, k)) {
-                p = m.slots[(size_t)k * m.stride + i];
-                is_first = p >= 0 && p < m.cap_points && m.valid[p] && work_row[p] == (l << MAP_KEY_SHIFT | i);
-            }
-        }
+        const int p = map_first_at(s_local, total, m, work_row, t0 + tid);
+        const bool is_first = p >= 0;
+        int cnt = 0;
         if (is_first) cnt = problem_edges<false>(a, work_kf, p, 0, 0, second);
         const bool has = is_first && cnt > 0;
         no_edge += is_first && cnt == 0;
         int my_point, my_edge, tile_points, tile_edges;
-        block_scan2(has, cnt, s_wave, my_point, my_edge, tile_points, tile_edges);
+        block_scan2<LB_WAVES>(has, cnt, s_wave, my_point, my_edge, tile_points, tile_edges);
         if (has) {
             const int idx = n_points + my_point, e0 = n_edges + my_edge;
             if (idx < a.cap_local_points) {
@@ -193,7 +162,7 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
         const int k = k0 + tid;
         const bool fixed = k < m.n_kf && work_kf[k] == LB_FIXED;
         int my, tile;
-        block_scan2(fixed, 0, s_wave, my, unused, tile, unused);
+        block_scan2<LB_WAVES>(fixed, 0, s_wave, my, unused, tile, unused);
         if (fixed) {
             const int q = n_loc + n_fixed + my;
             work_kf[k] = q;
@@ -227,11 +196,8 @@ __global__ __launch_bounds__(LB_T) void k_lba_problem(const ProblemArgs a)
     }
     for (int x = tid; x < n_edges; x += LB_T) {
         const int k = a.o_edge_kf[x], i = a.o_edge_kp[x];
-        const orbx_kp *kp = (const orbx_kp *)a.kps[k] + i;
         a.o_edge_pose[x] = work_kf[k];
-        a.o_edge_z[(size_t)x * 2] = (double)kp->x, a.o_edge_z[(size_t)x * 2 + 1] = (double)kp->y;
-        const float size = kp->size;
-        a.o_edge_inv_sigma2[x] = (double)((1.f / size) / size);   // :877
+        map_edge_measurement(a.kps, k, i, a.o_edge_z + (size_t)x * 2, a.o_edge_inv_sigma2 + x);   // :871-877
     }
 }
 

@@ -77,6 +77,56 @@ template <bool RELAXED = false, bool W> __device__ __forceinline__ bool map_live
     return (RELAXED ? ld(map_slot(m, k, i)) : *map_slot(m, k, i)) == p && m.bad[k] == 0;
 }
 
+// CSR entry j as an observation of row p NOW -> (k, i): usable and live
+template <bool RELAXED = false, bool W> __device__ __forceinline__ bool map_live_entry(const MapViewOf<W> &m, int j, int p, int &k, int &i)
+{
+    return map_entry(m, j, k, i) && map_live<RELAXED>(m, k, i, p);
+}
+
+// the second-entry test of the two bundle adjustments' assemblies: does a live entry of row p's list before j, in [b, j), name key
+// frame k as well?  Found by re-reading the list's start: n^2 / 2 reads for a list of n, nothing for the 2-30 of a map
+template <bool RELAXED = false, bool W> __device__ __forceinline__ bool map_second_entry(const MapViewOf<W> &m, int b, int j, int p, int k)
+{
+    bool again = false;
+    int k2, i2;
+    for (int j2 = b; j2 < j && !again; ++j2) again = map_live_entry<RELAXED>(m, j2, p, k2, i2) && k2 == k;
+    return again;
+}
+
+// The slot walk of the two bundle adjustments' assemblies over the key frames s_kf[0 .. n_list) (LDS), slot t = (position, slot) =
+// (t / stride, t % stride) of n_list * stride.  map_mark_first: every valid row named by one of those slots gets in work_row[] the least
+// (position << 13 | slot) naming it (atomicMin: whatever the order); work_row holds MAP_NONE behind a barrier, the caller's barrier
+// follows.  map_first_at: the row slot t names if t is that row's first occurrence, else -1 -- the caller takes the slots in order,
+// a tile of THREADS at a time, and numbers what it keeps of them by a block scan
+template <int THREADS, bool W> __device__ __forceinline__ void map_mark_first(const int *s_kf, int n_list, const MapViewOf<W> &m, int32_t *work_row)
+{
+    const int total = n_list * m.stride;                           // <= 1024 * 8192
+    for (int t = threadIdx.x; t < total; t += THREADS) {
+        const int l = t / m.stride, i = t - l * m.stride, k = s_kf[l];
+        if (i >= map_slots(m, k)) continue;
+        const int p = m.slots[(size_t)k * m.stride + i];
+        if (p >= 0 && p < m.cap_points && m.valid[p]) atomicMin(&work_row[p], l << MAP_KEY_SHIFT | i);
+    }
+}
+template <bool W> __device__ __forceinline__ int map_first_at(const int *s_kf, int total, const MapViewOf<W> &m, const int32_t *work_row, int t)
+{
+    if (t >= total) return -1;
+    const int l = t / m.stride, i = t - l * m.stride, k = s_kf[l];
+    if (i >= map_slots(m, k)) return -1;
+    const int p = m.slots[(size_t)k * m.stride + i];
+    return p >= 0 && p < m.cap_points && m.valid[p] && work_row[p] == (l << MAP_KEY_SHIFT | i) ? p : -1;
+}
+
+// An EdgeMono's / EdgeSE3ProjectXYZ's measurement and information from the orbx_kp record of feature i of key frame k (Optimize.cpp:871-877,
+// :1228-1234): kp.pt widened, invSigma2 = (double)((1.f / size) / size) -- the reference's float expression, written once
+__device__ __forceinline__ void map_edge_measurement(const void *const *kps, int k, int i, double *z, double *inv_sigma2)
+{
+    const orbx_kp *kp = (const orbx_kp *)kps[k] + i;
+    z[0] = (double)kp->x, z[1] = (double)kp->y;
+    const float size = kp->size;
+    *inv_sigma2 = (double)((1.f / size) / size);
+}
+
 // a list length read from device memory, kept inside the row
 template <bool W> __device__ __forceinline__ int graph_list_length(const GraphViewOf<W> &g, int k) { return min(max(g.ord_n[k], 0), g.n_kf); }
 

@@ -148,6 +148,9 @@ def _mlib():
                                              + [vp] * 16),
             "orbm_local_ba_apply_device": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32]
                                            + [vp] * 11),
+            "orbm_inertial_window_problem_device": (i32, [vp, C.POINTER(KfTable), vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32,
+                                                          i32, i32, i32] + [vp] * 20),
+            "orbm_inertial_window_velocity_prior_device": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp]),
             "orbm_update_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, i32, i32, i32, vp, vp, vp]),
             "orbm_erase_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, i32, vp, vp, vp, vp]),
             "orbm_fuse_targets_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp,
@@ -682,6 +685,34 @@ class ORBMatcher:
             p("edge_off"), p("edge_kf"), p("edge_kp"), p("est_pose_R"), p("est_pose_t"), p("est_points"), p("outlier"), p("result"),
             _lib.stream_arg(stream)))
 
+    # -- Optimize::localFullBundleAdjustment on the slot arrays: the window assembled (Optimize.cpp:1073-1108, :1129-1244) --
+    def InertialWindowProblemDevice(self, kf, d, stride, cap_points, n_obs, n_window, n_src, cap_bank, n_priors, max_fixed, cap_states,
+                                    cap_local_points, cap_edges, stream=None):
+        """orbm_inertial_window_problem_device: kf a KfTable.  d: dict of torch device tensors -- in: slots, valid, points, obs_off,
+        obs_kf, obs_kp as LocalBaProblemDevice takes them, window i32 [n_window] (getRecentKeyFrames, oldest first), kf_imu i32 [n_kf,3]
+        (state row, record, prior slot); work i32 [cap + 2 n_kf]; out, for the visual window: ba_points f64 [cap_local_points,3],
+        point_row i32 [cap_local_points], edge_off i32 [cap_local_points + 1], edge_state, edge_point i32 [cap_edges], edge_z f64
+        [cap_edges,2], edge_inv_sigma2 f64 [cap_edges], edge_kf, edge_kp i32 [cap_edges], state_kf i32 [cap_states]; for the inertial
+        side: init_jobs i32 [cap_states,3], fixed u8 [cap_states], inertial_edges i32 [n_window - 1,4], prior_jobs i32 [3], recover_jobs
+        i32 [n_window,3], bias_ids i32 [n_window], prior_info_jobs i32 [n_window - 1,3]; result i32 [16] ([0] n_states, [1] n_points,
+        [2] n_edges, [3] n_solve, [4] n_fixed, [5] refusal mask).  Enqueues on `stream`; nothing is copied or synchronised.  There is
+        no host-pointer twin (include/orbm.h)."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_inertial_window_problem_device(
+            self._hd._h, C.byref(kf), p("slots"), stride, p("valid"), p("points"), cap_points, p("obs_off"), p("obs_kf"), p("obs_kp"), n_obs,
+            p("window"), n_window, p("kf_imu"), n_src, cap_bank, n_priors, max_fixed, cap_states, cap_local_points, cap_edges, p("work"),
+            p("ba_points"), p("point_row"), p("edge_off"), p("edge_state"), p("edge_point"), p("edge_z"), p("edge_inv_sigma2"), p("edge_kf"),
+            p("edge_kp"), p("state_kf"), p("init_jobs"), p("fixed"), p("inertial_edges"), p("prior_jobs"), p("recover_jobs"), p("bias_ids"),
+            p("prior_info_jobs"), p("result"), _lib.stream_arg(stream)))
+
+    def InertialWindowVelocityPriorDevice(self, d, n_priors, n_src, stream=None):
+        """orbm_inertial_window_velocity_prior_device: d = dict of torch device tensors -- in / out: priors (the orbi_prior array, 36
+        floats a slot); in: src f32 [n_src,15] (the state rows the recover wrote), recover_jobs, prior_jobs (the assembly's); out: result
+        i32 [8].  The oldest key frame's velo_priori takes its recovered velocity.  Enqueues on `stream`."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_inertial_window_velocity_prior_device(
+            self._hd._h, p("priors"), n_priors, p("src"), n_src, p("recover_jobs"), p("prior_jobs"), p("result"), _lib.stream_arg(stream)))
+
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
         orbf_frame_post_device leaves it), desc2, cell_start, cell_items, pre (float32 [n1, 2], in / out), matches12 (int32 [n1], out),
@@ -747,3 +778,16 @@ def local_ba_problem_device(matcher, *args, **kwargs):
 def local_ba_apply_device(matcher, *args, **kwargs):
     """ORBMatcher.LocalBaApplyDevice (orbm_local_ba_apply_device)"""
     return matcher.LocalBaApplyDevice(*args, **kwargs)
+
+
+IW_MAX_SOLVE, IW_MAX_FIXED_DEFAULT = 32, 150   # ORBM_IW_MAX_SOLVE, ORBM_IW_MAX_FIXED_DEFAULT
+
+
+def inertial_window_problem_device(matcher, *args, **kwargs):
+    """ORBMatcher.InertialWindowProblemDevice (orbm_inertial_window_problem_device)"""
+    return matcher.InertialWindowProblemDevice(*args, **kwargs)
+
+
+def inertial_window_velocity_prior_device(matcher, *args, **kwargs):
+    """ORBMatcher.InertialWindowVelocityPriorDevice (orbm_inertial_window_velocity_prior_device)"""
+    return matcher.InertialWindowVelocityPriorDevice(*args, **kwargs)
