@@ -1168,6 +1168,37 @@ int orbm_inertial_window_problem_device(orbm_t *h, const orbm_kf_table *kf, cons
 int orbm_inertial_window_velocity_prior_device(orbm_t *h, struct orbi_prior *d_priors, int n_priors, const float *d_src, int n_src,
                                                const int32_t *d_recover_jobs, const int32_t *d_prior_jobs, int32_t *d_result, void *stream);
 
+/* ---- The map rescaled and rotated on the device ------------------------------------------------------------------------------------
+ * Map::applyScaleRotation (modules/BasicObject/Map.cpp:96-124), what LocalMapping::initializeIMU does with the gravity direction and
+ * the scale its optimisation found (LocalMapping.cpp:435-445), for a caller whose key-frame table, state rows, prior slots and map-point
+ * table live in device memory.  The steps ahead of it are orbii.h's; this header does not include it.
+ *   d_summary [10] (device, float): Rwy = d_summary[0..9) row-major and s = d_summary[9], as orbii_recover_device leaves them.  THEY ARE
+ *     READ ON THE DEVICE, and so is the reference's decision (LocalMapping.cpp:435-439): with be_first != 0 and s < min_scale (0.1f) the
+ *     call writes NOTHING but d_result, where [3] = 1 -- the chain needs no host wait to honour it.
+ *   Otherwise, float, no fused multiply-add, product-sums as (p0 + p1) + p2, Ryw = Rwy^T, (Ryw * x) * s read left to right:
+ *     per key frame k < n_kf with d_bad[k] == 0 (T_cw = d_pose_R / d_pose_t [k], doubles rounded to float first; the results are stored
+ *     as doubles holding floats):  R_cw <- R_cw * Rwy;  t_cw <- t_cw * s with be_first, else unchanged  (KeyFrame::setPose, Map.cpp:103-105).
+ *     Through d_kf_imu [n_kf][3] = (state row, record, prior slot), the map of orbm_inertial_window_problem_device: the state row's
+ *     (Rwb, twb) = T_cw.inverse() * T_cb of the NEW pose (KeyFrame.cpp:33), by the code of orbi_imu_pose_device; its v <- (Ryw * v) * s
+ *     (without `* s` when be_first == 0), which also goes to velo_priori of the prior slot (KeyFrame::setVelocity).  A key frame whose
+ *     state row or prior slot is outside [0, n_src) / [0, n_priors) ([1]), or names the row or slot of an earlier key frame that is not bad
+ *     ([2]), has its pose updated and neither its row nor its slot touched.  The record is not read.
+ *     per row p < min(max(*d_n_points, 0), cap_points) with d_valid[p] != 0:  pos <- (Ryw * pos) * s  (Map.cpp:117-119).
+ *   mp->update() (Map.cpp:120) is the caller's orbm_build_observations_device + orbm_refresh_points_device over all rows, and
+ *   tracker->updateFrameIMU() is orbi_predict_device; both exist.
+ * d_result (int32 x 8, written): [0] key frames whose row and slot were written, [1], [2] as above, [3] 1 when refused, [4] points moved.
+ * calib: a host struct (orbi.h's orbi_calib), copied into the launch.  Device pointers only, no host-pointer twin, no allocation, no
+ * handle scratch, no host wait; integer atomics only, so the same input gives the same bytes.  Three launches: the counters, a wave per
+ * key frame (four per workgroup), a thread per point row.  As compiled for gfx950 -- VGPRs / scratch / static LDS: k_rescale_begin
+ * 2 / 0 / 0 B, k_rescale_kf 12 / 0 / 768 B, k_rescale_points 10 / 0 / 4 B.
+ * Arguments are checked first (ORBX_E_ARG: a null pointer, a negative count; ORBX_E_UNSUPPORTED: cap_points > 524288); without a HIP
+ * device the call fails with ORBX_E_NO_DEVICE.  n_kf = 0 and cap_points = 0 are allowed.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+struct orbi_calib;
+int orbm_apply_scale_rotation_device(orbm_t *h, const struct orbi_calib *calib, int n_kf, double *d_pose_R, double *d_pose_t,
+                                     const uint8_t *d_bad, const int32_t *d_kf_imu, float *d_state, int n_src, struct orbi_prior *d_priors,
+                                     int n_priors, float *d_points, const uint8_t *d_valid, const int32_t *d_n_points, int cap_points,
+                                     const float *d_summary, int be_first, float min_scale, int32_t *d_result, void *stream);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

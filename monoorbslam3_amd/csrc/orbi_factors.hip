@@ -28,6 +28,7 @@
 #include "orb_math.h"
 #include "orbi_graph_device.h"
 #include "orbi_so3.h"
+#include "orbi_so3d.h"
 
 #pragma clang fp contract(off)
 
@@ -35,32 +36,6 @@ static_assert(sizeof(orbi_edge) == 16 && sizeof(orbi_prior) == 144 && sizeof(orb
               "orbi_factors.h fixes these layouts");
 
 namespace {
-
-__device__ __forceinline__ double dmul(double a, double b) { return ORB_DMUL(a, b); }
-// entries (i, j) of A*B, A^T*B, A*B^T, A^T*B^T and (s*hat(x,y,z))*hat(x,y,z); matrices row-major
-__device__ __forceinline__ double dm3(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[3 * i], B[j]), dmul(A[3 * i + 1], B[3 + j]), dmul(A[3 * i + 2], B[6 + j])); }
-__device__ __forceinline__ double dm3t(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[i], B[j]), dmul(A[3 + i], B[3 + j]), dmul(A[6 + i], B[6 + j])); }
-__device__ __forceinline__ double dm3nt(const double *A, const double *B, int i, int j) { return dsum3(dmul(-A[3 * i], B[3 * j]), dmul(-A[3 * i + 1], B[3 * j + 1]), dmul(-A[3 * i + 2], B[3 * j + 2])); } // (-A)*B^T
-__device__ __forceinline__ double dm3tt(const double *A, const double *B, int i, int j) { return dsum3(dmul(A[i], B[3 * j]), dmul(A[3 + i], B[3 * j + 1]), dmul(A[6 + i], B[3 * j + 2])); }
-__device__ __forceinline__ double dmv3t(const double *A, double x0, double x1, double x2, int i) { return dsum3(dmul(A[i], x0), dmul(A[3 + i], x1), dmul(A[6 + i], x2)); } // (A^T*x)_i
-__device__ __forceinline__ double dhat(double x, double y, double z, int e)
-{
-    return e == 1 ? -z : e == 2 ? y : e == 3 ? z : e == 5 ? -x : e == 6 ? -y : e == 7 ? x : 0.0;
-}
-__device__ __forceinline__ double deye(int e) { return (e == 0 || e == 4 || e == 8) ? 1.0 : 0.0; }
-__device__ __forceinline__ double dsww(double s, double x, double y, double z, int i, int j) // ((s*W)*W)_ij, W = Hat(x, y, z), zeros multiplied
-{
-    return dsum3(dmul(dmul(s, dhat(x, y, z, 3 * i)), dhat(x, y, z, j)), dmul(dmul(s, dhat(x, y, z, 3 * i + 1)), dhat(x, y, z, 3 + j)),
-                 dmul(dmul(s, dhat(x, y, z, 3 * i + 2)), dhat(x, y, z, 6 + j)));
-}
-__device__ __forceinline__ double dnorm2(double x, double y, double z) { return dsum3(dmul(x, x), dmul(y, y), dmul(z, z)); }
-// the double Newton step towards the polar factor: NormalizeRotationf's sequence, widened
-__device__ __forceinline__ double dcof(const double *X, int i, int j)
-{
-    const int p = i == 2 ? 0 : i + 1, r = i == 0 ? 2 : i - 1, q = j == 2 ? 0 : j + 1, s = j == 0 ? 2 : j - 1;
-    return dmul(X[3 * p + q], X[3 * r + s]) - dmul(X[3 * p + s], X[3 * r + q]);
-}
-__device__ __forceinline__ double ddet(const double *X) { return dsum3(dmul(X[0], dcof(X, 0, 0)), dmul(X[1], dcof(X, 0, 1)), dmul(X[2], dcof(X, 0, 2))); }
 
 constexpr int FAC_WAVES = 4, FAC_T = 64 * FAC_WAVES;
 
@@ -204,20 +179,6 @@ __global__ __launch_bounds__(64) void k_fac_init(const orbi_graph g, const orbi_
     flush_counts(s_cnt, result);
 }
 
-// NormalizeRotation in double: two Newton steps, in registers
-__device__ __forceinline__ void dnormalize(double X[9])
-{
-#pragma unroll
-    for (int step = 0; step < 2; ++step) {
-        double Y[9];
-        const double det = ddet(X);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) Y[k] = dmul(0.5, X[k] + dcof(X, k / 3, k % 3) / det);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) X[k] = Y[k];
-    }
-}
-
 __global__ __launch_bounds__(64) void k_fac_oplus(const orbi_graph g, const double *__restrict__ dx, int32_t *__restrict__ iter,
                                                   int32_t *__restrict__ result)
 {
@@ -234,13 +195,7 @@ __global__ __launch_bounds__(64) void k_fac_oplus(const orbi_graph g, const doub
             for (int k = 0; k < 9; ++k) R[k] = g.Rwb[9 * (size_t)s + k];
 #pragma unroll
             for (int k = 0; k < 3; ++k) g.twb[3 * (size_t)s + k] = g.twb[3 * (size_t)s + k] + dsum3(dmul(R[3 * k], d[3]), dmul(R[3 * k + 1], d[4]), dmul(R[3 * k + 2], d[5]));
-            const double x = d[0], y = d[1], z = d[2];
-            const double d2 = dnorm2(x, y, z), dd = sqrt(d2);
-            const bool small = dd < 1e-6;
-            const double s1 = small ? 1.0 : sin(dd) / dd, s2 = small ? 0.5 : (1.0 - cos(dd)) / d2;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) E[k] = (deye(k) + dmul(s1, dhat(x, y, z, k))) + dsww(s2, x, y, z, k / 3, k % 3);
-            dnormalize(E);                  // ExpSO3 returns NormalizeRotation(res)
+            dexp_so3(d[0], d[1], d[2], E);   // ExpSO3 returns NormalizeRotation(res)
 #pragma unroll
             for (int k = 0; k < 9; ++k) N[k] = dm3(R, E, k / 3, k % 3);
             const int it = iter[s] + 1;
@@ -417,8 +372,8 @@ enum { ST_OK = 0, ST_RANGE = 1, ST_REFUSED = 3 };   // == ORBI_R_DONE, ORBI_R_RA
 
 // a wave's LDS slice: floats (the record's first 79 floats as orbi_record lays them out, then the float temporaries) and doubles
 enum {
-    F_BIAS = 0, F_DT = 18, F_DR = 19, F_DV = 28, F_DP = 31, F_JRG = 34, F_JVG = 43, F_JVA = 52, F_JPG = 61, F_JPA = 70, F_REC = 79,
-    X_DB = 79, X_TH = 85, X_DVP = 88, X_W = 94, X_E = 103, X_M = 112, X_M2 = 121, X_DRU = 130, X_WORDS = 140
+    F_BIAS = RH_BIAS, F_DT = RH_DT, F_JRG = RH_JRG, F_JPA = RH_JPA, F_REC = RH_WORDS,
+    X_DB = F_REC + BD_DB, X_DVP = F_REC + BD_DVP, X_DRU = F_REC + BD_DRU, X_WORDS = 140   // the temporaries of bias_deltas (orbi_so3.h)
 };
 enum {
     D_R1 = 0, D_R2 = 9, D_T1 = 18, D_T2 = 21, D_V1 = 24, D_V2 = 27, D_B1 = 30, D_B2 = 36,   // (bg, ba) of state i, of state j
@@ -501,26 +456,7 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
     const int fix_i = a.g.fixed[si], fix_j = a.g.fixed[sj];
     WSYNC();
     // ---- the float part: the bias vertices cast to float, getDeltaRotation / Velocity / Position (Imu.cpp:182-192)
-    if (lane < 6) F[X_DB + lane] = sub((float)S[D_B1 + lane], F[F_BIAS + lane]);
-    WSYNC();
-    if (lane < 3) F[X_TH + lane] = mv3(F + F_JRG, F + X_DB, lane);
-    else if (lane < 6) F[X_DVP + lane - 3] = add(add(F[F_DV + lane - 3], mv3(F + F_JVG, F + X_DB, lane - 3)), mv3(F + F_JVA, F + X_DB + 3, lane - 3));
-    else if (lane < 9) F[X_DVP + lane - 3] = add(add(F[F_DP + lane - 6], mv3(F + F_JPG, F + X_DB, lane - 6)), mv3(F + F_JPA, F + X_DB + 3, lane - 6));
-    WSYNC();
-    {
-        const float tx = F[X_TH], ty = F[X_TH + 1], tz = F[X_TH + 2];
-        const So3 so = so3_scalars(tx, ty, tz);
-        if (g == 0) F[X_W + q] = hat(tx, ty, tz, q);
-        WSYNC();
-        if (g == 0) F[X_E + q] = exp_entry(so, F + X_W, q);
-        WSYNC();
-        if (g == 0) F[X_M + q] = m3(F + F_DR, F + X_E, i, j);
-        WSYNC();
-        if (g == 0) F[X_M2 + q] = newton_entry(F + X_M, i, j);
-        WSYNC();
-        if (g == 0) F[X_DRU + q] = newton_entry(F + X_M2, i, j);
-        WSYNC();
-    }
+    bias_deltas(F, F + F_REC, lane, lane < 6 ? (float)S[D_B1 + lane] : 0.f);
     if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = lane < 9 ? F[X_DRU + lane] : F[X_DVP + lane - 9];
     // ---- everything behind the cast to double
     const double dt = (double)F[F_DT], G = (double)a.gravity;
@@ -547,32 +483,15 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
     WSYNC();
     if (g == 0) S[D_ER + q] = dm3(S + D_A1, S + D_R2, i, j);                      // eR
     else if (g == 1) {                                                            // RightJacobianSO3(JRg * delta_bg)
-        const double x = S[D_TH], y = S[D_TH + 1], z = S[D_TH + 2];
-        const double d2 = dnorm2(x, y, z), d = sqrt(d2);
-        double v = deye(q);
-        if (!(d < 1e-6)) v = (deye(q) - dmul((1.0 - cos(d)) / d2, dhat(x, y, z, q))) + dsww((d - sin(d)) / dmul(d2, d), x, y, z, i, j);
+        const double v = dright_jacobian(S[D_TH], S[D_TH + 1], S[D_TH + 2], q);
         S[D_JR + q] = v;
     }
     WSYNC();
     {   // LogSO3(eR) and InverseRightJacobianSO3(er), the scalars in every lane
-        const double *R = S + D_ER;
-        const double tr = (R[0] + R[4]) + R[8];
-        double er0 = 0.0, er1 = 0.0, er2 = 0.0;
-        if (tr != 3.0) {
-            const double w0 = dmul(0.5, R[7] - R[5]), w1 = dmul(0.5, R[2] - R[6]), w2 = dmul(0.5, R[3] - R[1]);
-            const double sn = sqrt(dnorm2(w0, w1, w2)), cs = dmul(0.5, tr - 1.0);
-            const double th = atan2(sn, cs);
-            if (fabs(th) < 1e-6) er0 = w0, er1 = w1, er2 = w2;
-            else er0 = dmul(th, w0) / sn, er1 = dmul(th, w1) / sn, er2 = dmul(th, w2) / sn;
-        }
-        const double d2 = dnorm2(er0, er1, er2), d = sqrt(d2);
+        double er0, er1, er2;
+        dlog_so3(S + D_ER, er0, er1, er2);
         if (g == 0) {
-            double v = deye(q);
-            if (!(d < 1e-6)) {
-                const double coef = 1.0 / d2 - (1.0 + cos(d)) / dmul(dmul(2.0, d), sin(d));
-                v = (deye(q) + dhat(er0, er1, er2, q) / 2.0) + dsww(coef, er0, er1, er2, i, j);
-            }
-            S[D_INVJ + q] = v;
+            S[D_INVJ + q] = dinverse_right_jacobian(er0, er1, er2, q);
         } else if (g == 1 && q < 3) S[D_E + q] = q == 0 ? er0 : q == 1 ? er1 : er2;
     }
     WSYNC();

@@ -401,17 +401,11 @@ __global__ __launch_bounds__(64) void k_imu_pose(const orbi_calib cal, const dou
                                                  float *__restrict__ dst)
 {
     __shared__ float R[9], t[3], s_cb[12], twc[3];
-    const int lane = threadIdx.x, i = lane / 3, j = lane - 3 * i;
+    const int lane = threadIdx.x;
     if (lane < 9) R[lane] = (float)pose_R[lane], s_cb[lane] = cal.Rcb[lane];
     if (lane < 3) t[lane] = (float)pose_t[lane], s_cb[9 + lane] = cal.tcb[lane];
     WSYNC();
-    if (lane < 3) twc[lane] = sum3(mul(-R[lane], t[0]), mul(-R[3 + lane], t[1]), mul(-R[6 + lane], t[2]));
-    WSYNC();
-    if (lane < 9) dst[lane] = m3t(R, s_cb, i, j);                                                  // Rcw^T * Rcb
-    else if (lane < 12) {
-        const int k = lane - 9;
-        dst[lane] = add(sum3(mul(R[k], s_cb[9]), mul(R[3 + k], s_cb[10]), mul(R[6 + k], s_cb[11])), twc[k]);   // Rcw^T * tcb + twc
-    }
+    imu_pose_from_camera(R, t, s_cb, twc, dst, lane);
 }
 
 int check_bank(const void *bank, int cap, int n, const void *result)

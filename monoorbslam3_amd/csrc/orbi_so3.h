@@ -1,4 +1,4 @@
-// Float SO(3) helpers shared by the IMU kernels (orbi_imu.hip, orbi_factors.hip): the wave-level fence, the IEEE +, -, *, / wrappers
+// Float SO(3) helpers shared by the IMU kernels (orbi_imu.hip, orbi_factors.hip, orbii.hip, orbm_rescale.hip): the wave-level fence, the IEEE +, -, *, / wrappers
 // and the 3x3 products, ExpSO3f, RightJacobianSO3f and the Newton NormalizeRotationf in the evaluation orders include/orbi.h fixes.
 // Internal: everything is a macro or a forced-inline device function inside an anonymous namespace, so it adds no symbol.
 #pragma once
@@ -80,6 +80,50 @@ __device__ __forceinline__ float newton_entry(const float *X, int i, int j)
 {
     const float det = sum3(mul(X[0], cof(X, 0, 0)), mul(X[1], cof(X, 0, 1)), mul(X[2], cof(X, 0, 2)));
     return mul(0.5f, add(X[3 * i + j], dvd(cof(X, i, j), det)));
+}
+
+// ---- what the kernels on an orbi_record's head share ----------------------------------------------------------------------------------
+// the head of an orbi_record in floats (== offsetof(orbi_record, ...) / 4; the sources that use it assert that)
+enum { RH_BIAS = 0, RH_UPD = 6, RH_DELTA = 12, RH_DT = 18, RH_DR = 19, RH_DV = 28, RH_DP = 31, RH_JRG = 34, RH_JVG = 43, RH_JVA = 52, RH_JPG = 61, RH_JPA = 70, RH_WORDS = 79 };
+// the temporaries of bias_deltas: db[6] = b - bias, th[3] = JRg*dbg, (dV, dP)[6], W, E, M, M2 [9 each], dR [9]
+enum { BD_DB = 0, BD_TH = 6, BD_DVP = 9, BD_W = 15, BD_E = 24, BD_M = 33, BD_M2 = 42, BD_DRU = 51, BD_WORDS = 61 };
+// getDeltaRotation / Velocity / Position (Imu.cpp:182-192) of the bias whose entry `lane` (< 6) is b, by one wave: H the record's head and
+// T the temporaries, both in the wave's LDS.  Leaves dR in T[BD_DRU ..), (dV, dP) in T[BD_DVP ..), b - bias in T[BD_DB ..); ends on a WSYNC
+__device__ __forceinline__ void bias_deltas(const float *H, float *T, int lane, float b)
+{
+    const int g = lane / 9, q = lane - 9 * g, i = q / 3, j = q - 3 * i;
+    if (lane < 6) T[BD_DB + lane] = sub(b, H[RH_BIAS + lane]);
+    WSYNC();
+    if (lane < 3) T[BD_TH + lane] = mv3(H + RH_JRG, T + BD_DB, lane);
+    else if (lane < 6) T[BD_DVP + lane - 3] = add(add(H[RH_DV + lane - 3], mv3(H + RH_JVG, T + BD_DB, lane - 3)), mv3(H + RH_JVA, T + BD_DB + 3, lane - 3));
+    else if (lane < 9) T[BD_DVP + lane - 3] = add(add(H[RH_DP + lane - 6], mv3(H + RH_JPG, T + BD_DB, lane - 6)), mv3(H + RH_JPA, T + BD_DB + 3, lane - 6));
+    WSYNC();
+    const float tx = T[BD_TH], ty = T[BD_TH + 1], tz = T[BD_TH + 2];
+    const So3 so = so3_scalars(tx, ty, tz);
+    if (g == 0) T[BD_W + q] = hat(tx, ty, tz, q);
+    WSYNC();
+    if (g == 0) T[BD_E + q] = exp_entry(so, T + BD_W, q);
+    WSYNC();
+    if (g == 0) T[BD_M + q] = m3(H + RH_DR, T + BD_E, i, j);
+    WSYNC();
+    if (g == 0) T[BD_M2 + q] = newton_entry(T + BD_M, i, j);
+    WSYNC();
+    if (g == 0) T[BD_DRU + q] = newton_entry(T + BD_M2, i, j);
+    WSYNC();
+}
+
+// T_wb = T_cw.inverse() * T_cb (Frame.cpp:57-63, KeyFrame.cpp:27-34) by the first twelve lanes of a wave: R[9], t[3] = T_cw, cb[12] = (Rcb, tcb)
+// and twc[3] (scratch) in the wave's LDS, filled and fenced by the caller; dst[0..12) receives (Rwb, twb)
+__device__ __forceinline__ void imu_pose_from_camera(const float *R, const float *t, const float *cb, float *twc, float *dst, int lane)
+{
+    const int i = lane / 3, j = lane - 3 * i;
+    if (lane < 3) twc[lane] = sum3(mul(-R[lane], t[0]), mul(-R[3 + lane], t[1]), mul(-R[6 + lane], t[2]));
+    WSYNC();
+    if (lane < 9) dst[lane] = m3t(R, cb, i, j);                                                    // Rcw^T * Rcb
+    else if (lane < 12) {
+        const int k = lane - 9;
+        dst[lane] = add(sum3(mul(R[k], cb[9]), mul(R[3 + k], cb[10]), mul(R[6 + k], cb[11])), twc[k]);   // Rcw^T * tcb + twc
+    }
 }
 
 } // namespace

@@ -151,6 +151,7 @@ def _mlib():
             "orbm_inertial_window_problem_device": (i32, [vp, C.POINTER(KfTable), vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32,
                                                           i32, i32, i32] + [vp] * 20),
             "orbm_inertial_window_velocity_prior_device": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+            "orbm_apply_scale_rotation_device": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp]),
             "orbm_update_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, i32, i32, i32, vp, vp, vp]),
             "orbm_erase_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, i32, vp, vp, vp, vp]),
             "orbm_fuse_targets_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp,
@@ -713,6 +714,19 @@ class ORBMatcher:
         _lib.check(self._L.orbm_inertial_window_velocity_prior_device(
             self._hd._h, p("priors"), n_priors, p("src"), n_src, p("recover_jobs"), p("prior_jobs"), p("result"), _lib.stream_arg(stream)))
 
+    # -- Map::applyScaleRotation on the device-resident map (Map.cpp:96-124) --
+    def ApplyScaleRotationDevice(self, calib, d, n_kf, n_src, n_priors, cap_points, be_first, min_scale=0.1, stream=None):
+        """orbm_apply_scale_rotation_device: calib an imu.Calib.  d: dict of torch device tensors -- in / out: pose_R f64 [n_kf,9], pose_t
+        f64 [n_kf,3], state f32 [n_src,15], priors (the orbi_prior array), points f32 [cap_points,3]; in: bad u8 [n_kf], kf_imu i32 [n_kf,3]
+        (state row, record, prior slot), valid u8 [cap_points], n_points i32 [1], summary f32 [10] (Rwg, scale: imu_init.recover_device's);
+        out: result i32 [8] ([0] key frames, [1] out of range, [2] duplicates, [3] refused, [4] points).  With be_first and a scale below
+        min_scale nothing but result is written.  Enqueues on `stream`; nothing is copied or synchronised."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_apply_scale_rotation_device(
+            self._hd._h, C.addressof(calib), n_kf, p("pose_R"), p("pose_t"), p("bad"), p("kf_imu"), p("state"), n_src, p("priors"), n_priors,
+            p("points"), p("valid"), p("n_points"), cap_points, p("summary"), int(bool(be_first)), float(np.float32(min_scale)), p("result"),
+            _lib.stream_arg(stream)))
+
     def SearchForInitializationDevice(self, d, n1, n2, grid_cols, grid_rows, window=100, list_cap=768, stream=None):
         """orbm_search_for_initialization_device on torch device tensors: d = dict(kps1, desc1, kps2 (frame 2's record as
         orbf_frame_post_device leaves it), desc2, cell_start, cell_items, pre (float32 [n1, 2], in / out), matches12 (int32 [n1], out),
@@ -791,3 +805,8 @@ def inertial_window_problem_device(matcher, *args, **kwargs):
 def inertial_window_velocity_prior_device(matcher, *args, **kwargs):
     """ORBMatcher.InertialWindowVelocityPriorDevice (orbm_inertial_window_velocity_prior_device)"""
     return matcher.InertialWindowVelocityPriorDevice(*args, **kwargs)
+
+
+def apply_scale_rotation_device(matcher, *args, **kwargs):
+    """ORBMatcher.ApplyScaleRotationDevice (orbm_apply_scale_rotation_device)"""
+    return matcher.ApplyScaleRotationDevice(*args, **kwargs)
