@@ -8,7 +8,9 @@
 //
 // The float part of an edge (the deltas of the bias vertices cast to float) is orbi_imu.hip's arithmetic, from the shared orbi_so3.h;
 // everything behind the cast is IEEE double, +, -, *, / in the header's orders without fused multiply-add, and the device's sin, cos,
-// atan2 and sqrt.
+// atan2 and sqrt.  What EdgeInertial has in common with the edges of the IMU initialisation (orbii.hip) -- the widening, the rotation
+// residual and its Jacobian factors, Omega*e with chi2, the quadratic form, the refused-edge rule -- is orbi_edge.h's; ev, ep, the
+// Jacobian's entries, the Huber weight and the walks are here.
 //
 // Shape: the graphs are tiny (two states for the tracker, a few tens for a local window), so every kernel is latency-bound and the
 // aim is few launches and short dependent chains, not throughput.  An inertial edge is ONE WAVE, four per workgroup (k_imu's shape):
@@ -26,6 +28,7 @@
 #include "../../include/orbx.h"
 #include "orb_host.h"
 #include "orb_math.h"
+#include "orbi_edge.h"
 #include "orbi_graph_device.h"
 #include "orbi_so3.h"
 #include "orbi_so3d.h"
@@ -98,10 +101,7 @@ __global__ __launch_bounds__(64) void k_fac_prior_info(orbi_prior *__restrict__ 
         const int slot = jobs[3 * job], rec = jobs[3 * job + 1], st = jobs[3 * job + 2];
         int code = ORBI_R_DONE;
         if (slot < 0 || slot >= n_priors || rec < 0 || rec >= cap || st < -1 || st >= n_src || (st >= 0 && !src)) code = ORBI_R_RANGE;
-        else {
-            for (int k = 0; k < job; ++k)
-                if (jobs[3 * k] == slot) code = ORBI_R_DUPLICATE;
-        }
+        else if (job_named_before(jobs, 3, job, 0, slot)) code = ORBI_R_DUPLICATE;
         if (code == ORBI_R_DONE) {
             const float *C = bank[rec].C;
             double gi[9], ai[9];
@@ -159,10 +159,7 @@ __global__ __launch_bounds__(64) void k_fac_init(const orbi_graph g, const orbi_
         const int st = jobs[3 * job], from = jobs[3 * job + 1], rec = jobs[3 * job + 2];
         int code = ORBI_R_DONE;
         if (st < 0 || st >= g.n_states || from < 0 || from >= n_src || rec < -1 || rec >= cap) code = ORBI_R_RANGE;
-        else {
-            for (int k = 0; k < job; ++k)
-                if (jobs[3 * k] == st) code = ORBI_R_DUPLICATE;
-        }
+        else if (job_named_before(jobs, 3, job, 0, st)) code = ORBI_R_DUPLICATE;
         if (code == ORBI_R_DONE) {
             const float *f = src + 15 * (size_t)from;
             for (int k = 0; k < 9; ++k) g.Rwb[9 * (size_t)st + k] = (double)f[k];
@@ -228,10 +225,7 @@ __global__ __launch_bounds__(64) void k_fac_recover(const orbi_graph g, const or
         const int st = jobs[3 * job], to = jobs[3 * job + 1], flags = jobs[3 * job + 2];
         int code = ORBI_R_DONE;
         if (st < 0 || st >= g.n_states || to < 0 || to >= n_dst) code = ORBI_R_RANGE;
-        else {
-            for (int k = 0; k < job; ++k)
-                if (jobs[3 * k + 1] == to) code = ORBI_R_DUPLICATE;
-        }
+        else if (job_named_before(jobs, 3, job, 1, to)) code = ORBI_R_DUPLICATE;
         if (code != ORBI_R_DONE) {
             for (int k = 0; k < 6; ++k) bias[6 * (size_t)job + k] = 0.f;
         } else {
@@ -370,19 +364,11 @@ enum { W_HII = 0, W_HJJ = 225, W_B = 450, W_WALK = 480, W_STATUS = 486, W_RHO1 =
 static_assert(W_RHO1 + 1 == ORBI_EDGE_WORK, "orbi_factors.h states the workspace of an edge");
 enum { ST_OK = 0, ST_RANGE = 1, ST_REFUSED = 3 };   // == ORBI_R_DONE, ORBI_R_RANGE, ORBI_R_REFUSED
 
-// a wave's LDS slice: floats (the record's first 79 floats as orbi_record lays them out, then the float temporaries) and doubles
-enum {
-    F_BIAS = RH_BIAS, F_DT = RH_DT, F_JRG = RH_JRG, F_JPA = RH_JPA, F_REC = RH_WORDS,
-    X_DB = F_REC + BD_DB, X_DVP = F_REC + BD_DVP, X_DRU = F_REC + BD_DRU, X_WORDS = 140   // the temporaries of bias_deltas (orbi_so3.h)
-};
-enum {
-    D_R1 = 0, D_R2 = 9, D_T1 = 18, D_T2 = 21, D_V1 = 24, D_V2 = 27, D_B1 = 30, D_B2 = 36,   // (bg, ba) of state i, of state j
-    D_DR = 42, D_JRG = 51, D_JVG = 60, D_JVA = 69, D_JPG = 78, D_JPA = 87, D_DVP = 96, D_DBG = 102, D_TH = 105,
-    D_A1 = 108, D_RR = 117, D_ER = 126, D_JR = 135, D_INVJ = 144, D_T3 = 153, D_T4 = 162, D_T5 = 171,
-    D_E = 180, D_A = 189, D_C = 192, D_WE = 195, D_J = 204, D_INFO = 474, D_WJ = 555, D_WORDS = 825
-};
-static_assert(offsetof(orbi_record, JPa) == 4 * F_JPA && offsetof(orbi_record, C) == 4 * F_REC && offsetof(orbi_record, delta_t) == 4 * F_DT,
-              "the LDS image is the head of the record");
+// a wave's LDS slice: floats (the record's head, then the temporaries of bias_deltas) and doubles (orbi_edge.h's shared fields, then
+// (bg, ba) of state i and of state j, Rb1w*R2, (-invJr)*R2^T, Rb1w*(v2 - v1 - g*dt), Rb1w*(t2 - t1 - v1*dt - 0.5*g*dt*dt), J and W*J)
+enum { X_T = RH_WORDS, X_WORDS = RH_WORDS + BD_WORDS };
+enum { D_B1 = D_SHARED, D_B2 = D_B1 + 6, D_RR = D_B2 + 6, D_T3 = D_RR + 9, D_A = D_T3 + 9, D_C = D_A + 3, D_J = D_C + 3, D_WJ = D_J + 270, D_WORDS = D_WJ + 270 };
+static_assert(X_WORDS == 140 && D_WORDS == 825, "include/orbi.h states the LDS of k_fac_edge");
 
 // entry (r, c) of the raw 9 x 30 Jacobian (G2oTypes.cpp:413-444), columns [dphi1, dt1, dv1, dbg, dba | dphi2, dt2, dv2, -, -]
 __device__ __forceinline__ double jac_entry(const double *S, double dt, int r, int c)
@@ -425,8 +411,8 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
     const int rec = __builtin_amdgcn_readfirstlane(a.edges[e].rec), flags = __builtin_amdgcn_readfirstlane(a.edges[e].flags);
     const int g = lane / 9, q = lane - 9 * g, i = q / 3, j = q - 3 * i;
     int status = ST_OK;
-    if (si < 0 || si >= a.g.n_states || sj < 0 || sj >= a.g.n_states || si == sj || rec < 0 || rec >= a.cap) status = ST_RANGE;
-    else if (a.info[81 * (size_t)e] == 0.0) status = ST_REFUSED;   // what orbi_edge_information_device leaves for a refused edge
+    if (!edge_valid(si, sj, rec, a.g.n_states, a.cap)) status = ST_RANGE;
+    else if (edge_refused(a.info, e)) status = ST_REFUSED;
     if (status != ST_OK) {
         if (lane < 9) a.err[9 * (size_t)e + lane] = 0.0;
         if (lane < 3) a.chi2[3 * (size_t)e + lane] = 0.0;
@@ -440,8 +426,7 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
         return;
     }
     // ---- load: the head of the record, the vertices of both states, the information
-    const float *recf = (const float *)(a.bank + rec);
-    for (int k = lane; k < F_REC; k += 64) F[k] = recf[k];
+    edge_load(a.bank, rec, a.info, e, F, S, lane);
     if (lane < 9) S[D_R1 + lane] = a.g.Rwb[9 * (size_t)si + lane];
     else if (lane < 18) S[D_R2 + lane - 9] = a.g.Rwb[9 * (size_t)sj + lane - 9];
     else if (lane < 21) S[D_T1 + lane - 18] = a.g.twb[3 * (size_t)si + lane - 18];
@@ -452,22 +437,15 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
     else if (lane < 36) S[D_B1 + lane - 30] = a.g.ba[3 * (size_t)si + lane - 33];
     else if (lane < 39) S[D_B2 + lane - 36] = a.g.bg[3 * (size_t)sj + lane - 36];
     else if (lane < 42) S[D_B2 + lane - 36] = a.g.ba[3 * (size_t)sj + lane - 39];
-    for (int x = lane; x < 81; x += 64) S[D_INFO + x] = a.info[81 * (size_t)e + x];
     const int fix_i = a.g.fixed[si], fix_j = a.g.fixed[sj];
     WSYNC();
     // ---- the float part: the bias vertices cast to float, getDeltaRotation / Velocity / Position (Imu.cpp:182-192)
-    bias_deltas(F, F + F_REC, lane, lane < 6 ? (float)S[D_B1 + lane] : 0.f);
-    if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = lane < 9 ? F[X_DRU + lane] : F[X_DVP + lane - 9];
-    // ---- everything behind the cast to double
-    const double dt = (double)F[F_DT], G = (double)a.gravity;
-    if (g == 0) S[D_DR + q] = (double)F[X_DRU + q];
-    else if (g < 6) S[D_JRG + 9 * (g - 1) + q] = (double)F[F_JRG + 9 * (g - 1) + q];
-    else if (g == 6 && q < 6) S[D_DVP + q] = (double)F[X_DVP + q];
-    else if (g == 6) S[D_DBG + q - 6] = (double)F[X_DB + q - 6];
-    WSYNC();
-    if (g == 0) S[D_A1 + q] = dm3tt(S + D_DR, S + D_R1, i, j);                    // dR^T * Rb1w
-    else if (g == 1) S[D_RR + q] = dm3t(S + D_R1, S + D_R2, i, j);                // Rb1w * R2
-    else if (g == 2 && q < 3) {                                                   // Rb1w*(v2 - v1 - g*dt) and ev
+    bias_deltas(F, F + X_T, lane, lane < 6 ? (float)S[D_B1 + lane] : 0.f);
+    if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = lane < 9 ? F[X_T + BD_DRU + lane] : F[X_T + BD_DVP + lane - 9];
+    // ---- everything behind the cast to double: this edge's lines on lane groups 2 .. 4, the rotation residual beside them
+    const double dt = (double)F[RH_DT], G = (double)a.gravity;
+    edge_widen(F, F + X_T, S, lane);
+    if (g == 2 && q < 3) {                                                        // Rb1w*(v2 - v1 - g*dt) and ev
         double d[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) d[k] = (S[D_V2 + k] - S[D_V1 + k]) - dmul(k == 2 ? -G : 0.0, dt);
@@ -479,35 +457,11 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
         for (int k = 0; k < 3; ++k) d[k] = ((S[D_T2 + k] - S[D_T1 + k]) - dmul(S[D_V1 + k], dt)) - dmul(dmul(dmul(0.5, k == 2 ? -G : 0.0), dt), dt);
         const double v = dmv3t(S + D_R1, d[0], d[1], d[2], q);
         S[D_C + q] = v, S[D_E + 6 + q] = v - S[D_DVP + 3 + q];
-    } else if (g == 4 && q < 3) S[D_TH + q] = dsum3(dmul(S[D_JRG + 3 * q], S[D_DBG]), dmul(S[D_JRG + 3 * q + 1], S[D_DBG + 1]), dmul(S[D_JRG + 3 * q + 2], S[D_DBG + 2]));
-    WSYNC();
-    if (g == 0) S[D_ER + q] = dm3(S + D_A1, S + D_R2, i, j);                      // eR
-    else if (g == 1) {                                                            // RightJacobianSO3(JRg * delta_bg)
-        const double v = dright_jacobian(S[D_TH], S[D_TH + 1], S[D_TH + 2], q);
-        S[D_JR + q] = v;
-    }
-    WSYNC();
-    {   // LogSO3(eR) and InverseRightJacobianSO3(er), the scalars in every lane
-        double er0, er1, er2;
-        dlog_so3(S + D_ER, er0, er1, er2);
-        if (g == 0) {
-            S[D_INVJ + q] = dinverse_right_jacobian(er0, er1, er2, q);
-        } else if (g == 1 && q < 3) S[D_E + q] = q == 0 ? er0 : q == 1 ? er1 : er2;
-    }
-    WSYNC();
-    if (g == 0) S[D_T3 + q] = dm3nt(S + D_INVJ, S + D_R2, i, j);                  // (-invJr) * R2^T
-    else if (g == 1) S[D_T4 + q] = dm3nt(S + D_INVJ, S + D_ER, i, j);             // (-invJr) * eR^T
-    else if (g == 2) {                                                            // Omega * e
-        double s = 0.0;
-        for (int k = 0; k < 9; ++k) s = s + dmul(S[D_INFO + 9 * q + k], S[D_E + k]);
-        S[D_WE + q] = s;
-    }
-    WSYNC();
-    if (g == 0) S[D_T5 + q] = dm3(S + D_T4, S + D_JR, i, j);
-    WSYNC();
+    } else if (g == 4) S[D_RR + q] = dm3t(S + D_R1, S + D_R2, i, j);              // Rb1w * R2
+    edge_rotation(S, lane);
+    if (g == 2) S[D_T3 + q] = dm3nt(S + D_INVJ, S + D_R2, i, j);                  // (-invJr) * R2^T
     // ---- chi2, the Huber kernel (g2o's RobustKernelHuber), the walks
-    double chi = 0.0;
-    for (int k = 0; k < 9; ++k) chi = chi + dmul(S[D_E + k], S[D_WE + k]);
+    const double chi = edge_chi2(S, lane);
     double rho1 = 1.0;
     if (a.delta > 0.0 && chi > dmul(a.delta, a.delta)) rho1 = a.delta / sqrt(chi);
     double we[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, wchi[2] = {0.0, 0.0};
@@ -538,34 +492,14 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
         }
     }
     WSYNC();
-    // W*J with W = rho1 * Omega
-#pragma unroll
-    for (int h = 0; h < 5; ++h) {
-        const int x = lane + 64 * h;
-        if (x < 270) {
-            const int r = x / 30, c = x - 30 * r;
-            double s = 0.0;
-            for (int k = 0; k < 9; ++k) s = s + dmul(S[D_INFO + 9 * r + k], S[D_J + 30 * k + c]);
-            S[D_WJ + x] = dmul(rho1, s);
-        }
-    }
-    WSYNC();
-    // J^T*(W*J): H_ii and H_jj to the workspace, H_ij (with the walks' -W) to d_H_off; b = -J^T*(W*e)
-    for (int x = lane; x < 675; x += 64) {
-        const int blk = x / 225, y = x - 225 * blk, r = y / 15, c = y - 15 * r;
-        const int ca = (blk == 1 ? 15 : 0) + r, cb = (blk == 0 ? 0 : 15) + c;
-        double s = 0.0;
-        for (int k = 0; k < 9; ++k) s = s + dmul(S[D_J + 30 * k + ca], S[D_WJ + 30 * k + cb]);
-        if (blk == 2) {
-            if ((flags & ORBI_EDGE_WALKS) && r >= 9 && c >= 9 && r / 3 == c / 3 && !dof_fixed(fix_i, r) && !dof_fixed(fix_j, c))
-                s = s - a.walk_info[18 * (size_t)e + 9 * (r / 3 - 3) + 3 * (r % 3) + c % 3];
-            a.H_off[225 * (size_t)e + y] = s;
-        } else work[225 * blk + y] = s;
-    }
-    if (lane < 30) {
-        double s = 0.0;
-        for (int k = 0; k < 9; ++k) s = s + dmul(S[D_J + 30 * k + lane], dmul(rho1, S[D_WE + k]));
-        work[W_B + lane] = -s;
+    // W = rho1 * Omega: H_ii and H_jj, b_i and b_j to the workspace; H_ij, with the walks' -W, to d_H_off
+    edge_quadratic_form<30>(S, S + D_J, S + D_WJ, rho1, work + W_HII, work + W_B, lane);
+    for (int y = lane; y < 225; y += 64) {
+        const int r = y / 15, c = y - 15 * r;
+        double s = edge_jtwj<30>(S + D_J, S + D_WJ, r, 15 + c);
+        if ((flags & ORBI_EDGE_WALKS) && r >= 9 && c >= 9 && r / 3 == c / 3 && !dof_fixed(fix_i, r) && !dof_fixed(fix_j, c))
+            s = s - a.walk_info[18 * (size_t)e + 9 * (r / 3 - 3) + 3 * (r % 3) + c % 3];
+        a.H_off[225 * (size_t)e + y] = s;
     }
 }
 

@@ -1,5 +1,5 @@
 // The layer the kernels on the inertial graph share (the inertial factors, the visual edges, the marginalised window): the ordered three-term
-// sum, the fixed-dof rule, the validity of an orbi_edge, EdgeMono's pose path on a VertexPose -- the pose derived from (R_wb, t_wb) and
+// sum, the fixed-dof rule, the validity of an orbi_edge, the duplicate scan over a job list, EdgeMono's pose path on a VertexPose -- the pose derived from (R_wb, t_wb) and
 // orbi_calib, the pose Jacobian, the Huber kernel, the quadratic form and its scatter into a state's blocks -- and what the host side of
 // the two *_linearize_device entry points has in common.  Every operation order here is one the public headers fix and the numpy models
 // of tests/ hold to the bit: a correction is made here, once.  Internal.
@@ -25,6 +25,15 @@ __device__ __forceinline__ bool dof_fixed(int fixed, int dof) { return (fixed >>
 __device__ __forceinline__ bool edge_valid(int i, int j, int rec, int n, int cap)
 {
     return !(i < 0 || i >= n || j < 0 || j >= n || i == j || rec < 0 || rec >= cap);
+}
+// whether one of the jobs [0, job) of a list of `stride` ints names `value` in `field` (or `value2` in `field2`, where that is given),
+// dropped or not: the later job is the duplicate
+__device__ __forceinline__ bool job_named_before(const int32_t *jobs, int stride, int job, int field, int value, int field2 = -1, int value2 = 0)
+{
+    bool hit = false;
+    for (int k = 0; k < job; ++k)
+        if (jobs[stride * k + field] == value || (field2 >= 0 && jobs[stride * k + field2] == value2)) hit = true;
+    return hit;
 }
 
 // ---- the pose an EdgeMono hangs on, entry by entry: a caller spreads the entries over threads or unrolls them ---------------------------

@@ -8,7 +8,9 @@
 //
 // The float part of an edge is orbi_imu.hip's arithmetic from the shared orbi_so3.h (bias_deltas, the call k_fac_edge makes); the double
 // SO(3) functions are orbi_so3d.h's, shared with orbi_factors.hip.  Everything behind the cast is IEEE double, +, -, *, / in the header's
-// orders without fused multiply-add.
+// orders without fused multiply-add.  What EdgeInertialGS / EdgeInertialG have in common with EdgeInertial (k_fac_edge) -- the widening,
+// the rotation residual and its Jacobian factor, Omega*e with chi2, the quadratic form, the refused-edge rule -- is orbi_edge.h's; ev,
+// ep (scale, gravity direction, Oc / Pcb) and the Jacobian's entries are here.
 //
 // Shape: at most 157 key frames and 480 unknowns, so every kernel is latency-bound and the aim is few launches.  An edge is ONE WAVE, four
 // per workgroup (k_fac_edge's shape): its constants, the 3x3 temporaries, the 9x15 Jacobian, the 9x9 information and their product live
@@ -25,6 +27,8 @@
 #include "../../include/orbx.h"
 #include "orb_host.h"
 #include "orb_math.h"
+#include "orbi_edge.h"
+#include "orbi_graph_device.h"
 #include "orbi_so3.h"
 #include "orbi_so3d.h"
 
@@ -32,9 +36,6 @@
 
 static_assert(sizeof(orbii_graph) == 64 && sizeof(orbii_bias) == 24 && sizeof(orbi_edge) == 16 && sizeof(orbi_prior) == 144, "orbii.h fixes these layouts");
 static_assert(ORBII_N(ORBII_MAX_KF) == 480 && ORBII_N(2) == 15 && ORBII_N(3) == 30 && ORBII_N(17) == 60, "N = 15 * ceil((9 + 3 n_kf) / 15)");
-static_assert(offsetof(orbi_record, JPa) == 4 * RH_JPA && offsetof(orbi_record, C) == 4 * RH_WORDS && offsetof(orbi_record, delta_t) == 4 * RH_DT &&
-                  offsetof(orbi_record, delta_bias) == 4 * RH_DELTA,
-              "the LDS image is the head of the record");
 
 namespace {
 
@@ -56,10 +57,7 @@ __global__ __launch_bounds__(64) void k_ii_prior(const double *__restrict__ pose
         const int pr = jobs[II_JOB * k], sr = jobs[II_JOB * k + 1], rec = jobs[II_JOB * k + 2], sl = jobs[II_JOB * k + 3];
         int code = ORBI_R_DONE;
         if (pr < 0 || pr >= n_pose || sr < 0 || sr >= n_src || sl < 0 || sl >= n_priors || rec < (k == n - 1 ? -1 : 0) || rec >= cap) code = ORBI_R_RANGE;
-        else {
-            for (int m = 0; m < k; ++m)
-                if (jobs[II_JOB * m + 1] == sr || jobs[II_JOB * m + 3] == sl) code = ORBI_R_DUPLICATE;
-        }
+        else if (job_named_before(jobs, II_JOB, k, 1, sr, 3, sl)) code = ORBI_R_DUPLICATE;
         s_code[k] = code;
         float O[3] = {0.f, 0.f, 0.f}, RdV[3] = {0.f, 0.f, 0.f}, dt = 0.f;
         if (code == ORBI_R_DONE) {
@@ -208,10 +206,7 @@ __global__ __launch_bounds__(II_T) void k_ii_recover(const orbii_graph g, const 
         const int sr = jobs[II_JOB * k + 1], sl = jobs[II_JOB * k + 3];
         code = ORBI_R_DONE;
         if (sr < 0 || sr >= n_src || sl < 0 || sl >= n_priors) code = ORBI_R_RANGE;
-        else {
-            for (int m = 0; m < k; ++m)
-                if (jobs[II_JOB * m + 1] == sr || jobs[II_JOB * m + 3] == sl) code = ORBI_R_DUPLICATE;
-        }
+        else if (job_named_before(jobs, II_JOB, k, 1, sr, 3, sl)) code = ORBI_R_DUPLICATE;
         if (code == ORBI_R_DONE) {
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
@@ -252,17 +247,18 @@ __device__ __forceinline__ int edge_status(const LinArgs &a, int e)
 {
     const int rec = a.edges[e].rec;
     if (rec < 0 || rec >= a.cap) return ORBI_R_RANGE;
-    return a.info[81 * (size_t)e] == 0.0 ? ORBI_R_REFUSED : ORBI_R_DONE;
+    return edge_refused(a.info, e) ? ORBI_R_REFUSED : ORBI_R_DONE;
 }
 
-// a wave's LDS slice: floats (the record's head, then the temporaries of bias_deltas) and doubles
+// a wave's LDS slice: floats (the record's head, then the temporaries of bias_deltas) and doubles (orbi_edge.h's shared fields, then the
+// constants Oc and Pcb of both key frames, the shared vertices, g = Rwg*gI, JG = Rwg*gm, v2 - v1, (Oc2 - Oc1) - v1*dt, (-Rb1w)*JG,
+// (c*Rb1w)*JG, J and Omega*J)
 enum { X_T = RH_WORDS, X_WORDS = RH_WORDS + BD_WORDS };
 enum {
-    D_R1 = 0, D_R2 = 9, D_T1 = 18, D_T2 = 21, D_O1 = 24, D_O2 = 27, D_P1 = 30, D_P2 = 33, D_V1 = 36, D_V2 = 39, D_SH = 42,
-    D_DR = 58, D_JRG = 67, D_JVG = 76, D_JVA = 85, D_JPG = 94, D_JPA = 103, D_DVP = 112, D_DBG = 118, D_TH = 121,
-    D_A1 = 124, D_ER = 133, D_JR = 142, D_INVJ = 151, D_T4 = 160, D_T5 = 169, D_E = 178, D_WE = 187, D_G = 196, D_JG = 199,
-    D_DV = 205, D_DO = 208, D_RJG = 211, D_CRJG = 217, D_J = 223, D_INFO = 358, D_WJ = 439, D_WORDS = 574
+    D_O1 = D_SHARED, D_O2 = D_O1 + 3, D_P1 = D_O2 + 3, D_P2 = D_P1 + 3, D_SH = D_P2 + 3, D_G = D_SH + SH_WORDS, D_JG = D_G + 3, D_DV = D_JG + 6,
+    D_DO = D_DV + 3, D_RJG = D_DO + 3, D_CRJG = D_RJG + 6, D_J = D_CRJG + 6, D_WJ = D_J + 135, D_WORDS = D_WJ + 135
 };
+static_assert(X_WORDS == 140 && D_WORDS == 574, "include/orbii.h states the LDS of k_ii_edge");
 
 // entry (r, c) of the 9 x 15 Jacobian in the local order [v1, bg, ba, v2, gravity, scale] (G2oTypes.cpp:134-162, :222-245)
 __device__ __forceinline__ double jac_entry(const double *S, int kind, double dt, int r, int c)
@@ -303,7 +299,7 @@ __global__ __launch_bounds__(II_T) void k_ii_edge(const LinArgs a)
     double *S = s_d[wave];
     float *F = s_f[wave];
     double *work = a.work + (size_t)ORBII_EDGE_WORK * e;
-    const int g = lane / 9, q = lane - 9 * g, i = q / 3, j = q - 3 * i;
+    const int g = lane / 9, q = lane - 9 * g;
     const int status = __builtin_amdgcn_readfirstlane(edge_status(a, e));
     if (status != ORBI_R_DONE) {
         if (lane < 9) a.err[9 * (size_t)e + lane] = 0.0;
@@ -313,27 +309,21 @@ __global__ __launch_bounds__(II_T) void k_ii_edge(const LinArgs a)
     }
     const int rec = __builtin_amdgcn_readfirstlane(a.edges[e].rec), gs = a.kind == ORBII_KIND_GS;
     // ---- load: the head of the record, the constants of both key frames, the vertices, the information
-    const float *recf = (const float *)(a.bank + rec);
-    for (int k = lane; k < RH_WORDS; k += 64) F[k] = recf[k];
+    edge_load(a.bank, rec, a.info, e, F, S, lane);
     if (lane < 18) S[D_R1 + lane] = a.g.Rwb[9 * (size_t)e + lane];                  // R1, R2 are adjacent rows
     else if (lane < 24) S[D_T1 + lane - 18] = a.g.twb[3 * (size_t)e + lane - 18];
     else if (lane < 30) S[D_O1 + lane - 24] = a.g.Oc[3 * (size_t)e + lane - 24];
     else if (lane < 36) S[D_P1 + lane - 30] = a.g.Pcb[3 * (size_t)e + lane - 30];
     else if (lane < 42) S[D_V1 + lane - 36] = a.g.v[3 * (size_t)e + lane - 36];
     else if (lane < 58) S[D_SH + lane - 42] = a.g.shared[lane - 42];
-    for (int x = lane; x < 81; x += 64) S[D_INFO + x] = a.info[81 * (size_t)e + x];
     WSYNC();
     // ---- the float part: the bias vertices cast to float, getDeltaRotation / Velocity / Position (Imu.cpp:182-192)
     bias_deltas(F, F + X_T, lane, lane < 6 ? (float)S[D_SH + lane] : 0.f);
     if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = lane < 9 ? F[X_T + BD_DRU + lane] : F[X_T + BD_DVP + lane - 9];
-    // ---- everything behind the cast to double
+    // ---- everything behind the cast to double: this edge's lines on lane 63 and on lane groups 2 .. 5, the rotation residual beside them
     const double dt = (double)F[RH_DT], G = (double)a.gravity, s = S[D_SH + SH_SCALE];
     const double *Rwg = S + D_SH + SH_RWG;
-    if (g == 0) S[D_DR + q] = (double)F[X_T + BD_DRU + q];
-    else if (g < 6) S[D_JRG + 9 * (g - 1) + q] = (double)F[RH_JRG + 9 * (g - 1) + q];
-    else if (g == 6 && q < 6) S[D_DVP + q] = (double)F[X_T + BD_DVP + q];
-    else if (g == 6) S[D_DBG + q - 6] = (double)F[X_T + BD_DB + q - 6];
-    else if (lane == 63) {                                                        // g = Rwg*gI and JG = Rwg*gm, their zero terms dropped
+    if (lane == 63) {                                                             // g = Rwg*gI and JG = Rwg*gm, their zero terms dropped
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             S[D_G + k] = dmul(Rwg[3 * k + 2], -G);
@@ -341,10 +331,8 @@ __global__ __launch_bounds__(II_T) void k_ii_edge(const LinArgs a)
             S[D_JG + 2 * k + 1] = dmul(Rwg[3 * k], -G);
         }
     }
-    WSYNC();
-    if (g == 0) S[D_A1 + q] = dm3tt(S + D_DR, S + D_R1, i, j);                    // dR^T * Rb1w
-    else if (g == 1 && q < 3) S[D_TH + q] = dsum3(dmul(S[D_JRG + 3 * q], S[D_DBG]), dmul(S[D_JRG + 3 * q + 1], S[D_DBG + 1]), dmul(S[D_JRG + 3 * q + 2], S[D_DBG + 2]));
-    else if (g == 2 && q < 3) {                                                   // ev
+    edge_widen(F, F + X_T, S, lane);
+    if (g == 2 && q < 3) {                                                        // ev
         double d[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -370,28 +358,8 @@ __global__ __launch_bounds__(II_T) void k_ii_edge(const LinArgs a)
         S[D_RJG + q] = dsum3(dmul(-S[D_R1 + r], S[D_JG + c]), dmul(-S[D_R1 + 3 + r], S[D_JG + 2 + c]), dmul(-S[D_R1 + 6 + r], S[D_JG + 4 + c]));
         S[D_CRJG + q] = dsum3(dmul(dmul(cc, S[D_R1 + r]), S[D_JG + c]), dmul(dmul(cc, S[D_R1 + 3 + r]), S[D_JG + 2 + c]), dmul(dmul(cc, S[D_R1 + 6 + r]), S[D_JG + 4 + c]));
     }
-    WSYNC();
-    if (g == 0) S[D_ER + q] = dm3(S + D_A1, S + D_R2, i, j);                      // eR
-    else if (g == 1) S[D_JR + q] = dright_jacobian(S[D_TH], S[D_TH + 1], S[D_TH + 2], q);
-    WSYNC();
-    {   // LogSO3(eR) and InverseRightJacobianSO3(er), the scalars in every lane
-        double er0, er1, er2;
-        dlog_so3(S + D_ER, er0, er1, er2);
-        if (g == 0) S[D_INVJ + q] = dinverse_right_jacobian(er0, er1, er2, q);
-        else if (g == 1 && q < 3) S[D_E + q] = q == 0 ? er0 : q == 1 ? er1 : er2;
-    }
-    WSYNC();
-    if (g == 0) S[D_T4 + q] = dm3nt(S + D_INVJ, S + D_ER, i, j);                  // (-invJr) * eR^T
-    else if (g == 1) {                                                            // Omega * e
-        double w = 0.0;
-        for (int k = 0; k < 9; ++k) w = w + dmul(S[D_INFO + 9 * q + k], S[D_E + k]);
-        S[D_WE + q] = w;
-    }
-    WSYNC();
-    if (g == 0) S[D_T5 + q] = dm3(S + D_T4, S + D_JR, i, j);
-    WSYNC();
-    double chi = 0.0;
-    for (int k = 0; k < 9; ++k) chi = chi + dmul(S[D_E + k], S[D_WE + k]);
+    edge_rotation(S, lane);
+    const double chi = edge_chi2(S, lane);
     if (lane < 9) a.err[9 * (size_t)e + lane] = S[D_E + lane];
     if (lane == 0) a.chi2[e] = chi;
     if (a.mode != 0) return;
@@ -402,28 +370,7 @@ __global__ __launch_bounds__(II_T) void k_ii_edge(const LinArgs a)
         if (x < 135) S[D_J + x] = jac_entry(S, a.kind, dt, x / 15, x % 15);
     }
     WSYNC();
-#pragma unroll
-    for (int h = 0; h < 3; ++h) {
-        const int x = lane + 64 * h;
-        if (x < 135) {
-            const int r = x / 15, c = x - 15 * r;
-            double w = 0.0;
-            for (int k = 0; k < 9; ++k) w = w + dmul(S[D_INFO + 9 * r + k], S[D_J + 15 * k + c]);
-            S[D_WJ + x] = w;
-        }
-    }
-    WSYNC();
-    for (int x = lane; x < 225; x += 64) {
-        const int r = x / 15, c = x - 15 * r;
-        double w = 0.0;
-        for (int k = 0; k < 9; ++k) w = w + dmul(S[D_J + 15 * k + r], S[D_WJ + 15 * k + c]);
-        work[W_M + x] = w;
-    }
-    if (lane < 15) {
-        double w = 0.0;
-        for (int k = 0; k < 9; ++k) w = w + dmul(S[D_J + 15 * k + lane], S[D_WE + k]);
-        work[W_R + lane] = -w;
-    }
+    edge_quadratic_form<15>(S, S + D_J, S + D_WJ, 1.0, work + W_M, work + W_R, lane);
 }
 
 // the local index of global dof d on edge e, which touches it

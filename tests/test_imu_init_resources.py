@@ -37,19 +37,29 @@ def test_the_kernels_use_no_scratch_memory_and_the_lds_the_headers_state():
 
 
 def test_the_so3_code_is_written_once():
-    """orbii.hip and orbi_factors.hip take the double SO(3) functions from csrc/orbi_so3d.h and the float part of an edge (bias_deltas) from
-    csrc/orbi_so3.h; orbm_rescale.hip and orbi_imu.hip take T_wb = T_cw.inverse() * T_cb from there.  None defines them itself."""
+    """orbii.hip and orbi_factors.hip take what their edges share behind the cast to double (the prologue, the widening, the rotation
+    residual, Omega*e with chi2, the quadratic form) from csrc/orbi_edge.h, which takes LogSO3 and the two Jacobians from csrc/orbi_so3d.h;
+    both take ExpSO3 from there, the float part of an edge (bias_deltas) from csrc/orbi_so3.h and the duplicate scan over a job list from
+    csrc/orbi_graph_device.h; orbm_rescale.hip and orbi_imu.hip take T_wb = T_cw.inverse() * T_cb from orbi_so3.h.  None defines them
+    itself, and no scan is written out."""
     d, f = open(os.path.join(CSRC, "orbi_so3d.h")).read(), open(os.path.join(CSRC, "orbi_so3.h")).read()
+    e, g = open(os.path.join(CSRC, "orbi_edge.h")).read(), open(os.path.join(CSRC, "orbi_graph_device.h")).read()
     for fn in ("dlog_so3", "dright_jacobian", "dinverse_right_jacobian", "dexp_so3", "dnormalize", "dm3", "dcof"):
         assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, d, re.M)) == 1, fn
     for fn in ("bias_deltas", "imu_pose_from_camera"):
         assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, f, re.M)) == 1, fn
-    for src, header, fns in (("orbii.hip", "orbi_so3d.h", ("dlog_so3", "dright_jacobian", "dinverse_right_jacobian", "dexp_so3", "bias_deltas")),
-                             ("orbi_factors.hip", "orbi_so3d.h", ("dlog_so3", "dright_jacobian", "dinverse_right_jacobian", "dexp_so3", "bias_deltas")),
+    edge_fns = ("edge_refused", "edge_load", "edge_widen", "edge_rotation", "edge_chi2", "edge_jtwj", "edge_quadratic_form")
+    for fn in edge_fns:
+        assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, e, re.M)) == 1, fn
+    assert len(re.findall(r"^__device__ __forceinline__ \w+ job_named_before\(", g, re.M)) == 1
+    for src, header, fns in (("orbi_edge.h", "orbi_so3d.h", ("dlog_so3", "dright_jacobian", "dinverse_right_jacobian")),
+                             ("orbii.hip", "orbi_so3d.h", ("dexp_so3", "bias_deltas")), ("orbi_factors.hip", "orbi_so3d.h", ("dexp_so3", "bias_deltas")),
+                             ("orbii.hip", "orbi_edge.h", [fn for fn in edge_fns if fn != "edge_jtwj"]), ("orbi_factors.hip", "orbi_edge.h", edge_fns),
+                             ("orbii.hip", "orbi_graph_device.h", ("job_named_before",)), ("orbi_factors.hip", "orbi_graph_device.h", ("job_named_before",)),
                              ("orbm_rescale.hip", "orbi_so3.h", ("imu_pose_from_camera",)), ("orbi_imu.hip", "orbi_so3.h", ("imu_pose_from_camera",))):
         text = open(os.path.join(CSRC, src)).read()
         assert '#include "%s"' % header in text, src
         for fn in fns:
-            assert re.search(r"\b%s\(" % fn, text), (src, fn)
+            assert re.search(r"\b%s(?:<\d+>)?\(" % fn, text), (src, fn)
             assert not re.search(r"^\s*(?:__device__ |static |inline )[\w ]*\b%s\(" % fn, text, re.M), (src, fn)
     assert "orbii.hip" in open(os.path.join(CSRC, "Makefile")).read()
