@@ -10,7 +10,8 @@
 // everything behind the cast is IEEE double, +, -, *, / in the header's orders without fused multiply-add, and the device's sin, cos,
 // atan2 and sqrt.  What EdgeInertial has in common with the edges of the IMU initialisation (orbii.hip) -- the widening, the rotation
 // residual and its Jacobian factors, Omega*e with chi2, the quadratic form, the refused-edge rule -- is orbi_edge.h's; ev, ep, the
-// Jacobian's entries, the Huber weight and the walks are here.
+// Jacobian's entries and a job of the recovery, which fullInertialOptimize's shared-bias edge (orbfi.hip) takes as they are, are
+// orbi_factors_device.h's; the Huber weight and the walks are here.
 //
 // Shape: the graphs are tiny (two states for the tracker, a few tens for a local window), so every kernel is latency-bound and the
 // aim is few launches and short dependent chains, not throughput.  An inertial edge is ONE WAVE, four per workgroup (k_imu's shape):
@@ -29,6 +30,7 @@
 #include "orb_host.h"
 #include "orb_math.h"
 #include "orbi_edge.h"
+#include "orbi_factors_device.h"
 #include "orbi_graph_device.h"
 #include "orbi_so3.h"
 #include "orbi_so3d.h"
@@ -47,15 +49,6 @@ __global__ void k_fac_clear(int32_t *__restrict__ result)
 {
     if (threadIdx.x < 8) result[threadIdx.x] = 0;
 }
-__device__ __forceinline__ void flush_counts(const int *s_cnt, int32_t *result)
-{
-    if (threadIdx.x < 8) {
-        const int v = s_cnt[threadIdx.x];
-        if (gridDim.x == 1) result[threadIdx.x] = v;
-        else if (v) atomicAdd(&result[threadIdx.x], v);
-    }
-}
-
 // ---- orbi_prior_information_device: a thread per job ---------------------------------------------------------------------------------
 // one cyclic Jacobi rotation of the symmetric A on the pair (P, Q), R the third index; V collects the eigenvectors in its columns
 #define JROT(P, Q, R)                                                                             \
@@ -223,38 +216,7 @@ __global__ __launch_bounds__(64) void k_fac_recover(const orbi_graph g, const or
     const int job = blockIdx.x * 64 + threadIdx.x;
     if (job < n) {
         const int st = jobs[3 * job], to = jobs[3 * job + 1], flags = jobs[3 * job + 2];
-        int code = ORBI_R_DONE;
-        if (st < 0 || st >= g.n_states || to < 0 || to >= n_dst) code = ORBI_R_RANGE;
-        else if (job_named_before(jobs, 3, job, 1, to)) code = ORBI_R_DUPLICATE;
-        if (code != ORBI_R_DONE) {
-            for (int k = 0; k < 6; ++k) bias[6 * (size_t)job + k] = 0.f;
-        } else {
-            float *o = dst + 15 * (size_t)to;
-            for (int k = 0; k < 3; ++k) {
-                o[12 + k] = (float)g.v[3 * (size_t)st + k];
-                bias[6 * (size_t)job + k] = (float)g.bg[3 * (size_t)st + k];
-                bias[6 * (size_t)job + 3 + k] = (float)g.ba[3 * (size_t)st + k];
-            }
-            if (flags & ORBI_RECOVER_POSE) {
-                float R[9], t[3], tbw[3];
-#pragma unroll
-                for (int k = 0; k < 9; ++k) o[k] = R[k] = (float)g.Rwb[9 * (size_t)st + k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) o[9 + k] = t[k] = (float)g.twb[3 * (size_t)st + k];
-                if (pose_R) {               // T_cw = T_cb * T_wb.inverse(), k_imu_predict's orders
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) tbw[k] = sum3(mul(-R[k], t[0]), mul(-R[3 + k], t[1]), mul(-R[6 + k], t[2]));
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) {
-                        const int i = k / 3, j = k % 3;
-                        pose_R[9 * (size_t)job + k] = (double)sum3(mul(cal.Rcb[3 * i], R[3 * j]), mul(cal.Rcb[3 * i + 1], R[3 * j + 1]), mul(cal.Rcb[3 * i + 2], R[3 * j + 2]));
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        pose_t[3 * (size_t)job + k] = (double)add(sum3(mul(cal.Rcb[3 * k], tbw[0]), mul(cal.Rcb[3 * k + 1], tbw[1]), mul(cal.Rcb[3 * k + 2], tbw[2])), cal.tcb[k]);
-                }
-            }
-        }
+        const int code = recover_job(g, cal, jobs, job, st, to, flags, st, dst, n_dst, bias, pose_R, pose_t);   // the biases are the state's own
         atomicAdd(&s_cnt[code], 1);
     }
     __syncthreads();
@@ -364,38 +326,7 @@ enum { W_HII = 0, W_HJJ = 225, W_B = 450, W_WALK = 480, W_STATUS = 486, W_RHO1 =
 static_assert(W_RHO1 + 1 == ORBI_EDGE_WORK, "orbi_factors.h states the workspace of an edge");
 enum { ST_OK = 0, ST_RANGE = 1, ST_REFUSED = 3 };   // == ORBI_R_DONE, ORBI_R_RANGE, ORBI_R_REFUSED
 
-// a wave's LDS slice: floats (the record's head, then the temporaries of bias_deltas) and doubles (orbi_edge.h's shared fields, then
-// (bg, ba) of state i and of state j, Rb1w*R2, (-invJr)*R2^T, Rb1w*(v2 - v1 - g*dt), Rb1w*(t2 - t1 - v1*dt - 0.5*g*dt*dt), J and W*J)
-enum { X_T = RH_WORDS, X_WORDS = RH_WORDS + BD_WORDS };
-enum { D_B1 = D_SHARED, D_B2 = D_B1 + 6, D_RR = D_B2 + 6, D_T3 = D_RR + 9, D_A = D_T3 + 9, D_C = D_A + 3, D_J = D_C + 3, D_WJ = D_J + 270, D_WORDS = D_WJ + 270 };
 static_assert(X_WORDS == 140 && D_WORDS == 825, "include/orbi.h states the LDS of k_fac_edge");
-
-// entry (r, c) of the raw 9 x 30 Jacobian (G2oTypes.cpp:413-444), columns [dphi1, dt1, dv1, dbg, dba | dphi2, dt2, dv2, -, -]
-__device__ __forceinline__ double jac_entry(const double *S, double dt, int r, int c)
-{
-    const int rb = r / 3, i = r - 3 * rb, cb = c / 3, j = c - 3 * cb;
-    if (rb == 0) {
-        if (cb == 0) return dm3(S + D_T3, S + D_R1, i, j);             // ((-invJr)*R2^T)*R1
-        if (cb == 3) return dm3(S + D_T5, S + D_JRG, i, j);            // (((-invJr)*eR^T)*Jr)*JRg
-        if (cb == 5) return S[D_INVJ + 3 * i + j];
-        return 0.0;
-    }
-    if (rb == 1) {
-        if (cb == 0) return dhat(S[D_A], S[D_A + 1], S[D_A + 2], 3 * i + j);
-        if (cb == 2) return -S[D_R1 + 3 * j + i];                      // -Rb1w
-        if (cb == 3) return -S[D_JVG + 3 * i + j];
-        if (cb == 4) return -S[D_JVA + 3 * i + j];
-        if (cb == 7) return S[D_R1 + 3 * j + i];
-        return 0.0;
-    }
-    if (cb == 0) return dhat(S[D_C], S[D_C + 1], S[D_C + 2], 3 * i + j);
-    if (cb == 1) return i == j ? -1.0 : -0.0;                          // -Identity
-    if (cb == 2) return dmul(-S[D_R1 + 3 * j + i], dt);                // (-Rb1w)*dt
-    if (cb == 3) return -S[D_JPG + 3 * i + j];
-    if (cb == 4) return -S[D_JPA + 3 * i + j];
-    if (cb == 6) return S[D_RR + 3 * i + j];                           // Rb1w*R2
-    return 0.0;
-}
 
 __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
 {
@@ -445,19 +376,7 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
     // ---- everything behind the cast to double: this edge's lines on lane groups 2 .. 4, the rotation residual beside them
     const double dt = (double)F[RH_DT], G = (double)a.gravity;
     edge_widen(F, F + X_T, S, lane);
-    if (g == 2 && q < 3) {                                                        // Rb1w*(v2 - v1 - g*dt) and ev
-        double d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) d[k] = (S[D_V2 + k] - S[D_V1 + k]) - dmul(k == 2 ? -G : 0.0, dt);
-        const double v = dmv3t(S + D_R1, d[0], d[1], d[2], q);
-        S[D_A + q] = v, S[D_E + 3 + q] = v - S[D_DVP + q];
-    } else if (g == 3 && q < 3) {                                                 // Rb1w*(t2 - t1 - v1*dt - 0.5*g*dt*dt) and ep
-        double d[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) d[k] = ((S[D_T2 + k] - S[D_T1 + k]) - dmul(S[D_V1 + k], dt)) - dmul(dmul(dmul(0.5, k == 2 ? -G : 0.0), dt), dt);
-        const double v = dmv3t(S + D_R1, d[0], d[1], d[2], q);
-        S[D_C + q] = v, S[D_E + 6 + q] = v - S[D_DVP + 3 + q];
-    } else if (g == 4) S[D_RR + q] = dm3t(S + D_R1, S + D_R2, i, j);              // Rb1w * R2
+    edge_velocity_position(S, lane, G, dt);                                       // ev, ep and Rb1w*R2
     edge_rotation(S, lane);
     if (g == 2) S[D_T3 + q] = dm3nt(S + D_INVJ, S + D_R2, i, j);                  // (-invJr) * R2^T
     // ---- chi2, the Huber kernel (g2o's RobustKernelHuber), the walks
