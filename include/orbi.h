@@ -78,7 +78,7 @@
  *
  * Kernel resources (gfx950, VGPRs / scratch bytes / static LDS bytes; tests/test_imu_resources.py reads them from the ISA):
  *   k_imu<reset> 14 / 0 / 32 B, k_imu<integrate> 103 / 0 / 12368 B, k_imu<set_bias> 97 / 0 / 12368 B, k_imu<merge> 101 / 0 / 12368 B,
- *   k_imu_predict 26 / 0 / 688 B, k_imu_pose 8 / 0 / 124 B, k_imu_clear 2 / 0 / 0 B.
+ *   k_imu_predict 26 / 0 / 688 B, k_imu_pose 8 / 0 / 124 B, k_counters_clear 2 / 0 / 0 B.
  * One wave per job, four waves per workgroup: the record, the 9x9 product's intermediate and the 3x3 temporaries live in the
  * wave's own part of LDS, the lanes are spread over matrix entries, and the phases of a sample are separated by wave-level
  * fences only -- no workgroup barrier inside the sample loop.
@@ -137,7 +137,7 @@
  *
  * Kernel resources (gfx950, VGPRs / scratch bytes / static LDS bytes; tests/test_factors_resources.py reads them from the ISA):
  *   k_fac_prior_info 103 / 0 / 32 B, k_fac_init 40 / 0 / 32 B, k_fac_edge_info 40 / 0 / 5792 B, k_fac_edge 81 / 0 / 28640 B,
- *   k_fac_gather 50 / 0 / 32 B, k_fac_oplus 70 / 0 / 32 B, k_fac_recover 38 / 0 / 32 B, k_fac_clear 2 / 0 / 0 B.
+ *   k_fac_gather 50 / 0 / 32 B, k_fac_oplus 70 / 0 / 32 B, k_fac_recover 38 / 0 / 32 B, k_counters_clear 2 / 0 / 0 B.
  * The graphs are tiny (2 states for the tracker, a few tens for a local window) and every call is latency-bound: nothing here has
  * been tuned for throughput and no throughput claim is made.  An inertial edge is one wave, four per workgroup (k_imu's shape), its
  * 9x30 Jacobian, the 9x9 information and their product in the wave's own LDS slice; a wave per state then gathers its edges in edge

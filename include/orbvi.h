@@ -100,7 +100,7 @@
  *               d_out[2] is that pivot.  g2o treats a failed solve as a rejected trial.
  *
  * Kernel resources (gfx950, VGPRs / scratch bytes / static LDS bytes; tests/test_vi_resources.py reads them from the ISA):
- *   k_vi_linearize 126 / 0 / 3952 B, k_vi_solve 81 / 0 / 30032 B, k_vi_clear 2 / 0 / 0 B.
+ *   k_vi_linearize 126 / 0 / 3952 B, k_vi_solve 81 / 0 / 30032 B, k_counters_clear 2 / 0 / 0 B.
  * Both calls are latency-bound (one group of a few hundred to 2000 edges; at most 60 unknowns): nothing here has been tuned for
  * throughput and no throughput claim is made.
  */

@@ -83,6 +83,22 @@ __device__ __forceinline__ void block_add(int *s_count, int slot, int v)
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s_count[slot], v);
 }
 
+// The eight counters of a d_result.  A kernel counts in LDS and ends on flush_counts behind a barrier: one workgroup writes them, several
+// add to what k_counters_clear zeroed ahead of them on the stream (LAUNCH_COUNTED of orb_host.h launches the pair).  A template only so
+// that a file which never launches it gets no copy of it: a plain __global__ is emitted wherever it is seen
+template <int = 0> __global__ void k_counters_clear(int32_t *__restrict__ result)
+{
+    if (threadIdx.x < 8) result[threadIdx.x] = 0;
+}
+__device__ __forceinline__ void flush_counts(const int *s_cnt, int32_t *result)
+{
+    if (threadIdx.x < 8) {
+        const int v = s_cnt[threadIdx.x];
+        if (gridDim.x == 1) result[threadIdx.x] = v;
+        else if (v) atomicAdd(&result[threadIdx.x], v);
+    }
+}
+
 // N per-thread floating-point sums over a workgroup of WAVES waves in a fixed order, so that the same input gives the same bytes and no
 // floating-point atomic is needed.  block_sums_put: the butterfly over the wave, then lane 0 leaves sum k of [first, last) (uniform) in
 // s_part[wave][k]; the caller's barrier follows; block_sums_get: sum k of the workgroup, the wave slots added in ascending order

@@ -29,6 +29,15 @@ hipError_t orbx_lds_opt_in(const void *kernel, size_t bytes);
         if (e_ != hipSuccess) return orbx_set_error(ORBX_E_NO_DEVICE, std::string(#expr ": ") + hipGetErrorString(e_)); \
     } while (0)
 
+// launches `grid` workgroups of a kernel that ends in flush_counts (orb_device.h), or in its like; eight zeros first unless exactly one
+// workgroup writes them
+#define LAUNCH_COUNTED(kernel, grid, threads, s, result, ...)                                           \
+    do {                                                                                                \
+        if ((grid) != 1) hipLaunchKernelGGL(k_counters_clear<>, dim3(1), dim3(64), 0, s, result);       \
+        if ((grid) > 0) hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, __VA_ARGS__);       \
+        ORB_TRY(hipGetLastError());                                                                     \
+    } while (0)
+
 namespace {
 
 // Fails without a HIP device.  With `device`, also resolves a handle's ordinal: < 0 is the calling thread's current device.

@@ -21,6 +21,8 @@ static_assert(offsetof(orbi_record, JPa) == 4 * RH_JPA && offsetof(orbi_record, 
 
 namespace {
 
+// a wave's float slice: the record's head, then the temporaries of bias_deltas
+enum { X_T = RH_WORDS, X_WORDS = RH_WORDS + BD_WORDS };
 // the shared fields of a wave's double slice; a kernel numbers its own fields from D_SHARED on
 enum {
     D_R1 = 0, D_R2 = 9, D_T1 = 18, D_T2 = 21, D_V1 = 24, D_V2 = 27,                                  // the vertices of both states

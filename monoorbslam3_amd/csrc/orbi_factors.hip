@@ -11,7 +11,8 @@
 // atan2 and sqrt.  What EdgeInertial has in common with the edges of the IMU initialisation (orbii.hip) -- the widening, the rotation
 // residual and its Jacobian factors, Omega*e with chi2, the quadratic form, the refused-edge rule -- is orbi_edge.h's; ev, ep, the
 // Jacobian's entries and a job of the recovery, which fullInertialOptimize's shared-bias edge (orbfi.hip) takes as they are, are
-// orbi_factors_device.h's; the Huber weight and the walks are here.
+// orbi_factors_device.h's; the Huber weight and the walks are here.  The eight counters of a d_result -- the flush at a kernel's end,
+// the clear kernel ahead of several workgroups and the launch of the pair (LAUNCH_COUNTED) -- are orb_device.h's and orb_host.h's.
 //
 // Shape: the graphs are tiny (two states for the tracker, a few tens for a local window), so every kernel is latency-bound and the
 // aim is few launches and short dependent chains, not throughput.  An inertial edge is ONE WAVE, four per workgroup (k_imu's shape):
@@ -27,6 +28,7 @@
 
 #include "../../include/orbi.h"
 #include "../../include/orbx.h"
+#include "orb_device.h"
 #include "orb_host.h"
 #include "orb_math.h"
 #include "orbi_edge.h"
@@ -44,11 +46,6 @@ namespace {
 
 constexpr int FAC_WAVES = 4, FAC_T = 64 * FAC_WAVES;
 
-// per-workgroup counters -> d_result: one workgroup writes, several add to what k_fac_clear zeroed ahead of them on the stream
-__global__ void k_fac_clear(int32_t *__restrict__ result)
-{
-    if (threadIdx.x < 8) result[threadIdx.x] = 0;
-}
 // ---- orbi_prior_information_device: a thread per job ---------------------------------------------------------------------------------
 // one cyclic Jacobi rotation of the symmetric A on the pair (P, Q), R the third index; V collects the eigenvectors in its columns
 #define JROT(P, Q, R)                                                                             \
@@ -556,14 +553,6 @@ int check_jobs(const void *jobs, int n, const void *result)
     if (n > ORBI_MAX_JOBS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBI_MAX_JOBS (4096) jobs in one call");
     return ORBX_OK;
 }
-
-// launches `grid` workgroups of a kernel that ends in flush_counts; eight zeros first unless exactly one workgroup writes them
-#define LAUNCH_COUNTED(kernel, grid, threads, s, result, ...)                                           \
-    do {                                                                                                \
-        if ((grid) != 1) hipLaunchKernelGGL(k_fac_clear, dim3(1), dim3(64), 0, s, result);              \
-        if ((grid) > 0) hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, __VA_ARGS__);       \
-        ORB_TRY(hipGetLastError());                                                                     \
-    } while (0)
 
 } // namespace
 

@@ -1,12 +1,14 @@
 // What the kernels on EdgeInertial share beyond orbi_edge.h (k_fac_edge and k_fac_recover of orbi_factors.hip: a bias pair per state;
 // k_fi_edge and k_fi_recover of orbfi.hip: one bias pair in a carrier state): the fields of a wave's slices that EdgeInertial adds to
 // orbi_edge.h's, ev and ep, the entries of the raw 9 x 30 Jacobian (G2oTypes.cpp:377-445), a job of the optimisers' recovery
-// (Optimize.cpp:401-434, :602-607, :1044-1053) and the flush of a workgroup's counters.  Every order is the one include/orbi.h fixes.
+// (Optimize.cpp:401-434, :602-607, :1044-1053).  The flush of a workgroup's counters is orb_device.h's.  Every order is the one
+// include/orbi.h fixes.
 // Internal: forced-inline device functions inside an anonymous namespace, so it adds no symbol.  A correction is made here, once.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/orbi.h"
+#include "orb_device.h"
 #include "orbi_edge.h"
 #include "orbi_graph_device.h"
 #include "orbi_so3.h"
@@ -16,18 +18,8 @@
 
 namespace {
 
-__device__ __forceinline__ void flush_counts(const int *s_cnt, int32_t *result)
-{
-    if (threadIdx.x < 8) {
-        const int v = s_cnt[threadIdx.x];
-        if (gridDim.x == 1) result[threadIdx.x] = v;
-        else if (v) atomicAdd(&result[threadIdx.x], v);
-    }
-}
-
-// a wave's LDS slice: floats (the record's head, then the temporaries of bias_deltas) and doubles (orbi_edge.h's shared fields, then
-// (bg, ba) of state i and of state j, Rb1w*R2, (-invJr)*R2^T, Rb1w*(v2 - v1 - g*dt), Rb1w*(t2 - t1 - v1*dt - 0.5*g*dt*dt), J and W*J)
-enum { X_T = RH_WORDS, X_WORDS = RH_WORDS + BD_WORDS };
+// a wave's LDS slice: floats (orbi_edge.h's X_WORDS) and doubles (orbi_edge.h's shared fields, then (bg, ba) of state i and of state j,
+// Rb1w*R2, (-invJr)*R2^T, Rb1w*(v2 - v1 - g*dt), Rb1w*(t2 - t1 - v1*dt - 0.5*g*dt*dt), J and W*J)
 enum { D_B1 = D_SHARED, D_B2 = D_B1 + 6, D_RR = D_B2 + 6, D_T3 = D_RR + 9, D_A = D_T3 + 9, D_C = D_A + 3, D_J = D_C + 3, D_WJ = D_J + 270, D_WORDS = D_WJ + 270 };
 
 // entry (r, c) of the raw 9 x 30 Jacobian (G2oTypes.cpp:413-444), columns [dphi1, dt1, dv1, dbg, dba | dphi2, dt2, dv2, -, -]

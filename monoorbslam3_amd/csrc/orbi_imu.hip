@@ -25,6 +25,7 @@
 
 #include "../../include/orbi.h"
 #include "../../include/orbx.h"
+#include "orb_device.h"
 #include "orb_host.h"
 #include "orb_math.h"
 #include "orbi_so3.h"
@@ -323,16 +324,11 @@ template <int MODE> __global__ __launch_bounds__(IMU_T) void k_imu(const ImuArgs
         }
     }
     __syncthreads();
-    if (threadIdx.x < 8) {   // one workgroup writes; several add to what k_imu_clear zeroed ahead of them on the stream
+    if (threadIdx.x < 8) {   // flush_counts (orb_device.h) with the greatest NEED: one workgroup writes, several add to k_counters_clear's zeros
         const int v = s_cnt[threadIdx.x];
         if (gridDim.x == 1) a.result[threadIdx.x] = v;
         else if (v) threadIdx.x == ORBI_R_NEED ? atomicMax(&a.result[threadIdx.x], v) : atomicAdd(&a.result[threadIdx.x], v);
     }
-}
-
-__global__ void k_imu_clear(int32_t *__restrict__ result)
-{
-    if (threadIdx.x < 8) result[threadIdx.x] = 0;
 }
 
 // the prediction: one wave, nine lanes per matrix; LDS words
@@ -420,9 +416,7 @@ template <int MODE> int launch(const ImuArgs &a, void *stream)
     if (int rc = orb_need_device()) return rc;
     hipStream_t s = (hipStream_t)stream; // NULL is stream 0 itself (include/orbx.h, "Streams")
     const int grid = (a.n + IMU_WAVES - 1) / IMU_WAVES;
-    if (grid != 1) hipLaunchKernelGGL(k_imu_clear, dim3(1), dim3(64), 0, s, a.result);
-    if (grid > 0) hipLaunchKernelGGL(k_imu<MODE>, dim3(grid), dim3(IMU_T), 0, s, a);
-    ORB_TRY(hipGetLastError());
+    LAUNCH_COUNTED(k_imu<MODE>, grid, IMU_T, s, a.result, a);
     return ORBX_OK;
 }
 

@@ -250,10 +250,8 @@ __device__ __forceinline__ int edge_status(const LinArgs &a, int e)
     return edge_refused(a.info, e) ? ORBI_R_REFUSED : ORBI_R_DONE;
 }
 
-// a wave's LDS slice: floats (the record's head, then the temporaries of bias_deltas) and doubles (orbi_edge.h's shared fields, then the
-// constants Oc and Pcb of both key frames, the shared vertices, g = Rwg*gI, JG = Rwg*gm, v2 - v1, (Oc2 - Oc1) - v1*dt, (-Rb1w)*JG,
-// (c*Rb1w)*JG, J and Omega*J)
-enum { X_T = RH_WORDS, X_WORDS = RH_WORDS + BD_WORDS };
+// a wave's LDS slice: floats (orbi_edge.h's X_WORDS) and doubles (orbi_edge.h's shared fields, then the constants Oc and Pcb of both key
+// frames, the shared vertices, g = Rwg*gI, JG = Rwg*gm, v2 - v1, (Oc2 - Oc1) - v1*dt, (-Rb1w)*JG, (c*Rb1w)*JG, J and Omega*J)
 enum {
     D_O1 = D_SHARED, D_O2 = D_O1 + 3, D_P1 = D_O2 + 3, D_P2 = D_P1 + 3, D_SH = D_P2 + 3, D_G = D_SH + SH_WORDS, D_JG = D_G + 3, D_DV = D_JG + 6,
     D_DO = D_DV + 3, D_RJG = D_DO + 3, D_CRJG = D_RJG + 6, D_J = D_CRJG + 6, D_WJ = D_J + 135, D_WORDS = D_WJ + 135

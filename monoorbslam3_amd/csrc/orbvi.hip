@@ -31,12 +31,6 @@ static_assert(sizeof(orbvi_camera) == 72, "orbvi.h fixes this layout");
 
 namespace {
 
-// per-workgroup counters -> d_result: one workgroup writes, several add to what k_vi_clear zeroed ahead of them on the stream
-__global__ void k_vi_clear(int32_t *__restrict__ result)
-{
-    if (threadIdx.x < 8) result[threadIdx.x] = 0;
-}
-
 // ---- orbvi_linearize_device: a 1024-thread workgroup per group ---------------------------------------------------------------------------
 constexpr int VI_T = 1024, VI_WAVES = VI_T / 64;
 enum { S_PLAIN = 27, S_ROBUST = 28, VI_SUMS = 29 };    // behind quad_accumulate's 21 + 6
@@ -313,9 +307,7 @@ extern "C" int orbvi_linearize_device(orbi_graph graph, orbi_calib calib, orbvi_
     a.n_groups = n_groups, a.cap_edges = cap_edges, a.group_state = d_group_state, a.edge_off = d_edge_off, a.points = d_points, a.z = d_edge_z;
     a.w = d_edge_inv_sigma2, a.active = d_active, a.threshold = chi2_threshold, a.mode = mode, a.work = d_work, a.err = d_err, a.chi2 = d_chi2, a.total = d_total;
     a.H = d_H_diag, a.b = d_b, a.n_inliers = d_n_inliers, a.result = d_result;
-    if (n_groups != 1) hipLaunchKernelGGL(k_vi_clear, dim3(1), dim3(64), 0, s, d_result);
-    if (n_groups > 0) hipLaunchKernelGGL(k_vi_linearize, dim3(n_groups), dim3(VI_T), 0, s, a);
-    ORB_TRY(hipGetLastError());
+    LAUNCH_COUNTED(k_vi_linearize, n_groups, VI_T, s, d_result, a);
     return ORBX_OK;
 }
 

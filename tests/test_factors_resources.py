@@ -7,7 +7,7 @@ from test_kernel_resources import _isa, _kernels
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # kernel (substring of the mangled name) -> static LDS bytes as include/orbi.h states them
-STATED = {"k_fac_clear": 0, "k_fac_prior_info": 32, "k_fac_init": 32, "k_fac_oplus": 32, "k_fac_recover": 32, "k_fac_edge_info": 5792,
+STATED = {"k_counters_clear": 0, "k_fac_prior_info": 32, "k_fac_init": 32, "k_fac_oplus": 32, "k_fac_recover": 32, "k_fac_edge_info": 5792,
           "k_fac_edgeENS": 28640, "k_fac_gather": 32}
 
 

@@ -31,11 +31,20 @@ def test_the_kernels_use_no_scratch_memory_and_the_lds_the_header_states():
 def test_the_edge_and_the_recovery_are_shared_not_copied():
     """orbfi.hip and orbi_factors.hip take the edge's prologue, widening, rotation residual, chi2 and quadratic form from csrc/orbi_edge.h, the
     fields EdgeInertial adds, ev and ep, the Jacobian's entries and a job of the recovery from csrc/orbi_factors_device.h, the float part from
-    csrc/orbi_so3.h and the validity of an edge and the duplicate scan from csrc/orbi_graph_device.h; neither defines them itself"""
+    csrc/orbi_so3.h, the validity of an edge and the duplicate scan from csrc/orbi_graph_device.h and the flush of the eight counters from
+    csrc/orb_device.h, which also has the one clear kernel that csrc/orb_host.h's LAUNCH_COUNTED launches; neither defines them itself"""
     shared = open(os.path.join(CSRC, "orbi_factors_device.h")).read()
+    device = open(os.path.join(CSRC, "orb_device.h")).read()
     own = ("jac_entry", "edge_velocity_position", "recover_job", "flush_counts")
     for fn in own:
-        assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, shared, re.M)) == 1, fn
+        where = device if fn == "flush_counts" else shared
+        assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, where, re.M)) == 1, fn
+    assert "flush_counts(" not in shared and len(re.findall(r"__global__ void k_counters_clear\(", device)) == 1
+    assert "define LAUNCH_COUNTED" in open(os.path.join(CSRC, "orb_host.h")).read()
+    for src in ("orbfi.hip", "orbi_factors.hip", "orbvi.hip", "orbi_imu.hip"):          # no clear kernel and no launch of one of their own
+        text = open(os.path.join(CSRC, src)).read()
+        assert not re.search(r"__global__[^\n(]*clear\(", text) and not re.search(r"hipLaunchKernelGGL\([^\n]*clear", text), src
+        assert "define LAUNCH_COUNTED" not in text and (src == "orbfi.hip") == ("LAUNCH_COUNTED(" not in text), src
     edge_fns = ("edge_refused", "edge_load", "edge_widen", "edge_rotation", "edge_chi2", "edge_jtwj", "edge_quadratic_form")
     for src in ("orbfi.hip", "orbi_factors.hip"):
         text = open(os.path.join(CSRC, src)).read()

@@ -7,7 +7,7 @@ from test_kernel_resources import _isa, _kernels
 # kernel (substring of the mangled name) -> (the header's name for it, static LDS bytes as include/orbi.h states them)
 STATED = {"k_imuILi0E": ("k_imu<reset>", 32), "k_imuILi1E": ("k_imu<integrate>", 12368), "k_imuILi2E": ("k_imu<set_bias>", 12368),
           "k_imuILi3E": ("k_imu<merge>", 12368), "k_imu_predict": ("k_imu_predict", 688), "k_imu_pose": ("k_imu_pose", 124),
-          "k_imu_clear": ("k_imu_clear", 0)}
+          "k_counters_clear": ("k_counters_clear", 0)}
 
 
 def test_the_imu_kernels_use_no_scratch_memory_and_the_lds_the_header_states():

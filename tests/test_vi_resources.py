@@ -9,7 +9,7 @@ from test_vw_resources import SHARED_DEVICE, SHARED_HOST
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "monoorbslam3_amd", "csrc")
 # kernel (substring of the mangled name) -> static LDS bytes as include/orbvi.h states them
-STATED = {"k_vi_clear": 0, "k_vi_linearize": 3952, "k_vi_solve": 30032}
+STATED = {"k_counters_clear": 0, "k_vi_linearize": 3952, "k_vi_solve": 30032}
 
 
 def test_the_kernels_use_no_scratch_memory_and_the_lds_the_header_states():
