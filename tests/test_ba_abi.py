@@ -9,8 +9,9 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, E_ARG, E_NO_DEVICE = 0, -1, -2
+from abi_checks import E_ARG, E_NO_DEVICE, P, ROOT, built, declared, returns
+
+OK = 0
 RANGE, ORDER, TWICE, ALL_FIXED = ("edge index out of range", "edges must be grouped by point",
                                   "a point is observed twice by the same key frame", "every pose is fixed: nothing to optimise")
 
@@ -113,10 +114,7 @@ def test_the_index_builder_refuses_malformed_content(ba_index, name):
 # ----------------------------------------------------------------------------------------------------------------- the C ABI
 @pytest.fixture(scope="module")
 def ba():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import ba
-    return ba
+    return built("ba")
 
 
 def _host_problem(ba, fixed, n_points, ep, el, keep):
@@ -129,11 +127,6 @@ def _host_problem(ba, fixed, n_points, ep, el, keep):
                        (C.c_double * 4)(0, 0, 0, 0))
 
 
-def _last_error():
-    from monoorbslam3_amd import _lib
-    return _lib.lib().orbx_last_error().decode()
-
-
 def _host_calls(ba, prob):
     """the three host-pointer entry points on one problem, every output NULL (any of them may be)"""
     L = ba._L()
@@ -144,10 +137,10 @@ def _host_calls(ba, prob):
 
 
 def _device_calls(ba, **over):
-    """the five entry points that take device pointers and a pose batch on host pointers, with valid arguments (fake addresses, never
-    dereferenced before the device is looked for) except for `over`"""
+    """the five entry points that take device pointers and a pose batch on host pointers, with valid arguments (the fake device address)
+    except for `over`"""
     L = ba._L()
-    p = 0x1000
+    p = P
     a = dict(n_poses=3, n_points=5, n_edges=9, n_frames=1, n2=4, nq=4, pose_R=p, out_R=p, chi2=p, outlier=p, edge_off=p, frame_mp=p, inlier=p)
     a.update(over)
     tail = (0, (C.c_double * 4)(0, 0, 0, 0))
@@ -172,12 +165,10 @@ DEVICE_NAMES = ("orbba_local_bundle_adjustment_device", "orbba_pose_optimize_bat
 
 
 def test_the_eight_entry_points_are_declared_and_bound(ba):
-    import re
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "orbba.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(orbba_[a-z_]+)\s*\(", header))
-    assert declared == set(HOST_NAMES) | set(DEVICE_NAMES) | {"orbba_set_variant"}
+    names = declared("orbba_", "orbba.h")
+    assert names == set(HOST_NAMES) | set(DEVICE_NAMES) | {"orbba_set_variant"}
     L = ba._L()
-    for name in declared:
+    for name in names:
         assert getattr(L, name).argtypes is not None, name
 
 
@@ -187,13 +178,13 @@ def test_argument_errors_are_reported_before_the_device_is_looked_for(ba):
     good = _host_problem(ba, *VALID["3_poses_5_points_9_edges"], keep)
     lin, opt, res = ba._Result(), ba._LmOptions(max_iterations=1), ba._LmResult()
     # a NULL struct
-    for rc in (L.orbba_linearize(None, C.byref(lin), -1), L.orbba_linearize(C.byref(good), None, -1),
-               L.orbba_optimize(None, C.byref(opt), C.byref(res), -1), L.orbba_optimize(C.byref(good), None, C.byref(res), -1),
-               L.orbba_optimize(C.byref(good), C.byref(opt), None, -1), L.orbba_local_bundle_adjustment(None, C.byref(res), None, -1),
-               L.orbba_local_bundle_adjustment(C.byref(good), None, None, -1), L.orbba_local_bundle_adjustment_device(None, C.byref(res), 0x1000, None),
-               L.orbba_local_bundle_adjustment_device(C.byref(good), None, 0x1000, None), L.orbba_pose_optimize_batch(None, None, -1),
-               L.orbba_pose_optimize_batch_device(None, None, None)):
-        assert rc == E_ARG and _last_error() == "null argument"
+    for fn, *args in ((L.orbba_linearize, None, C.byref(lin), -1), (L.orbba_linearize, C.byref(good), None, -1),
+                      (L.orbba_optimize, None, C.byref(opt), C.byref(res), -1), (L.orbba_optimize, C.byref(good), None, C.byref(res), -1),
+                      (L.orbba_optimize, C.byref(good), C.byref(opt), None, -1), (L.orbba_local_bundle_adjustment, None, C.byref(res), None, -1),
+                      (L.orbba_local_bundle_adjustment, C.byref(good), None, None, -1), (L.orbba_local_bundle_adjustment_device, None, C.byref(res), P, None),
+                      (L.orbba_local_bundle_adjustment_device, C.byref(good), None, P, None), (L.orbba_pose_optimize_batch, None, None, -1),
+                      (L.orbba_pose_optimize_batch_device, None, None, None)):
+        assert returns(E_ARG, fn, *args) == "null argument"
     # sizes and arrays of the host-pointer problem
     for field, value, text, names in [("n_poses", 0, "bad sizes", HOST_NAMES), ("n_points", 0, "bad sizes", HOST_NAMES),
                                       ("n_edges", -1, "bad sizes", HOST_NAMES), ("n_edges", 0, "bad sizes", HOST_NAMES[1:]),
@@ -204,14 +195,14 @@ def test_argument_errors_are_reported_before_the_device_is_looked_for(ba):
         setattr(bad, field, value)
         calls = _host_calls(ba, bad)
         for name in names:
-            assert calls[name]() == E_ARG and _last_error() == text, (field, name)
+            assert returns(E_ARG, calls[name], what=(field, name)) == text
     opt_bad = ba._LmOptions(max_iterations=-1)
-    assert L.orbba_optimize(C.byref(good), C.byref(opt_bad), C.byref(res), -1) == E_ARG and _last_error() == "negative iteration count"
+    assert returns(E_ARG, L.orbba_optimize, C.byref(good), C.byref(opt_bad), C.byref(res), -1) == "negative iteration count"
     # malformed content
     for case, (problem, text) in MALFORMED.items():
         calls = _host_calls(ba, _host_problem(ba, *problem, keep))
         for name in HOST_NAMES[1:] + (HOST_NAMES[:1] if text in (RANGE, ORDER) else ()):
-            assert calls[name]() == E_ARG and _last_error() == text, (case, name)
+            assert returns(E_ARG, calls[name], what=(case, name)) == text
     # the device-pointer entry points and the pose batch
     lba, pob = "null array (every pointer is device memory here, chi2 and outlier included)", "null array (every pointer is device memory here, chi2 included)"
     for over, name, text in [(dict(n_poses=0), "orbba_local_bundle_adjustment_device", "bad sizes"),
@@ -226,7 +217,7 @@ def test_argument_errors_are_reported_before_the_device_is_looked_for(ba):
                              (dict(n_frames=0), "orbba_pose_optimize_batch", "bad sizes / null arrays"),
                              (dict(edge_off=None), "orbba_pose_optimize_batch", "bad sizes / null arrays"),
                              (dict(out_R=None), "orbba_pose_optimize_batch", "null output array")]:
-        assert _device_calls(ba, **over)[name]() == E_ARG and _last_error() == text, (over, name)
+        assert returns(E_ARG, _device_calls(ba, **over)[name], what=(over, name)) == text
 
 
 def test_a_valid_call_fails_loudly_without_a_gpu(ba):
@@ -240,5 +231,4 @@ def test_a_valid_call_fails_loudly_without_a_gpu(ba):
     calls["orbba_linearize(no edges)"] = _host_calls(ba, _host_problem(ba, FIXED, 5, [], [], keep))["orbba_linearize"]
     assert len(calls) == 5 + 2 * 3 + 1
     for name, call in calls.items():
-        assert call() == E_NO_DEVICE, name
-        assert "no HIP device" in _last_error(), name
+        returns(E_NO_DEVICE, call, what=name)                   # and "no HIP device" in the message

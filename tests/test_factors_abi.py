@@ -2,52 +2,29 @@
 orbi_factors.h it includes -- is exported by the built library and resolved by monoorbslam3_amd.imu; the layouts are the header's;
 bad arguments are reported before the device is looked for; without a GPU every call fails with ORBX_E_NO_DEVICE."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
+import abi_checks as abi
 import factors_model as fm
+from abi_checks import E_ARG, E_NO_DEVICE, E_UNSUPPORTED, P, returns
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_ARG, E_NO_DEVICE, E_UNSUPPORTED = -1, -2, -4
 FACTOR_ENTRY_POINTS = ["orbi_edge_information_device", "orbi_graph_init_device", "orbi_graph_oplus_device", "orbi_graph_recover_device",
                        "orbi_linearize_device", "orbi_prior_information_device"]
 
 
 @pytest.fixture(scope="module")
 def imu():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import imu
-    return imu
-
-
-def _declared(name, seen=None):
-    """the orbi_* functions a header declares, the headers it includes from its own directory included"""
-    seen = set() if seen is None else seen
-    if name in seen:
-        return set()
-    seen.add(name)
-    txt = open(os.path.join(ROOT, "include", name)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    out = set(re.findall(r"\b(orbi_[a-z0-9_]+)\s*\(", txt))
-    for inc in re.findall(r'#include "(orbi[a-z_]*\.h)"', txt):
-        out |= _declared(inc, seen)
-    return out
+    return abi.built("imu")
 
 
 def test_every_declared_entry_point_is_exported_and_mirrored(imu):
-    from monoorbslam3_amd import _lib
-    declared = _declared("orbi.h")
+    declared = abi.declared("orbi_", "orbi.h", follow_includes=True)      # itself or through the orbi_factors.h it includes
     assert set(FACTOR_ENTRY_POINTS) <= declared and len(declared) == 12, sorted(declared)
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in sorted(declared):
-        assert hasattr(L, n), "liborbx.so does not export %s" % n
-        assert n in imu._SIGS and callable(getattr(imu, n[len("orbi_"):])), n
-    imu._L()                                                    # binds every name of _SIGS or raises
+    abi.exported_and_mirrored(imu, "orbi_", declared, sigs_equal=False)
     assert imu.EDGE == fm.EDGE and imu.PRIOR == fm.PRIOR and imu.PRIOR_JOB == fm.PRIOR_JOB and C.sizeof(imu.Graph) == 56
-    header = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "orbi_factors.h")).read())
+    header = re.sub(r"\s+", " ", abi.header("orbi_factors.h"))
     for name, value in [("ORBI_FIX_POSE", imu.FIX_POSE), ("ORBI_FIX_VELO", imu.FIX_VELO), ("ORBI_FIX_GYRO", imu.FIX_GYRO), ("ORBI_FIX_ACC", imu.FIX_ACC),
                         ("ORBI_EDGE_WALKS", imu.EDGE_WALKS), ("ORBI_PRIOR_VELO", imu.PRIOR_VELO), ("ORBI_PRIOR_GYRO", imu.PRIOR_GYRO),
                         ("ORBI_PRIOR_ACC", imu.PRIOR_ACC), ("ORBI_PRIOR_ACC_GYRO_INFO", imu.PRIOR_ACC_GYRO_INFO), ("ORBI_RECOVER_POSE", imu.RECOVER_POSE),
@@ -58,8 +35,8 @@ def test_every_declared_entry_point_is_exported_and_mirrored(imu):
 
 
 def _calls(imu, **over):
-    """every wrapper with valid arguments (fake device addresses, never dereferenced) except for `over`"""
-    p = 0x1000
+    """every wrapper with valid arguments (the fake device address) except for `over`"""
+    p = P
     a = dict(Rwb=p, twb=p, v=p, bg=p, ba=p, fixed=p, n_states=3, bank=p, cap=8, src=p, n_src=3, jobs=p, n=2, result=p, priors=p, n_priors=2,
              edges=p, n_edges=2, info=p, walk=p, work=p, err=p, chi2=p, total=p, pjobs=p, n_pjobs=1, chi2_prior=p, delta=4.1134, mode=0,
              H_diag=p, H_off=p, b=p, J=p, flt=p, dx=p, it=p, dst=p, n_dst=3, bias=p, pose_R=p, pose_t=p)
@@ -77,13 +54,6 @@ def _calls(imu, **over):
                                                a["mode"], a["H_diag"], a["H_off"], a["b"], a["J"], a["flt"]),
         graph_oplus=lambda: imu.graph_oplus_device(g, a["dx"], a["it"], a["result"]),
         graph_recover=lambda: imu.graph_recover_device(g, cal, a["jobs"], a["n"], a["dst"], a["n_dst"], a["bias"], a["result"], a["pose_R"], a["pose_t"]))
-
-
-def _code(call):
-    from monoorbslam3_amd._lib import OrbxError
-    with pytest.raises(OrbxError) as e:
-        call()
-    return e.value.code
 
 
 GRAPH_CALLS = ("graph_init", "linearize", "graph_oplus", "graph_recover")
@@ -106,23 +76,18 @@ def test_argument_errors_are_reported_before_the_device_is_looked_for(imu):
     cases += [(dict(mode=2), ("linearize",)), (dict(mode=-1), ("linearize",)), (dict(delta=float("nan")), ("linearize",)), (dict(n_pjobs=-1), ("linearize",))]
     for over, names in cases:
         for name in names:
-            assert _code(_calls(imu, **over)[name]) == E_ARG, (over, name)
+            returns(E_ARG, _calls(imu, **over)[name], what=(over, name))
     for over, names in [(dict(n=imu.MAX_JOBS + 1), ("prior_information", "graph_init", "graph_recover")), (dict(n_states=imu.MAX_JOBS + 1), GRAPH_CALLS),
                         (dict(n_edges=imu.MAX_JOBS + 1), ("edge_information", "linearize")), (dict(n_pjobs=imu.MAX_JOBS + 1), ("linearize",))]:
         for name in names:
-            assert _code(_calls(imu, **over)[name]) == E_UNSUPPORTED, (over, name)
+            returns(E_UNSUPPORTED, _calls(imu, **over)[name], what=(over, name))
 
 
 def test_every_wrapper_fails_loudly_without_a_gpu(imu):
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("needs a machine without a GPU")
-    from monoorbslam3_amd import _lib
     for name, call in _calls(imu).items():
-        assert _code(call) == E_NO_DEVICE, name
-        assert b"no HIP device" in _lib.lib().orbx_last_error(), name
+        returns(E_NO_DEVICE, call, what=name)                   # and "no HIP device" in the message
     # the optional arguments are optional: still the device that is missing, not an argument
-    assert _code(_calls(imu, mode=1, H_diag=None, H_off=None, b=None, J=None, flt=None)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(imu, n_pjobs=0, pjobs=None, priors=None, chi2_prior=None, n_priors=0)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(imu, pose_R=None, pose_t=None)["graph_recover"]) == E_NO_DEVICE and _code(_calls(imu, src=None, n_src=0)["prior_information"]) == E_NO_DEVICE
-    assert _code(_calls(imu, n=0)["graph_init"]) == E_NO_DEVICE and _code(_calls(imu, n_edges=0)["linearize"]) == E_NO_DEVICE
+    returns(E_NO_DEVICE, _calls(imu, mode=1, H_diag=None, H_off=None, b=None, J=None, flt=None)["linearize"])
+    returns(E_NO_DEVICE, _calls(imu, n_pjobs=0, pjobs=None, priors=None, chi2_prior=None, n_priors=0)["linearize"])
+    returns(E_NO_DEVICE, _calls(imu, pose_R=None, pose_t=None)["graph_recover"]), returns(E_NO_DEVICE, _calls(imu, src=None, n_src=0)["prior_information"])
+    returns(E_NO_DEVICE, _calls(imu, n=0)["graph_init"]), returns(E_NO_DEVICE, _calls(imu, n_edges=0)["linearize"])

@@ -9,51 +9,39 @@ import re
 import pytest
 
 import full_inertial_model as fim
+from abi_checks import E_ARG, E_NO_DEVICE, E_UNSUPPORTED, P, ROOT, built, exported_and_mirrored, flat, header, returns, stripped
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_ARG, E_NO_DEVICE, E_UNSUPPORTED = -1, -2, -4
 ENTRY_POINTS = {"orbfi_jobs_device": 14, "orbfi_linearize_device": 25, "orbfi_recover_device": 12}      # name -> arguments
-P = 0x1000                # a fake device pointer: never dereferenced, every call below fails before a launch
 
 
 @pytest.fixture(scope="module")
 def fi():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import full_inertial
-    return full_inertial
-
-
-def _header(name="orbfi.h"):
-    return open(os.path.join(ROOT, "include", name)).read()
+    return built("full_inertial")
 
 
 def test_every_declared_entry_point_is_exported_and_mirrored_with_its_signature(fi):
-    from monoorbslam3_amd import _lib, imu
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    from monoorbslam3_amd import imu
+    txt = stripped("orbfi.h")
     declared = {m.group(1): m.group(2) for m in re.finditer(r"\bint (orbfi_[a-z0-9_]+)\s*\(([^;]*)\);", txt)}
     assert set(declared) == set(ENTRY_POINTS), sorted(declared)
-    L = C.CDLL(_lib.LIB_PATH)
+    exported_and_mirrored(fi, "orbfi_", declared, sigs_equal=True)
     for n, args in declared.items():
-        assert hasattr(L, n), "liborbx.so does not export %s" % n
-        assert n in fi._SIGS and callable(getattr(fi, n[len("orbfi_"):])), n
         assert len(args.split(",")) == ENTRY_POINTS[n] == len(fi._SIGS[n]), (n, len(args.split(",")), len(fi._SIGS[n]))
         for decl, ct in zip(args.split(","), fi._SIGS[n]):        # pointers, ints, floats and doubles where the header has them
             decl = decl.strip()
             want = C.c_void_p if "*" in decl else imu.Graph if decl.startswith("orbi_graph") else imu.Calib if decl.startswith("orbi_calib") else \
                 C.c_float if decl.startswith("float") else C.c_double if decl.startswith("double") else C.c_int
             assert ct is want, (n, decl, ct)
-    assert set(fi._SIGS) == set(declared)
-    assert fi._L() is _lib.lib() and fi.Calib is imu.Calib and fi.Graph is imu.Graph
-    assert '#include "orbi.h"' in txt and "orbvw" not in _header()       # like orbm.h it names the visual window's calls by what they do
+    assert fi.Calib is imu.Calib and fi.Graph is imu.Graph
+    assert '#include "orbi.h"' in txt and "orbvw" not in header("orbfi.h")     # like orbm.h it names the visual window's calls by what they do
     for other in os.listdir(os.path.join(ROOT, "include")):         # nothing includes it
-        assert other == "orbfi.h" or "orbfi.h" not in _header(other), other
+        assert other == "orbfi.h" or "orbfi.h" not in header(other), other
     assert "orbfi.hip" in open(os.path.join(ROOT, "monoorbslam3_amd", "csrc", "Makefile")).read()
 
 
 def test_the_defines_equal_the_mirrors_and_the_models(fi):
     from monoorbslam3_amd import vw
-    h = _header()
+    h = header("orbfi.h")
     assert int(re.search(r"#define ORBFI_MAX_KEYFRAMES (\d+) +/\* ORBVW_MAX_SOLVE_STATES - 1", h).group(1)) == vw.MAX_SOLVE_STATES - 1 == fi.MAX_KEYFRAMES == fim.MAX_KEYFRAMES == 31
     assert int(re.search(r"#define ORBFI_EDGE_WORK (\d+)", h).group(1)) == fi.EDGE_WORK == fim.EDGE_WORK
     assert float(re.search(r"#define ORBFI_HUBER_DELTA ([\d.]+)", h).group(1)) == fi.HUBER_DELTA == fim.HUBER_DELTA == 4.1134
@@ -98,36 +86,31 @@ def _calls(fi):
 def test_bad_arguments_are_refused_before_the_device_in_the_documented_order(fi):
     """a null pointer, a negative count, bias_state out of range, a mode outside 0..1, a huber_delta that is not a number, 32 key frames
     refused; an argument error wins over the limit; without a device a valid call fails with ORBX_E_NO_DEVICE"""
-    import torch
     calls = _calls(fi)
     for name, (call, pointers, counts) in calls.items():
         for key in pointers:
-            assert call(**{key: None}) == E_ARG, (name, key)
+            returns(E_ARG, call, **{key: None})
         for key in counts:
-            assert call(**{key: 0}) == E_ARG and call(**{key: -1}) == E_ARG, (name, key)
+            returns(E_ARG, call, **{key: 0}), returns(E_ARG, call, **{key: -1})
         large = dict(n_kf=32) if name == "jobs" else dict(graph=_graph(33), bias_state=32)
         limit = dict(n_kf=31) if name == "jobs" else dict(graph=_graph(32), bias_state=31)
-        assert call(**large) == E_UNSUPPORTED and call(**dict(large, **{pointers[0]: None})) == E_ARG, name     # the argument error first
+        returns(E_UNSUPPORTED, call, **large), returns(E_ARG, call, **dict(large, **{pointers[0]: None}))     # the argument error first
         if name != "jobs":
             for field in ("Rwb", "twb", "v", "bg", "ba", "fixed"):
-                assert call(graph=_graph(6, **{field: None})) == E_ARG, (name, field)
-            assert call(graph=_graph(-1)) == E_ARG and call(bias_state=6) == E_ARG and call(bias_state=-1) == E_ARG, name
-            assert call(bias_state=40, **{k: v for k, v in large.items() if k == "graph"}) == E_ARG, name
-        if not torch.cuda.is_available():
-            assert call() == E_NO_DEVICE and call(**limit) == E_NO_DEVICE, name
+                returns(E_ARG, call, graph=_graph(6, **{field: None}), what=(name, field))
+            returns(E_ARG, call, graph=_graph(-1)), returns(E_ARG, call, bias_state=6), returns(E_ARG, call, bias_state=-1)
+            returns(E_ARG, call, bias_state=40, **{k: v for k, v in large.items() if k == "graph"})
+        returns(E_NO_DEVICE, call), returns(E_NO_DEVICE, call, **limit)
     lin, rec = calls["linearize"][0], calls["recover"][0]
-    assert lin(n_edges=-1) == E_ARG and lin(n_edges=4097) == E_UNSUPPORTED and rec(n=-1) == E_ARG and rec(n=4097) == E_UNSUPPORTED
-    assert lin(mode=2) == E_ARG and lin(mode=-1) == E_ARG and lin(huber=float("nan")) == E_ARG
-    assert lin(mode=1, H_diag=None, b=None, off_edges=None, H_off=None) != E_ARG
-    assert rec(pose_R=None) == E_ARG and rec(pose_t=None) == E_ARG and rec(pose_R=None, pose_t=None) != E_ARG
-    assert fi._L().orbx_last_error()
-    if not torch.cuda.is_available():
-        assert lin(mode=1, H_diag=None, b=None, off_edges=None, H_off=None) == E_NO_DEVICE and lin(n_edges=0) == E_NO_DEVICE
-        assert rec(pose_R=None, pose_t=None) == E_NO_DEVICE and lin(prior_rec=-1) == E_NO_DEVICE and lin(flt=P) == E_NO_DEVICE
+    returns(E_ARG, lin, n_edges=-1), returns(E_UNSUPPORTED, lin, n_edges=4097), returns(E_ARG, rec, n=-1), returns(E_UNSUPPORTED, rec, n=4097)
+    returns(E_ARG, lin, mode=2), returns(E_ARG, lin, mode=-1), returns(E_ARG, lin, huber=float("nan"))
+    returns(E_ARG, rec, pose_R=None), returns(E_ARG, rec, pose_t=None)
+    # what is optional is optional: still the device that is missing, not an argument (with a device: tests/test_full_inertial_gpu.py)
+    returns(E_NO_DEVICE, lin, mode=1, H_diag=None, b=None, off_edges=None, H_off=None), returns(E_NO_DEVICE, lin, n_edges=0)
+    returns(E_NO_DEVICE, rec, pose_R=None, pose_t=None), returns(E_NO_DEVICE, lin, prior_rec=-1), returns(E_NO_DEVICE, lin, flt=P)
 
 
 def test_the_documents_name_what_is_built():
-    flat = lambda path: re.sub(r"\s*\n( \*)?\s*", " ", open(os.path.join(ROOT, path)).read())  # noqa: E731
     design, integration, readme = flat("DESIGN.md"), flat("INTEGRATION.md"), flat("README.md")
     for name in ENTRY_POINTS:
         assert name in design and name in integration, name

@@ -1,6 +1,6 @@
 """Kernel resources of the fuse's hit handling, read from the gfx950 ISA that hipcc emits for the shipped source (no GPU needed), by
 the method of tests/test_kernel_resources.py: what include/orbm.h states for it."""
-from test_kernel_resources import _isa, _kernels
+from resource_checks import _isa, _kernels
 
 
 def test_the_fuse_kernel_uses_no_scratch_memory_and_fits_sixteen_waves():

@@ -3,52 +3,36 @@ orbm_apply_scale_rotation_device, is exported by the built library and bound by 
 model's; bad arguments are refused before the device is looked for, in the documented order (ORBX_E_ARG, then ORBX_E_UNSUPPORTED, then
 ORBX_E_NO_DEVICE); the places that said "not built" name what is built now."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
 import imu_init_model as mm
+from abi_checks import E_ARG, E_NO_DEVICE, E_UNSUPPORTED, P, built, declared, exported, exported_and_mirrored, flat, header, returns, stripped
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_ARG, E_NO_DEVICE, E_UNSUPPORTED = -1, -2, -4
 ENTRY_POINTS = ["orbii_prior_device", "orbii_graph_init_device", "orbii_linearize_device", "orbii_damp_device", "orbii_oplus_device", "orbii_recover_device"]
-P = 0x1000                # a fake device pointer: never dereferenced, every call below fails before a launch
 
 
 @pytest.fixture(scope="module")
 def ii():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import imu_init
-    return imu_init
-
-
-def _header(name="orbii.h"):
-    return open(os.path.join(ROOT, "include", name)).read()
+    return built("imu_init")
 
 
 def test_every_declared_entry_point_is_exported_and_mirrored(ii):
-    from monoorbslam3_amd import _lib, imu, matcher
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(orbii_[a-z0-9_]+)\s*\(", txt))
-    assert declared == set(ENTRY_POINTS), sorted(declared)
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in sorted(declared):
-        assert hasattr(L, n), "liborbx.so does not export %s" % n
-        assert n in ii._SIGS and callable(getattr(ii, n[len("orbii_"):])), n
-    assert set(ii._SIGS) == declared
-    ii._L()                                                     # binds every name of _SIGS or raises
-    assert ii._L() is _lib.lib() and ii.Calib is imu.Calib and C.sizeof(ii.Graph) == 64 and C.sizeof(ii.Bias) == 24
-    assert '#include "orbi.h"' in txt
-    m = re.sub(r"/\*.*?\*/", "", _header("orbm.h"), flags=re.S)
-    assert "orbm_apply_scale_rotation_device" in set(re.findall(r"\b(orbm_[a-z0-9_]+)\s*\(", m)) and hasattr(L, "orbm_apply_scale_rotation_device")
+    from monoorbslam3_amd import imu, matcher
+    names = declared("orbii_", "orbii.h")
+    assert names == set(ENTRY_POINTS), sorted(names)
+    exported_and_mirrored(ii, "orbii_", names, sigs_equal=True)
+    assert ii.Calib is imu.Calib and C.sizeof(ii.Graph) == 64 and C.sizeof(ii.Bias) == 24
+    assert '#include "orbi.h"' in stripped("orbii.h")
+    assert "orbm_apply_scale_rotation_device" in declared("orbm_", "orbm.h")
+    exported(["orbm_apply_scale_rotation_device"])
     fn = matcher._mlib().orbm_apply_scale_rotation_device
     assert len(fn.argtypes) == 20 and fn.restype is C.c_int and callable(matcher.ORBMatcher.ApplyScaleRotationDevice) and callable(matcher.apply_scale_rotation_device)
 
 
 def test_the_defines_equal_the_mirrors_and_the_models(ii):
-    defines = dict(re.findall(r"#define (ORBII_[A-Z_]+) (\d+)", _header()))
+    defines = dict(re.findall(r"#define (ORBII_[A-Z_]+) (\d+)", header("orbii.h")))
     assert defines == {"ORBII_MAX_KF": "157", "ORBII_EDGE_WORK": "240", "ORBII_KIND_GS": "0", "ORBII_KIND_G": "1", "ORBII_SHARED_BG": "0",
                        "ORBII_SHARED_BA": "3", "ORBII_SHARED_RWG": "6", "ORBII_SHARED_SCALE": "15", "ORBII_SUMMARY": "10"}
     for name, value in defines.items():
@@ -114,32 +98,28 @@ def _calls(ii):
 def test_bad_arguments_are_refused_before_the_device_in_the_documented_order(ii):
     """null pointers, n_kf 1 and 158, kind 2, mode 2; an argument error wins over the limit; without a device a valid call fails with
     ORBX_E_NO_DEVICE"""
-    import torch
     calls = _calls(ii)
     for name, (call, pointers, counts) in calls.items():
         for key in pointers:
-            assert call(**{key: None}) == E_ARG, (name, key)
+            returns(E_ARG, call, **{key: None})
         for key in counts:
-            assert call(**{key: 0}) == E_ARG and call(**{key: -1}) == E_ARG, (name, key)
+            returns(E_ARG, call, **{key: 0}), returns(E_ARG, call, **{key: -1})
         small, large = (dict(n=1), dict(n=158)) if name == "prior" else (dict(n_kf=1), dict(n_kf=158)) if name == "damp" else (dict(graph=_graph(ii, 1)), dict(graph=_graph(ii, 158)))
-        assert call(**small) == E_ARG and call(**large) == E_UNSUPPORTED, name
-        assert call(**dict(large, **{pointers[0]: None})) == E_ARG, name                      # the argument error first
+        returns(E_ARG, call, **small), returns(E_UNSUPPORTED, call, **large)
+        returns(E_ARG, call, **dict(large, **{pointers[0]: None}))                            # the argument error first
         if name not in ("prior", "damp"):
             for field in ("v", "shared", "iter", "Rwb", "twb", "Oc", "Pcb"):
-                assert call(graph=_graph(ii, 6, **{field: None})) == E_ARG, (name, field)
+                returns(E_ARG, call, graph=_graph(ii, 6, **{field: None}), what=(name, field))
         if name in ("linearize", "damp", "oplus"):
-            assert call(kind=2) == E_ARG and call(kind=-1) == E_ARG and call(kind=2, **large) == E_ARG, name
-        if not torch.cuda.is_available():
-            assert call() == E_NO_DEVICE, name
+            returns(E_ARG, call, kind=2), returns(E_ARG, call, kind=-1), returns(E_ARG, call, kind=2, **large)
+        returns(E_NO_DEVICE, call)
     lin = calls["linearize"][0]
-    assert lin(mode=2) == E_ARG and lin(mode=-1) == E_ARG and lin(mode=1, H=None, b=None) != E_ARG and lin(mode=0, H=None) == E_ARG
-    assert ii._L().orbx_last_error()
-    if not torch.cuda.is_available():
-        assert lin(mode=1, H=None, b=None) == E_NO_DEVICE and calls["init"][0](Rwg=P) == E_NO_DEVICE and calls["prior"][0](n=157) == E_NO_DEVICE
+    returns(E_ARG, lin, mode=2), returns(E_ARG, lin, mode=-1), returns(E_ARG, lin, mode=0, H=None)
+    # mode 1 takes no H and no b: still the device that is missing, not an argument (with a device: tests/test_imu_init_gpu.py)
+    returns(E_NO_DEVICE, lin, mode=1, H=None, b=None), returns(E_NO_DEVICE, calls["init"][0], Rwg=P), returns(E_NO_DEVICE, calls["prior"][0], n=157)
 
 
 def test_the_rescale_checks_its_arguments_before_any_device_call(ii):
-    import torch
     from monoorbslam3_amd import imu, matcher
     L = matcher._mlib()
     cal = imu.Calib.make([1, 0, 0, 0, 1, 0, 0, 0, 1], [0, 0, 0], [1] * 6, [1] * 6)
@@ -152,17 +132,15 @@ def test_the_rescale_checks_its_arguments_before_any_device_call(ii):
                                                   a["n_priors"], a["points"], a["valid"], a["n_points"], a["cap_points"], a["summary"], 1, 0.1, a["result"], None)
 
     for key in ("calib", "pose_R", "pose_t", "bad", "kf_imu", "state", "priors", "points", "valid", "n_points", "summary", "result"):
-        assert call(**{key: None}) == E_ARG, key
+        returns(E_ARG, call, **{key: None})
     for key in ("n_kf", "n_src", "n_priors", "cap_points"):
-        assert call(**{key: -1}) == E_ARG, key
-    assert call(cap_points=524289) == E_UNSUPPORTED and call(cap_points=524289, summary=None) == E_ARG
-    if not torch.cuda.is_available():
-        assert call() == E_NO_DEVICE and call(n_kf=0, pose_R=None, bad=None) == E_NO_DEVICE and call(cap_points=0, points=None, valid=None) == E_NO_DEVICE
+        returns(E_ARG, call, **{key: -1})
+    returns(E_UNSUPPORTED, call, cap_points=524289), returns(E_ARG, call, cap_points=524289, summary=None)
+    returns(E_NO_DEVICE, call), returns(E_NO_DEVICE, call, n_kf=0, pose_R=None, bad=None), returns(E_NO_DEVICE, call, cap_points=0, points=None, valid=None)
 
 
 def test_the_not_built_sentences_name_what_is_built():
     """DESIGN.md said three times that the IMU initialisation was not built; it names the new calls now and records what is still open"""
-    flat = lambda path: re.sub(r"\s*\n( \*)?\s*", " ", open(os.path.join(ROOT, path)).read())  # noqa: E731
     design = flat("DESIGN.md")
     for name in ENTRY_POINTS + ["orbm_apply_scale_rotation_device"]:
         assert name in design, name
@@ -174,4 +152,4 @@ def test_the_not_built_sentences_name_what_is_built():
         assert "orbii_linearize_device" in flat(path) and "orbm_apply_scale_rotation_device" in flat(path), path
     assert "orbvw_solve_device" in flat("INTEGRATION.md") and "IMU initialisation as a chain on one stream" in flat("INTEGRATION.md")
     for name in ("orbii.h",):                                   # the header describes the solve's layout without naming the call
-        assert "orbvw" not in _header(name) and "orbvi" not in _header(name)
+        assert "orbvw" not in header(name) and "orbvi" not in header(name)

@@ -1,13 +1,8 @@
 """Kernel resources of the IMU initialisation's steps (csrc/orbii.hip) and of the map rescale (csrc/orbm_rescale.hip), read from the gfx950
 ISA that hipcc emits for the shipped sources (no GPU needed), by the method of tests/test_vi_resources.py: what include/orbii.h and
 include/orbm.h state.  Nothing else is read from the ISA."""
-import os
-import re
+from resource_checks import defined_once, source, stated, used_not_defined
 
-from test_kernel_resources import _isa, _kernels
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monoorbslam3_amd", "csrc")
 # kernel (substring of the mangled name) -> (static LDS bytes as the header states them, threads of its workgroup)
 STATED = {
     "orbii": ("orbii.h", {"k_ii_prior": (5748, 64), "k_ii_init": (256, 256), "k_ii_edge": (20608, 256), "k_ii_assemble": (0, 256), "k_ii_damp": (0, 256),
@@ -23,17 +18,9 @@ def test_the_kernels_use_no_scratch_memory_and_the_lds_the_headers_state():
     k_ii_recover hold the 256 bytes of their workgroup count."""
     assert STATED["orbii"][1]["k_ii_edge"][0] == 4 * (574 * 8 + 140 * 4) and STATED["orbii"][1]["k_ii_prior"][0] == 157 * 9 * 4 + (8 + 3 + 9) * 4 + 16
     assert STATED["orbm_rescale"][1]["k_rescale_kf"][0] == 4 * 48 * 4
-    for src, (header_name, stated) in STATED.items():
-        k = _kernels(_isa(src))
-        header = re.sub(r"\s*\n \* +", " ", open(os.path.join(ROOT, "include", header_name)).read())
-        assert len(k) == len(stated), sorted(k)
-        for key, (lds_stated, threads) in stated.items():
-            mangled = [m for m in k if key in m]
-            assert len(mangled) == 1, (key, sorted(k))
-            vgpr, scratch, lds = k[mangled[0]]
-            print(key, "VGPRs", vgpr, "scratch", scratch, "static LDS", lds)
-            assert scratch == 0 and vgpr <= 128 and threads in (64, 256) and lds == lds_stated
-            assert "%s %d / 0 / %d B" % (key, vgpr, lds) in header, key
+    for src, (header_name, table) in STATED.items():
+        assert all(threads in (64, 256) for _, threads in table.values())
+        stated(src, header_name, {key: lds for key, (lds, _) in table.items()}, 128)
 
 
 def test_the_so3_code_is_written_once():
@@ -42,24 +29,22 @@ def test_the_so3_code_is_written_once():
     both take ExpSO3 from there, the float part of an edge (bias_deltas) from csrc/orbi_so3.h and the duplicate scan over a job list from
     csrc/orbi_graph_device.h; orbm_rescale.hip and orbi_imu.hip take T_wb = T_cw.inverse() * T_cb from orbi_so3.h.  None defines them
     itself, and no scan is written out."""
-    d, f = open(os.path.join(CSRC, "orbi_so3d.h")).read(), open(os.path.join(CSRC, "orbi_so3.h")).read()
-    e, g = open(os.path.join(CSRC, "orbi_edge.h")).read(), open(os.path.join(CSRC, "orbi_graph_device.h")).read()
+    d, f, e, g = source("orbi_so3d.h"), source("orbi_so3.h"), source("orbi_edge.h"), source("orbi_graph_device.h")
     for fn in ("dlog_so3", "dright_jacobian", "dinverse_right_jacobian", "dexp_so3", "dnormalize", "dm3", "dcof"):
-        assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, d, re.M)) == 1, fn
+        assert defined_once(d, fn), fn
     for fn in ("bias_deltas", "imu_pose_from_camera"):
-        assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, f, re.M)) == 1, fn
+        assert defined_once(f, fn), fn
     edge_fns = ("edge_refused", "edge_load", "edge_widen", "edge_rotation", "edge_chi2", "edge_jtwj", "edge_quadratic_form")
     for fn in edge_fns:
-        assert len(re.findall(r"^__device__ __forceinline__ \w+ %s\(" % fn, e, re.M)) == 1, fn
-    assert len(re.findall(r"^__device__ __forceinline__ \w+ job_named_before\(", g, re.M)) == 1
+        assert defined_once(e, fn), fn
+    assert defined_once(g, "job_named_before")
     for src, header, fns in (("orbi_edge.h", "orbi_so3d.h", ("dlog_so3", "dright_jacobian", "dinverse_right_jacobian")),
                              ("orbii.hip", "orbi_so3d.h", ("dexp_so3", "bias_deltas")), ("orbi_factors.hip", "orbi_so3d.h", ("dexp_so3", "bias_deltas")),
                              ("orbii.hip", "orbi_edge.h", [fn for fn in edge_fns if fn != "edge_jtwj"]), ("orbi_factors.hip", "orbi_edge.h", edge_fns),
                              ("orbii.hip", "orbi_graph_device.h", ("job_named_before",)), ("orbi_factors.hip", "orbi_graph_device.h", ("job_named_before",)),
                              ("orbm_rescale.hip", "orbi_so3.h", ("imu_pose_from_camera",)), ("orbi_imu.hip", "orbi_so3.h", ("imu_pose_from_camera",))):
-        text = open(os.path.join(CSRC, src)).read()
+        text = source(src)
         assert '#include "%s"' % header in text, src
         for fn in fns:
-            assert re.search(r"\b%s(?:<\d+>)?\(" % fn, text), (src, fn)
-            assert not re.search(r"^\s*(?:__device__ |static |inline )[\w ]*\b%s\(" % fn, text, re.M), (src, fn)
-    assert "orbii.hip" in open(os.path.join(CSRC, "Makefile")).read()
+            assert used_not_defined(text, fn), (src, fn)
+    assert "orbii.hip" in source("Makefile")

@@ -1,8 +1,6 @@
 """Kernel resources of the IMU preintegration and pose prediction, read from the gfx950 ISA that hipcc emits for the shipped source (no
 GPU needed), by the method of tests/test_keyframe_resources.py: what include/orbi.h states for them."""
-import re
-
-from test_kernel_resources import _isa, _kernels
+from resource_checks import stated
 
 # kernel (substring of the mangled name) -> (the header's name for it, static LDS bytes as include/orbi.h states them)
 STATED = {"k_imuILi0E": ("k_imu<reset>", 32), "k_imuILi1E": ("k_imu<integrate>", 12368), "k_imuILi2E": ("k_imu<set_bias>", 12368),
@@ -15,14 +13,4 @@ def test_the_imu_kernels_use_no_scratch_memory_and_the_lds_the_header_states():
     SIMD: nothing competes for the register file, but a spill would put the record's matrices behind global memory); static LDS as
     stated: four wave slices of 768 words (the record's image, the 9x9 intermediate, thirteen 3x3 temporaries, 33 staged samples), the
     calibration's twelve floats and the eight counters.  No dynamic LDS."""
-    k = _kernels(_isa("orbi_imu"))
-    header = open(__file__.replace("tests/test_imu_resources.py", "include/orbi.h")).read()
-    header = re.sub(r"\s*\n \* ", " ", header)                       # the comment's line breaks
-    assert len(k) == len(STATED), sorted(k)
-    for key, (name, lds_stated) in STATED.items():
-        mangled = [m for m in k if key in m]
-        assert len(mangled) == 1, (key, sorted(k))
-        vgpr, scratch, lds = k[mangled[0]]
-        print(name, "VGPRs", vgpr, "scratch", scratch, "static LDS", lds)
-        assert scratch == 0 and vgpr <= 128 and lds == lds_stated
-        assert "%s %d / 0 / %d B" % (name, vgpr, lds) in header, name
+    stated("orbi_imu", "orbi.h", STATED, 128, breaks=r"\s*\n \* ")

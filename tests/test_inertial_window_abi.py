@@ -2,17 +2,14 @@
 the limits equal to the visual-window module's, every argument error reported before the device is looked for, the limits, and
 ORBX_E_NO_DEVICE without a GPU.  No GPU."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
 import inertial_window_model as wm
+from abi_checks import E_ARG, E_NO_DEVICE, E_UNSUPPORTED, P, built, declared, flat, header, returns
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("orbm_inertial_window_problem_device", "orbm_inertial_window_velocity_prior_device")
-P = 0x1000                # a fake device pointer: never dereferenced, every call below fails before a launch
-E_ARG, E_NO_DEVICE, E_UNSUPPORTED = -1, -2, -4
 POINTERS = ("slots", "valid", "points", "obs_off", "obs_kf", "obs_kp", "window", "kf_imu", "work", "ba_points", "point_row", "edge_off", "edge_state",
             "edge_point", "edge_z", "edge_inv_sigma2", "edge_kf", "edge_kp", "state_kf", "init_jobs", "fixed", "inertial_edges", "prior_jobs",
             "recover_jobs", "bias_ids", "prior_info_jobs", "result")
@@ -20,22 +17,15 @@ POINTERS = ("slots", "valid", "points", "obs_off", "obs_kf", "obs_kp", "window",
 
 @pytest.fixture(scope="module")
 def mlib():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import matcher
+    matcher = built("matcher")
     return matcher._mlib(), matcher
-
-
-def _header():
-    return open(os.path.join(ROOT, "include", "orbm.h")).read()
 
 
 def test_the_header_declares_the_entry_points_and_the_library_exports_them(mlib):
     L, matcher = mlib
-    txt = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(orbm_[a-z0-9_]+)\s*\(", txt))
+    names = declared("orbm_", "orbm.h")
     for name in NAMES:
-        assert name in declared, name
+        assert name in names, name
         fn = getattr(L, name)
         assert fn.argtypes is not None and fn.argtypes[0] is C.c_void_p and fn.restype is C.c_int, name
     assert len(L.orbm_inertial_window_problem_device.argtypes) == 41 and len(L.orbm_inertial_window_velocity_prior_device.argtypes) == 9
@@ -48,11 +38,11 @@ def test_the_limits_equal_the_visual_window_modules_and_the_flags_the_inertial_m
     """orbm.h does not include the headers whose calls take its outputs, so it names its limits itself: they must be those"""
     _, matcher = mlib
     from monoorbslam3_amd import imu, vw
-    defines = dict(re.findall(r"#define (ORBM_IW_[A-Z_]+) (\d+)", _header()))
+    defines = dict(re.findall(r"#define (ORBM_IW_[A-Z_]+) (\d+)", header("orbm.h")))
     assert defines == {"ORBM_IW_MAX_SOLVE": "32", "ORBM_IW_MAX_FIXED_DEFAULT": "150"}
     assert int(defines["ORBM_IW_MAX_SOLVE"]) == vw.MAX_SOLVE_STATES == matcher.IW_MAX_SOLVE == wm.MAX_SOLVE
     assert int(defines["ORBM_IW_MAX_FIXED_DEFAULT"]) == matcher.IW_MAX_FIXED_DEFAULT == wm.MAX_FIXED_DEFAULT == 150   # Optimize.cpp:1095
-    assert wm.MAX_OBS == vw.MAX_OBS == 256 and "more than 256 kept edges" in re.sub(r"\s*\n \*\s+", " ", _header())
+    assert wm.MAX_OBS == vw.MAX_OBS == 256 and "more than 256 kept edges" in flat("include/orbm.h")
     assert wm.FIX_ALL == imu.FIX_POSE | imu.FIX_VELO | imu.FIX_GYRO | imu.FIX_ACC and wm.EDGE_WALKS == imu.EDGE_WALKS
     assert wm.PRIOR_ALL == imu.PRIOR_VELO | imu.PRIOR_GYRO | imu.PRIOR_ACC | imu.PRIOR_ACC_GYRO_INFO and wm.RECOVER_POSE == imu.RECOVER_POSE
 
@@ -60,7 +50,7 @@ def test_the_limits_equal_the_visual_window_modules_and_the_flags_the_inertial_m
 def test_the_three_not_built_sentences_point_to_the_section():
     """the visual-window header, DESIGN.md and INTEGRATION.md said that assembling the window from the device-resident map was not built"""
     for path in ("include/orbvw.h", "DESIGN.md", "INTEGRATION.md", "README.md"):
-        txt = re.sub(r"\s*\n( \*)?\s*", " ", open(os.path.join(ROOT, path)).read())
+        txt = flat(path)
         assert "orbm_inertial_window_problem_device" in txt, path
         assert "Not here either: assembling this problem from the device-resident map" not in txt, path
 
@@ -95,24 +85,28 @@ def test_the_entry_points_check_their_arguments_before_any_device_call(mlib):
     """every ORBX_E_ARG and ORBX_E_UNSUPPORTED case of the section, returned with a NULL handle and fake pointers: before the device is
     asked for; an argument error wins over a limit; without a device a valid call fails with ORBX_E_NO_DEVICE"""
     L, matcher = mlib
-    import torch
+
+    def problem(**over):
+        return _problem(L, matcher, **over)
+
+    def velocity(**over):
+        return _velocity(L, **over)
+
     for key in POINTERS:
-        assert _problem(L, matcher, **{key: None}) == E_ARG, key
-    assert _problem(L, matcher, kf=None) == E_ARG
+        returns(E_ARG, problem, **{key: None})
+    returns(E_ARG, problem, kf=None)
     for field in ("bad", "kps", "n"):
-        assert _problem(L, matcher, kf=_kf(matcher, **{field: None})) == E_ARG, field
-    assert _problem(L, matcher, kf=_kf(matcher, n_kf=-1)) == E_ARG and _problem(L, matcher, kf=_kf(matcher, kps=P + 4)) == E_ARG
+        returns(E_ARG, problem, kf=_kf(matcher, **{field: None}), what=field)
+    returns(E_ARG, problem, kf=_kf(matcher, n_kf=-1)), returns(E_ARG, problem, kf=_kf(matcher, kps=P + 4))
     for key in ("stride", "cap_points", "n_obs", "n_src", "cap_bank", "n_priors"):
-        assert _problem(L, matcher, **{key: -1}) == E_ARG, key
+        returns(E_ARG, problem, **{key: -1})
     for key in ("n_window", "max_fixed", "cap_states", "cap_local_points", "cap_edges"):
-        assert _problem(L, matcher, **{key: 0}) == E_ARG and _problem(L, matcher, **{key: -3}) == E_ARG, key
-    assert _problem(L, matcher, n_window=33, cap_edges=0) == E_ARG and _problem(L, matcher, stride=8193, work=None) == E_ARG   # the argument error first
-    assert _problem(L, matcher, n_window=33) == E_UNSUPPORTED and _problem(L, matcher, stride=8193) == E_UNSUPPORTED
-    assert _problem(L, matcher, cap_points=524289) == E_UNSUPPORTED and L.orbx_last_error()
+        returns(E_ARG, problem, **{key: 0}), returns(E_ARG, problem, **{key: -3})
+    returns(E_ARG, problem, n_window=33, cap_edges=0), returns(E_ARG, problem, stride=8193, work=None)   # the argument error first
+    returns(E_UNSUPPORTED, problem, n_window=33), returns(E_UNSUPPORTED, problem, stride=8193), returns(E_UNSUPPORTED, problem, cap_points=524289)
     for key in ("priors", "src", "recover_jobs", "prior_jobs", "result"):
-        assert _velocity(L, **{key: None}) == E_ARG, key
-    assert _velocity(L, n_priors=-1) == E_ARG and _velocity(L, n_src=-1) == E_ARG
-    if not torch.cuda.is_available():
-        assert _problem(L, matcher) == E_NO_DEVICE and _problem(L, matcher, n_window=32, stride=8192, cap_points=524288) == E_NO_DEVICE
-        assert _problem(L, matcher, n_window=1, max_fixed=1) == E_NO_DEVICE and _problem(L, matcher, kf=_kf(matcher, pose_R=None, pose_t=None, desc=None)) == E_NO_DEVICE
-        assert _velocity(L) == E_NO_DEVICE and _velocity(L, n_priors=0, n_src=0) == E_NO_DEVICE
+        returns(E_ARG, velocity, **{key: None})
+    returns(E_ARG, velocity, n_priors=-1), returns(E_ARG, velocity, n_src=-1)
+    returns(E_NO_DEVICE, problem), returns(E_NO_DEVICE, problem, n_window=32, stride=8192, cap_points=524288)
+    returns(E_NO_DEVICE, problem, n_window=1, max_fixed=1), returns(E_NO_DEVICE, problem, kf=_kf(matcher, pose_R=None, pose_t=None, desc=None))
+    returns(E_NO_DEVICE, velocity), returns(E_NO_DEVICE, velocity, n_priors=0, n_src=0)

@@ -1,8 +1,6 @@
 """Kernel resources of the inertial window's assembly and its velocity prior, read from the gfx950 ISA that hipcc emits for the shipped
 source (no GPU needed), by the method of tests/test_keyframe_resources.py: what include/orbm.h states for them."""
-import re
-
-from test_kernel_resources import _isa, _kernels
+from resource_checks import stated
 
 # kernel -> static LDS bytes, as include/orbm.h states them
 STATED = {"k_iw_problem": 320, "k_iw_velocity_prior": 0}
@@ -12,14 +10,4 @@ def test_the_inertial_window_kernels_use_no_scratch_memory_and_the_resources_the
     """Two kernels, the ones the header names.  No scratch memory; within 64 VGPRs (the assembly is a workgroup of sixteen waves: 128 is
     all a thread could have); static LDS as stated: the window's 32 key frames, 2 x 16 wave totals and sixteen counters in the assembly,
     none in the velocity prior; the VGPRs the compiler gives are the ones the header prints."""
-    k = _kernels(_isa("orbm_inertial_window"))
-    header = open(__file__.replace("tests/test_inertial_window_resources.py", "include/orbm.h")).read()
-    header = re.sub(r"\s*\n \* ", " ", header)                       # the comment's line breaks
-    assert len(k) == len(STATED), sorted(k)
-    for name, lds_stated in STATED.items():
-        mangled = [m for m in k if name in m]
-        assert len(mangled) == 1, (name, sorted(k))
-        vgpr, scratch, lds = k[mangled[0]]
-        print(name, "VGPRs", vgpr, "scratch", scratch, "static LDS", lds)
-        assert scratch == 0 and vgpr <= 64 and lds == lds_stated
-        assert "%s %d / 0 / %d B" % (name, vgpr, lds) in header, name
+    stated("orbm_inertial_window", "orbm.h", STATED, 64, breaks=r"\s*\n \* ")

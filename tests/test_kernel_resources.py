@@ -1,18 +1,9 @@
 """Register / scratch budgets of the kernels whose occupancy the measured numbers depend on, read from the gfx950 ISA that
 hipcc emits for the shipped sources (no GPU needed).  A few more VGPRs are invisible in a diff and cost a whole workgroup per CU:
 the batch quadtree went from four to three workgroups per CU (0.23 -> 0.27 ms per 512 frames) on a 125 -> 133 VGPR step."""
-import hashlib
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "monoorbslam3_amd", "csrc")
-FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "--offload-arch=gfx950", "-mllvm",
-         "-amdgpu-mfma-vgpr-form=1", "--cuda-device-only", "-S"]
+from resource_checks import _isa, _kernels
 
 # kernel (substring of the mangled name) -> (max VGPRs, max scratch bytes, why)
 BUDGET = {
@@ -27,34 +18,6 @@ BUDGET = {
     "k_orientILb0E": (64, 0, "8 waves per SIMD"),
     "k_blur_mfmaILi256": (96, 0, "5 waves per SIMD"),
 }
-
-
-def _isa(source="orbx_kernels"):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not found")
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(CSRC)):
-        if f.endswith((".hip", ".h")):
-            h.update(open(os.path.join(CSRC, f), "rb").read())
-    out_dir = os.path.join(ROOT, "build", "isa")
-    os.makedirs(out_dir, exist_ok=True)
-    out = os.path.join(out_dir, "%s_%s.s" % (source, h.hexdigest()[:16]))
-    if not os.path.exists(out):
-        subprocess.run([hipcc] + FLAGS + ["-o", out, os.path.join(CSRC, source + ".hip")], check=True, cwd=CSRC,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    return open(out).read()
-
-
-def _kernels(isa):
-    """mangled name -> (VGPRs, scratch bytes, static LDS bytes)"""
-    out = {}
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", isa, re.S):
-        body = m.group(2)
-        out[m.group(1)] = (int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)),
-                           int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)),
-                           int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1)))
-    return out
 
 
 def test_occupancy_critical_kernels_stay_within_their_register_budgets():

@@ -1,9 +1,7 @@
 """Kernel resources of the key-frame insertion, the registration of new map points and the map-point culling, read from the gfx950 ISA
 that hipcc emits for the shipped source (no GPU needed), by the method of tests/test_local_map_resources.py: what include/orbm.h states
 for them."""
-import re
-
-from test_kernel_resources import _isa, _kernels
+from resource_checks import stated
 
 # kernel -> static LDS bytes, as include/orbm.h states them
 STATED = {"k_kf_insert": 32, "k_kf_register": 0, "k_kf_cull_points": 352}
@@ -13,14 +11,4 @@ def test_the_keyframe_kernels_use_no_scratch_memory_and_the_lds_the_header_state
     """Three kernels, the ones the header names.  No scratch memory anywhere; within 64 VGPRs (each is a workgroup of sixteen waves: 128
     is all a thread could have); static LDS as stated: the eight counters, and in k_kf_cull_points also the scan's sixteen slots and the
     words of the workgroup-wide `or` behind the premise's test.  The masks of one bit per table row are dynamic LDS."""
-    k = _kernels(_isa("orbm_keyframe"))
-    header = open(__file__.replace("tests/test_keyframe_resources.py", "include/orbm.h")).read()
-    header = re.sub(r"\s*\n \* ", " ", header)                       # the comment's line breaks
-    assert len(k) == len(STATED), sorted(k)
-    for name, lds_stated in STATED.items():
-        mangled = [m for m in k if name in m]
-        assert len(mangled) == 1, (name, sorted(k))
-        vgpr, scratch, lds = k[mangled[0]]
-        print(name, "VGPRs", vgpr, "scratch", scratch, "static LDS", lds)
-        assert scratch == 0 and vgpr <= 64 and lds == lds_stated
-        assert "%s %d / 0 / %d B" % (name, vgpr, lds) in header, name
+    stated("orbm_keyframe", "orbm.h", STATED, 64, breaks=r"\s*\n \* ")

@@ -1,6 +1,6 @@
 """Kernel resources of the local bundle adjustment's assembly and apply, read from the gfx950 ISA that hipcc emits for the shipped source
 (no GPU needed), by the method of tests/test_fuse_resources.py: what include/orbm.h states for them."""
-from test_kernel_resources import _isa, _kernels
+from resource_checks import _isa, _kernels
 
 
 def test_the_local_ba_kernels_use_no_scratch_memory_and_fit_sixteen_waves():

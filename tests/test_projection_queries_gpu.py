@@ -199,7 +199,7 @@ def test_drop_outliers_alone():
 
 def test_the_new_kernels_use_no_scratch_memory():
     """read from the gfx950 ISA under build/isa, by the method of tests/test_kernel_resources.py"""
-    from test_kernel_resources import _isa, _kernels
+    from resource_checks import _isa, _kernels
     k = _kernels(_isa("orbm_project"))
     proj = {name: v for name, v in k.items() if "k_project" in name}
     assert len(proj) == 3, sorted(k)

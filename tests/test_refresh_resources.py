@@ -1,6 +1,6 @@
 """Kernel resources of the refresh kernels, read from the gfx950 ISA that hipcc emits for the shipped source (no GPU needed), by the
 method of tests/test_kernel_resources.py."""
-from test_kernel_resources import _isa, _kernels
+from resource_checks import _isa, _kernels
 
 
 def test_refresh_kernels_use_no_scratch_memory():

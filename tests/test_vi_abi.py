@@ -2,40 +2,26 @@
 is exported by the built library and resolved by monoorbslam3_amd.vi; the layouts and constants are the header's; bad arguments are
 reported before the device is looked for; without a GPU every call fails with ORBX_E_NO_DEVICE; orbi.h does not include orbvi.h."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
 import vi_model as vm
+from abi_checks import E_ARG, E_NO_DEVICE, E_UNSUPPORTED, P, built, declared, exported_and_mirrored, header, returns, stripped
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_ARG, E_NO_DEVICE, E_UNSUPPORTED = -1, -2, -4
 ENTRY_POINTS = ["orbvi_linearize_device", "orbvi_solve_device"]
 
 
 @pytest.fixture(scope="module")
 def vi():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import vi
-    return vi
-
-
-def _header(name):
-    return open(os.path.join(ROOT, "include", name)).read()
+    return built("vi")
 
 
 def test_every_declared_entry_point_is_exported_and_mirrored(vi):
-    from monoorbslam3_amd import _lib, imu
-    txt = re.sub(r"/\*.*?\*/", "", _header("orbvi.h"), flags=re.S)
-    declared = set(re.findall(r"\b(orbvi_[a-z0-9_]+)\s*\(", txt))
-    assert declared == set(ENTRY_POINTS), sorted(declared)
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in sorted(declared):
-        assert hasattr(L, n), "liborbx.so does not export %s" % n
-        assert n in vi._SIGS and callable(getattr(vi, n[len("orbvi_"):])), n
-    vi._L()                                                     # binds every name of _SIGS or raises
+    from monoorbslam3_amd import imu
+    txt, names = stripped("orbvi.h"), declared("orbvi_", "orbvi.h")
+    assert names == set(ENTRY_POINTS), sorted(names)
+    exported_and_mirrored(vi, "orbvi_", names, sigs_equal=False)
     assert C.sizeof(vi.Camera) == 72 and vi.Graph is imu.Graph and vi.Calib is imu.Calib and C.sizeof(vi.Graph) == 56
     header = re.sub(r"\s+", " ", txt)
     for name, value in [("ORBVI_MAX_STATES", vi.MAX_STATES), ("ORBVI_EDGE_WORK", vi.EDGE_WORK), ("ORBVI_R_NONFINITE", vi.R_NONFINITE)]:
@@ -82,12 +68,12 @@ def test_the_binder_binds_once_and_a_missing_symbol_raises(vi):
 
 def test_orbi_h_still_does_not_include_orbvi_h():
     for name in ("orbi.h", "orbi_factors.h", "orbx.h", "orbba.h"):
-        assert "orbvi" not in _header(name), name
+        assert "orbvi" not in header(name), name
 
 
 def _calls(vi, **over):
-    """both wrappers with valid arguments (fake device addresses, never dereferenced) except for `over`"""
-    p = 0x1000
+    """both wrappers with valid arguments (the fake device address) except for `over`"""
+    p = P
     a = dict(Rwb=p, twb=p, v=p, bg=p, ba=p, fixed=p, n_states=2, n_groups=1, cap_edges=400, group_state=p, edge_off=p, points=p, z=p, w=p,
              active=p, delta=vm.HUBER_MONO, threshold=vm.CHI2_MONO, mode=0, work=p, err=p, chi2=p, total=p, H_diag=p, b=p, n_inliers=p, result=p,
              camera_model=0, edges=p, n_edges=1, cap=4, H_off=p, lam=p, dx=p, out=p)
@@ -105,13 +91,6 @@ def _calls(vi, **over):
                                       a["dx"], a["out"], a["result"]))
 
 
-def _code(call):
-    from monoorbslam3_amd._lib import OrbxError
-    with pytest.raises(OrbxError) as e:
-        call()
-    return e.value.code
-
-
 def test_argument_errors_are_reported_before_the_device_is_looked_for(vi):
     both, lin, sol = ("linearize", "solve"), ("linearize",), ("solve",)
     cases = [(dict(result=None), both), (dict(fixed=None), both), (dict(H_diag=None), both), (dict(b=None), both), (dict(n_states=-1), both)]
@@ -123,25 +102,20 @@ def test_argument_errors_are_reported_before_the_device_is_looked_for(vi):
     cases += [(dict(n_edges=-1), sol), (dict(cap=0), sol), (dict(n_states=0), sol)]
     for over, names in cases:
         for name in names:
-            assert _code(_calls(vi, **over)[name]) == E_ARG, (over, name)
+            returns(E_ARG, _calls(vi, **over)[name], what=(over, name))
     for over, names in [(dict(n_states=vi.MAX_STATES + 1), sol), (dict(n_edges=4097), sol), (dict(n_groups=4097), lin), (dict(n_states=4097), lin)]:
         for name in names:
-            assert _code(_calls(vi, **over)[name]) == E_UNSUPPORTED, (over, name)
+            returns(E_UNSUPPORTED, _calls(vi, **over)[name], what=(over, name))
     # an argument error wins over the unsupported size, and both over the missing device
-    assert _code(_calls(vi, n_states=vi.MAX_STATES + 1, dx=None)["solve"]) == E_ARG
+    returns(E_ARG, _calls(vi, n_states=vi.MAX_STATES + 1, dx=None)["solve"])
 
 
 def test_every_wrapper_fails_loudly_without_a_gpu(vi):
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("needs a machine without a GPU")
-    from monoorbslam3_amd import _lib
     for name, call in _calls(vi).items():
-        assert _code(call) == E_NO_DEVICE, name
-        assert b"no HIP device" in _lib.lib().orbx_last_error(), name
+        returns(E_NO_DEVICE, call, what=name)                   # and "no HIP device" in the message
     # the optional arguments are optional: still the device that is missing, not an argument
-    assert _code(_calls(vi, mode=1, H_diag=None, b=None, work=None, active=None, n_inliers=None)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vi, mode=2, H_diag=None, b=None, work=None, total=None)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vi, active=None, n_inliers=None)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vi, n_groups=0, cap_edges=0)["linearize"]) == E_NO_DEVICE and _code(_calls(vi, camera_model=1)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vi, n_edges=0, edges=None, H_off=None)["solve"]) == E_NO_DEVICE and _code(_calls(vi, n_states=vi.MAX_STATES)["solve"]) == E_NO_DEVICE
+    returns(E_NO_DEVICE, _calls(vi, mode=1, H_diag=None, b=None, work=None, active=None, n_inliers=None)["linearize"])
+    returns(E_NO_DEVICE, _calls(vi, mode=2, H_diag=None, b=None, work=None, total=None)["linearize"])
+    returns(E_NO_DEVICE, _calls(vi, active=None, n_inliers=None)["linearize"])
+    returns(E_NO_DEVICE, _calls(vi, n_groups=0, cap_edges=0)["linearize"]), returns(E_NO_DEVICE, _calls(vi, camera_model=1)["linearize"])
+    returns(E_NO_DEVICE, _calls(vi, n_edges=0, edges=None, H_off=None)["solve"]), returns(E_NO_DEVICE, _calls(vi, n_states=vi.MAX_STATES)["solve"])

@@ -9,35 +9,21 @@ import re
 import pytest
 
 import vw_model as wm
+from abi_checks import E_ARG, E_NO_DEVICE, E_UNSUPPORTED, P, ROOT, built, declared, exported_and_mirrored, header, returns, stripped
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-E_ARG, E_NO_DEVICE, E_UNSUPPORTED = -1, -2, -4
 ENTRY_POINTS = ["orbvw_linearize_device", "orbvw_reduce_device", "orbvw_solve_device", "orbvw_backsub_device"]
 
 
 @pytest.fixture(scope="module")
 def vw():
-    import __graft_entry__ as g
-    g.build()
-    from monoorbslam3_amd import vw
-    return vw
-
-
-def _header(name):
-    return open(os.path.join(ROOT, "include", name)).read()
+    return built("vw")
 
 
 def test_every_declared_entry_point_is_exported_and_mirrored(vw):
-    from monoorbslam3_amd import _lib, imu, vi
-    txt = re.sub(r"/\*.*?\*/", "", _header("orbvw.h"), flags=re.S)
-    declared = set(re.findall(r"\b(orbvw_[a-z0-9_]+)\s*\(", txt))
-    assert declared == set(ENTRY_POINTS), sorted(declared)
-    L = C.CDLL(_lib.LIB_PATH)
-    for n in sorted(declared):
-        assert hasattr(L, n), "liborbx.so does not export %s" % n
-        assert n in vw._SIGS and callable(getattr(vw, n[len("orbvw_"):])), n
-    assert set(vw._SIGS) == declared
-    vw._L()                                                     # binds every name of _SIGS or raises
+    from monoorbslam3_amd import imu, vi
+    txt, names = stripped("orbvw.h"), declared("orbvw_", "orbvw.h")
+    assert names == set(ENTRY_POINTS), sorted(names)
+    exported_and_mirrored(vw, "orbvw_", names, sigs_equal=True)
     assert vw.Graph is imu.Graph and vw.Calib is imu.Calib and vw.Camera is vi.Camera and C.sizeof(vw.Camera) == 72 and imu.EDGE.itemsize == 16
     header = re.sub(r"\s+", " ", txt)
     for name, text, value in [("ORBVW_MAX_SOLVE_STATES", "32", vw.MAX_SOLVE_STATES), ("ORBVW_MAX_EDGES", "(1 << 20)", vw.MAX_EDGES),
@@ -52,7 +38,7 @@ def test_every_declared_entry_point_is_exported_and_mirrored(vw):
 def test_nothing_includes_orbvw_h():
     for name in sorted(os.listdir(os.path.join(ROOT, "include"))):
         if name != "orbvw.h":
-            assert "orbvw" not in _header(name), name
+            assert "orbvw" not in header(name), name
     csrc = os.path.join(ROOT, "monoorbslam3_amd", "csrc")
     for name in sorted(os.listdir(csrc)):
         if name.endswith((".hip", ".h")) and name != "orbvw.hip":
@@ -63,12 +49,12 @@ LIN = ("Rwb", "twb", "v", "bg", "ba", "gfixed", "points", "edge_state", "edge_po
 
 
 def _calls(vw, **over):
-    """the four wrappers with valid arguments (fake device addresses, never dereferenced) except for `over`"""
-    p = 0x1000
+    """the four wrappers with valid arguments (the fake device address) except for `over`"""
+    p = P
     a = dict({k: p for k in LIN + ("active", "outlier", "result", "fixed", "edges", "H_off", "lam", "S", "rhs", "Hll_inv", "tl", "out", "dx", "xl", "points_out",
                                    "out_points")},
              n_states=12, n_solve=10, n_points=500, cap_edges=2000, delta=wm.HUBER_MONO, threshold=wm.CHI2_MONO, mode=0, camera_model=0, n_edges=9, cap=16)
-    a["points_out"] = 0x2000
+    a["points_out"] = 2 * P                                     # the updated points may not be the points
     a.update(over)
     import imu_model as im
     c = im.calib()
@@ -87,13 +73,6 @@ def _calls(vw, **over):
                                           a["lam"], a["points"], a["xl"], a["points_out"], a["out_points"], a["result"]))
 
 
-def _code(call):
-    from monoorbslam3_amd._lib import OrbxError
-    with pytest.raises(OrbxError) as e:
-        call()
-    return e.value.code
-
-
 def test_argument_errors_are_reported_before_the_device_is_looked_for(vw):
     every, lin, red, sol, bck = ("linearize", "reduce", "solve", "backsub"), ("linearize",), ("reduce",), ("solve",), ("backsub",)
     cases = [(dict(result=None), every), (dict(n_solve=0), every), (dict(n_solve=-1), every), (dict(b=None), ("linearize", "reduce", "solve")),
@@ -108,34 +87,29 @@ def test_argument_errors_are_reported_before_the_device_is_looked_for(vw):
               (dict(threshold=float("nan")), lin), (dict(camera_model=2), lin), (dict(camera_model=-1), lin), (dict(mode=2, outlier=None), lin),
               (dict(mode=1, total=None), lin)]
     cases += [(dict([(k, None)]), red) for k in ("fixed", "edges", "H_off", "tl")] + [(dict(n_edges=-1), red), (dict(cap=0), red)]
-    cases += [(dict([(k, None)]), bck) for k in ("xl", "points_out", "out_points")] + [(dict(points_out=0x1000), bck)]
+    cases += [(dict([(k, None)]), bck) for k in ("xl", "points_out", "out_points")] + [(dict(points_out=P), bck)]
     for over, names in cases:
         for name in names:
-            assert _code(_calls(vw, **over)[name]) == E_ARG, (over, name)
+            returns(E_ARG, _calls(vw, **over)[name], what=(over, name))
     limits = [(dict(n_solve=vw.MAX_SOLVE_STATES + 1, n_states=40), every), (dict(cap_edges=vw.MAX_EDGES + 1), ("linearize", "reduce", "backsub")),
               (dict(n_points=vw.MAX_POINTS + 1), ("linearize", "reduce", "backsub")), (dict(n_states=4097), lin), (dict(n_edges=4097), red)]
     for over, names in limits:
         for name in names:
-            assert _code(_calls(vw, **over)[name]) == E_UNSUPPORTED, (over, name)
+            returns(E_UNSUPPORTED, _calls(vw, **over)[name], what=(over, name))
     # an argument error wins over the unsupported size, and both over the missing device
     for name, over in (("linearize", dict(err=None)), ("reduce", dict(S=None)), ("solve", dict(dx=None)), ("backsub", dict(xl=None))):
-        assert _code(_calls(vw, n_solve=vw.MAX_SOLVE_STATES + 1, n_states=40, **over)[name]) == E_ARG, name
+        returns(E_ARG, _calls(vw, n_solve=vw.MAX_SOLVE_STATES + 1, n_states=40, **over)[name], what=name)
 
 
 def test_every_wrapper_fails_loudly_without_a_gpu(vw):
-    import torch
-    if torch.cuda.is_available():
-        pytest.skip("needs a machine without a GPU")
-    from monoorbslam3_amd import _lib
     for name, call in _calls(vw).items():
-        assert _code(call) == E_NO_DEVICE, name
-        assert b"no HIP device" in _lib.lib().orbx_last_error(), name
+        returns(E_NO_DEVICE, call, what=name)                   # and "no HIP device" in the message
     # the optional arguments are optional and the limits themselves are supported: still the device that is missing
     null0 = dict(work=None, H_diag=None, b=None, Hll=None, bl=None, Hlp=None)
-    assert _code(_calls(vw, mode=1, active=None, outlier=None, **null0)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vw, mode=2, active=None, total=None, **null0)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vw, active=None, outlier=None)["linearize"]) == E_NO_DEVICE and _code(_calls(vw, camera_model=1, cap_edges=0)["linearize"]) == E_NO_DEVICE
-    assert _code(_calls(vw, n_edges=0, edges=None, H_off=None)["reduce"]) == E_NO_DEVICE
+    returns(E_NO_DEVICE, _calls(vw, mode=1, active=None, outlier=None, **null0)["linearize"])
+    returns(E_NO_DEVICE, _calls(vw, mode=2, active=None, total=None, **null0)["linearize"])
+    returns(E_NO_DEVICE, _calls(vw, active=None, outlier=None)["linearize"]), returns(E_NO_DEVICE, _calls(vw, camera_model=1, cap_edges=0)["linearize"])
+    returns(E_NO_DEVICE, _calls(vw, n_edges=0, edges=None, H_off=None)["reduce"])
     top = dict(n_solve=vw.MAX_SOLVE_STATES, n_states=vw.MAX_SOLVE_STATES, cap_edges=vw.MAX_EDGES, n_points=vw.MAX_POINTS, n_edges=4096)
     for name, call in _calls(vw, **top).items():
-        assert _code(call) == E_NO_DEVICE, name
+        returns(E_NO_DEVICE, call, what=name)
