@@ -98,6 +98,21 @@ int orbx_level_size(const orbx_t *h, int w0, int h0, int level, int *w, int *ht)
 /* Upper bound on keypoints one frame can yield (sum over levels of max(quota+3, 4*nIni)) */
 int orbx_max_keypoints(const orbx_t *h, int w0, int h0);
 
+/* Layout of the caller's image -- ONE contract for orbx_extract, orbx_extract_batch and orbx_extract_batch_device
+ * (tests/test_extractor_layouts_gpu.py holds every kernel that reads level 0 to it):
+ *  - Pixel (x, y) of frame f is the byte at imgs + f * frame_stride + y * stride + x.  ANY stride >= width is accepted
+ *    (a cv::Mat ROI's step, a hipMallocPitch pitch), ANY frame_stride (a ring of frames with headers between them), and ANY
+ *    byte alignment of imgs, stride and frame_stride.  stride < width is ORBX_E_ARG and nothing is computed.
+ *  - The bytes between the rows (x >= width) and between the frames never influence a result: the output is a function
+ *    of the width x height pixels of each frame alone, the same bytes as for a dense copy of them.
+ *  - The image is const: nothing in the caller's buffer is written.
+ *  - Nothing outside [imgs, imgs + (n_frames - 1) * frame_stride + (height - 1) * stride + width) -- frame 0's first pixel
+ *    to the last frame's last pixel -- is read, so an image may end at the last byte of its allocation.  Inside that range
+ *    the device kernels do fetch pad bytes with their packed loads (up to 16 bytes past the end of a row that is not the
+ *    frame's last one: the per-cell FAST tile and the pyramid's LDS staging), and then ignore them.
+ * The host entry points copy the frames as they lie (dense rows in one linear copy per batch or frame, pitched rows in one
+ * 2-D copy per frame) and read the caller's memory only through those copies.  Alignment changes nothing but speed. */
+
 /* ORBExtractor::operator()(image, keyPoints, descriptors)
  * (modules/ORB/ORBExtractor.cpp:495-547).  Host pointers.  img is 8UC1 with
  * `stride` bytes per row.  On success *n_out keypoints and n_out*32 descriptor

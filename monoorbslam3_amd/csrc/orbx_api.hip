@@ -659,7 +659,8 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         raw(l - 1, &sp, &sfs, &spitch);
         // (small calls only: per 512 frames the pyramid takes 0.71 ms this way against 0.47 -- a workgroup's two phases run one
         // after the other -- while a single 1242x375 frame is back 20 us sooner, 157 -> 138 us; ORBX_VAR_RESIZE2 = 2 forces it)
-        if ((c->resize2 == 2 || (c->resize2 == 1 && n_frames < 24)) && l + 1 < L && c->resize2_ok[l]) {
+        // (a source under 8 pixels wide is narrower than the 8-byte window of k_resize2's first phase: orbx_launch_resize has a kernel for it)
+        if ((c->resize2 == 2 || (c->resize2 == 1 && n_frames < 24)) && l + 1 < L && c->resize2_ok[l] && LV.lv[l - 1].w >= 8) {
             orbx_launch_resize2(st, sp, sfs, spitch, LV.lv[l - 1].w, LV.lv[l - 1].h, b.img_arena + LV.lv[l].raw_off, b.img_frame_stride,
                                 LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, xtap(l), ytap(l), b.img_arena + LV.lv[l + 1].raw_off,
                                 b.img_frame_stride, LV.lv[l + 1].pitch, LV.lv[l + 1].w, LV.lv[l + 1].h, xtap(l + 1),

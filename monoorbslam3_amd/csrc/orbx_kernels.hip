@@ -459,10 +459,38 @@ void orbx_launch_resize2(hipStream_t s, const uint8_t *src, size_t src_fs, int s
     hipLaunchKernelGGL(k_resize2, dim3(orbx_xcd_grid(a.gx * a.gy, n_frames)), dim3(256), 0, s, a);
 }
 
+// A source narrower than k_resize's 8-byte window (no key point can come from such a level, but the pyramid is still built):
+// its window would start before the row -- for the first row of a caller's image, before the image.  One thread per output
+// pixel and byte loads instead; same integers as resize_quad.
+__global__ __launch_bounds__(256) void k_resize_narrow(const uint8_t *__restrict__ src, size_t src_fs, int src_pitch, int sw, int sh,
+                                                       uint8_t *__restrict__ dst, size_t dst_fs, int dst_pitch, int dw, int dh,
+                                                       const OrbxTap *__restrict__ xtap, const OrbxTap *__restrict__ ytap,
+                                                       int *__restrict__ zero_counts)
+{
+    const int frame = blockIdx.y;
+    if (zero_counts && blockIdx.x == 0 && threadIdx.x < ORBX_MAX_LEVELS) zero_counts[frame * ORBX_MAX_LEVELS + threadIdx.x] = 0;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= dw * dh) return;
+    const int y = i / dw, x = i - y * dw;
+    const OrbxTap tx = xtap[x], ty = ytap[y];
+    const int x0 = min(max(tx.ofs, 0), sw - 1), x1 = min(x0 + 1, sw - 1); // (the tap on the last column has c1 = 0)
+    const uint8_t *S = src + (size_t)frame * src_fs;
+    const uint8_t *p0 = S + (size_t)min(max(ty.ofs, 0), sh - 1) * src_pitch, *p1 = S + (size_t)min(max(ty.ofs + 1, 0), sh - 1) * src_pitch;
+    const uint32_t r0 = (uint32_t)p0[x0] * (uint32_t)tx.c0 + (uint32_t)p0[x1] * (uint32_t)tx.c1;
+    const uint32_t r1 = (uint32_t)p1[x0] * (uint32_t)tx.c0 + (uint32_t)p1[x1] * (uint32_t)tx.c1;
+    const int v = (((int)__umul24((uint32_t)ty.c0, r0 >> 4) >> 16) + ((int)__umul24((uint32_t)ty.c1, r1 >> 4) >> 16) + 2) >> 2;
+    dst[(size_t)frame * dst_fs + (size_t)y * dst_pitch + x] = (uint8_t)v;
+}
+
 void orbx_launch_resize(hipStream_t s, const uint8_t *src, size_t src_fs, int src_pitch, int sw, int sh,
                         uint8_t *dst, size_t dst_fs, int dst_pitch, int dw, int dh, const OrbxTap *xtap,
                         const OrbxTap *ytap, int n_frames, int *zero_counts)
 {
+    if (sw < 8) {
+        hipLaunchKernelGGL(k_resize_narrow, dim3((dw * dh + 255) / 256, n_frames), dim3(256), 0, s, src, src_fs, src_pitch, sw, sh, dst,
+                           dst_fs, dst_pitch, dw, dh, xtap, ytap, zero_counts);
+        return;
+    }
     const int gx = (dw + 255) / 256, gy = (dh + 4 * RS_ROWS - 1) / (4 * RS_ROWS);
     hipLaunchKernelGGL(k_resize, dim3(orbx_xcd_grid(gx * gy, n_frames)), dim3(64, 4), 0, s, src, src_fs, src_pitch, sw, sh, dst,
                        dst_fs, dst_pitch, dw, dh, xtap, ytap, gx, gy, n_frames, zero_counts);

@@ -161,15 +161,19 @@ class ORBExtractor:
         return kps[: n.value].copy(), desc[: n.value].copy()
 
     def extract_batch(self, images):
-        """Batch of equally sized frames (n, h, w) u8 on the host -> list of (keypoints, descriptors)."""
-        images = np.ascontiguousarray(images, dtype=np.uint8)
+        """Batch of equally sized frames (n, h, w) u8 on the host -> list of (keypoints, descriptors).
+        A uint8 array whose pixels of a row are adjacent is passed as it lies, with its own row and frame strides (a crop, every
+        second frame of a stack); anything else is copied first."""
+        images = np.asarray(images)
         nf, h, w = images.shape
+        if images.dtype != np.uint8 or images.strides[2] != 1 or images.strides[1] < w or images.strides[0] <= 0:
+            images = np.ascontiguousarray(images, dtype=np.uint8)
         cap = self.max_keypoints(w, h)
         kps = np.zeros((nf, cap), KP_DTYPE)
         desc = np.zeros((nf, cap, 32), np.uint8)
         counts = np.zeros(nf, np.int32)
-        _lib.check(self._L.orbx_extract_batch(self._h, _vp(images), nf, w, h, w, h * w, _vp(kps), _vp(desc), cap,
-                                              _vp(counts)))
+        _lib.check(self._L.orbx_extract_batch(self._h, _vp(images), nf, w, h, images.strides[1], images.strides[0],
+                                              _vp(kps), _vp(desc), cap, _vp(counts)))
         return [(kps[f, : counts[f]].copy(), desc[f, : counts[f]].copy()) for f in range(nf)]
 
     def extract_batch_device(self, d_imgs_ptr, n_frames, w, h, stride, frame_stride, d_kp_ptr, d_desc_ptr, cap,
