@@ -8,10 +8,11 @@
  * this header adds the two layers between them, so that one Levenberg-Marquardt iteration is a chain on one stream
  *   orbi_graph_init_device -> orbi_edge_information_device -> orbi_linearize_device -> orbvi_linearize_device ->
  *   orbvi_solve_device -> orbi_graph_oplus_device -> orbi_linearize_device (mode 1) + orbvi_linearize_device (mode 1)
- * and the caller reads back two scalars (the chi2 at the trial point, d_out[0] of the solve) for its accept / reject decision.  THE
- * LOOP ITSELF IS NOT HERE: its decisions are the caller's.  A caller that closes it (tests/inertial_loop.py does, as test
- * code) needs two things no call does for it.  The lambda init: d_out[1], what computeLambdaInit multiplies by tau, is written by
- * orbvi_solve_device only, so iteration 0 of every optimize() costs one solve whose step is discarded (any *d_lambda; a refused
+ * and the caller reads back two scalars (the chi2 at the trial point, d_out[0] of the solve) for its accept / reject decision.  In
+ * these STAGED calls THE LOOP ITSELF IS NOT HERE: its decisions are the caller's.  The tracker's two loops, closed, are
+ * orbvi_pose_optimize_device (orbvi_loop.h; the end of this comment): one launch on the same stage code.  A caller that closes the staged chain
+ * itself (tests/inertial_loop.py does, as test code) needs two things no staged call does for it.  The lambda init: d_out[1], what
+ * computeLambdaInit multiplies by tau, is written by orbvi_solve_device only, so iteration 0 of every optimize() costs one solve whose step is discarded (any *d_lambda; a refused
  * solve writes d_out[1] all the same).  The pop: g2o pushes CameraImuPose WITH its update counter, so a rejected trial restores d_iter
  * along with Rwb, twb, v, bg and ba -- a counter left as the trial set it renormalises the rotation at other updates than the
  * reference.  Not here either: EdgeMono (G2oTypes.cpp:59-69), where the
@@ -103,6 +104,17 @@
  *   k_vi_linearize 126 / 0 / 3952 B, k_vi_solve 81 / 0 / 30032 B, k_counters_clear 2 / 0 / 0 B.
  * Both calls are latency-bound (one group of a few hundred to 2000 edges; at most 60 unknowns): nothing here has been tuned for
  * throughput and no throughput claim is made.
+ *
+ * ---- the tracker's two loops, closed: include/orbvi_loop.h ----
+ *
+ * orbvi_pose_optimize_device runs the whole of poseFullOptimize / poseInertialOptimize as ONE kernel launch of one workgroup: the rounds,
+ * g2o's Levenberg-Marquardt policy, push / pop and the classification, on the stage code of the two calls above and of
+ * orbi_linearize_device / orbi_graph_oplus_device (csrc/orbvi_stages.h, which the staged kernels run as well), so that a linearisation,
+ * a solve and an update inside the loop give the bytes of the staged calls.  Its contract, options and kernel resources are in
+ * orbvi_loop.h, which includes this header; the chain is
+ *   orbi_graph_init_device -> orbi_edge_information_device -> orbvi_pose_optimize_device -> orbi_graph_recover_device
+ *   (-> orbba_pose_drop_outliers_device)
+ * The window loops (localFullBundleAdjustment) and initializeIMU's loops are not in the product.
  */
 #ifndef ORBVI_H
 #define ORBVI_H

@@ -101,14 +101,16 @@ __device__ __forceinline__ void flush_counts(const int *s_cnt, int32_t *result)
 
 // N per-thread floating-point sums over a workgroup of WAVES waves in a fixed order, so that the same input gives the same bytes and no
 // floating-point atomic is needed.  block_sums_put: the butterfly over the wave, then lane 0 leaves sum k of [first, last) (uniform) in
-// s_part[wave][k]; the caller's barrier follows; block_sums_get: sum k of the workgroup, the wave slots added in ascending order
-template <int WAVES, int N> __device__ __forceinline__ void block_sums_put(const double (&acc)[N], double (&s_part)[WAVES][N], int first = 0, int last = N)
+// s_part[wave][k] (wave: the slot, by default the thread's own wave -- a thread that stands in for several gives the wave it stands in
+// for); the caller's barrier follows; block_sums_get: sum k of the workgroup, the wave slots added in ascending order
+template <int WAVES, int N>
+__device__ __forceinline__ void block_sums_put(const double (&acc)[N], double (&s_part)[WAVES][N], int first = 0, int last = N, int wave = -1)
 {
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         if (k < first || k >= last) continue;
         const double v = wave_sum(acc[k]);
-        if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6][k] = v;
+        if ((threadIdx.x & 63) == 0) s_part[wave < 0 ? (int)(threadIdx.x >> 6) : wave][k] = v;
     }
 }
 template <int WAVES, int N> __device__ __forceinline__ double block_sums_get(const double (&s_part)[WAVES][N], int k)

@@ -36,6 +36,7 @@
 #include "orbi_graph_device.h"
 #include "orbi_so3.h"
 #include "orbi_so3d.h"
+#include "orbvi_stages.h"
 
 #pragma clang fp contract(off)
 
@@ -174,30 +175,7 @@ __global__ __launch_bounds__(64) void k_fac_oplus(const orbi_graph g, const doub
     __syncthreads();
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s < g.n_states) {
-        const int fixed = g.fixed[s];
-        const double *d = dx + 15 * (size_t)s;
-        if (!(fixed & ORBI_FIX_POSE)) {   // CameraImuPose::update
-            double R[9], E[9], N[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) R[k] = g.Rwb[9 * (size_t)s + k];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) g.twb[3 * (size_t)s + k] = g.twb[3 * (size_t)s + k] + dsum3(dmul(R[3 * k], d[3]), dmul(R[3 * k + 1], d[4]), dmul(R[3 * k + 2], d[5]));
-            dexp_so3(d[0], d[1], d[2], E);   // ExpSO3 returns NormalizeRotation(res)
-#pragma unroll
-            for (int k = 0; k < 9; ++k) N[k] = dm3(R, E, k / 3, k % 3);
-            const int it = iter[s] + 1;
-            if (it == 3) dnormalize(N);
-            iter[s] = it == 3 ? 0 : it;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) g.Rwb[9 * (size_t)s + k] = N[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (!(fixed & ORBI_FIX_VELO)) g.v[3 * (size_t)s + k] = g.v[3 * (size_t)s + k] + d[6 + k];
-            if (!(fixed & ORBI_FIX_GYRO)) g.bg[3 * (size_t)s + k] = g.bg[3 * (size_t)s + k] + d[9 + k];
-            if (!(fixed & ORBI_FIX_ACC)) g.ba[3 * (size_t)s + k] = g.ba[3 * (size_t)s + k] + d[12 + k];
-        }
-        if ((fixed & 15) != 15) atomicAdd(&s_cnt[ORBI_R_DONE], 1);
+        if (fac_oplus_state(g, dx, iter, s)) atomicAdd(&s_cnt[ORBI_R_DONE], 1);
     }
     __syncthreads();
     flush_counts(s_cnt, result);
@@ -298,31 +276,11 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge_info(const orbi_record *__re
     flush_counts(s_cnt, result);
 }
 
-// ---- orbi_linearize_device ---------------------------------------------------------------------------------------------------------------
-struct LinArgs {
-    orbi_graph g;
-    const orbi_record *bank;
-    int cap;
-    float gravity;
-    const orbi_edge *edges;
-    int n_edges;
-    const double *info, *walk_info;
-    const orbi_prior *priors;
-    int n_priors;
-    const orbi_prior_job *pjobs;
-    int n_pjobs;
-    double delta;
-    int mode;
-    double *work, *err, *chi2, *chi2_prior, *total, *H_diag, *H_off, *b, *J;
-    float *flt;
-    int32_t *result;
-};
-
-// the workspace of an edge: H_ii (225), H_jj (225), b_i (15), b_j (15), W_gyro*e_gyro (3), W_acc*e_acc (3), status, Huber weight
-enum { W_HII = 0, W_HJJ = 225, W_B = 450, W_WALK = 480, W_STATUS = 486, W_RHO1 = 487 };
-static_assert(W_RHO1 + 1 == ORBI_EDGE_WORK, "orbi_factors.h states the workspace of an edge");
-enum { ST_OK = 0, ST_RANGE = 1, ST_REFUSED = 3 };   // == ORBI_R_DONE, ORBI_R_RANGE, ORBI_R_REFUSED
-
+// ---- orbi_linearize_device: the wave of an edge, the wave of a state and the tail wave are orbvi_stages.h's ----------------------------------
+// which k_vi_pose_loop (orbvi_loop.hip) runs as well: a kernel here owns its LDS, its launch shape and its counters.  fac_edge_wave is, in
+// the order k_fac_edge had them: edge_valid(), edge_refused(), edge_load(), bias_deltas(), edge_widen(), edge_velocity_position(),
+// edge_rotation(), edge_chi2(), jac_entry() under dof_fixed(), edge_quadratic_form<30>() and edge_jtwj<30>(); fac_oplus_state is
+// CameraImuPose::update on dexp_so3().
 static_assert(X_WORDS == 140 && D_WORDS == 825, "include/orbi.h states the LDS of k_fac_edge");
 
 __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
@@ -332,91 +290,7 @@ __global__ __launch_bounds__(FAC_T) void k_fac_edge(const LinArgs a)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int e = blockIdx.x * FAC_WAVES + wave;
     if (e >= a.n_edges) return;                      // no workgroup barrier in this kernel
-    double *S = s_d[wave];
-    float *F = s_f[wave];
-    double *work = a.work + (size_t)ORBI_EDGE_WORK * e;
-    const int si = __builtin_amdgcn_readfirstlane(a.edges[e].i), sj = __builtin_amdgcn_readfirstlane(a.edges[e].j);
-    const int rec = __builtin_amdgcn_readfirstlane(a.edges[e].rec), flags = __builtin_amdgcn_readfirstlane(a.edges[e].flags);
-    const int g = lane / 9, q = lane - 9 * g, i = q / 3, j = q - 3 * i;
-    int status = ST_OK;
-    if (!edge_valid(si, sj, rec, a.g.n_states, a.cap)) status = ST_RANGE;
-    else if (edge_refused(a.info, e)) status = ST_REFUSED;
-    if (status != ST_OK) {
-        if (lane < 9) a.err[9 * (size_t)e + lane] = 0.0;
-        if (lane < 3) a.chi2[3 * (size_t)e + lane] = 0.0;
-        if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = 0.f;
-        if (a.mode == 0) {
-            for (int x = lane; x < 225; x += 64) a.H_off[225 * (size_t)e + x] = 0.0;
-            if (a.J)
-                for (int x = lane; x < 270; x += 64) a.J[270 * (size_t)e + x] = 0.0;
-        }
-        if (lane == 0) work[W_STATUS] = (double)status;
-        return;
-    }
-    // ---- load: the head of the record, the vertices of both states, the information
-    edge_load(a.bank, rec, a.info, e, F, S, lane);
-    if (lane < 9) S[D_R1 + lane] = a.g.Rwb[9 * (size_t)si + lane];
-    else if (lane < 18) S[D_R2 + lane - 9] = a.g.Rwb[9 * (size_t)sj + lane - 9];
-    else if (lane < 21) S[D_T1 + lane - 18] = a.g.twb[3 * (size_t)si + lane - 18];
-    else if (lane < 24) S[D_T2 + lane - 21] = a.g.twb[3 * (size_t)sj + lane - 21];
-    else if (lane < 27) S[D_V1 + lane - 24] = a.g.v[3 * (size_t)si + lane - 24];
-    else if (lane < 30) S[D_V2 + lane - 27] = a.g.v[3 * (size_t)sj + lane - 27];
-    else if (lane < 33) S[D_B1 + lane - 30] = a.g.bg[3 * (size_t)si + lane - 30];
-    else if (lane < 36) S[D_B1 + lane - 30] = a.g.ba[3 * (size_t)si + lane - 33];
-    else if (lane < 39) S[D_B2 + lane - 36] = a.g.bg[3 * (size_t)sj + lane - 36];
-    else if (lane < 42) S[D_B2 + lane - 36] = a.g.ba[3 * (size_t)sj + lane - 39];
-    const int fix_i = a.g.fixed[si], fix_j = a.g.fixed[sj];
-    WSYNC();
-    // ---- the float part: the bias vertices cast to float, getDeltaRotation / Velocity / Position (Imu.cpp:182-192)
-    bias_deltas(F, F + X_T, lane, lane < 6 ? (float)S[D_B1 + lane] : 0.f);
-    if (a.flt && lane < 15) a.flt[15 * (size_t)e + lane] = lane < 9 ? F[X_T + BD_DRU + lane] : F[X_T + BD_DVP + lane - 9];
-    // ---- everything behind the cast to double: this edge's lines on lane groups 2 .. 4, the rotation residual beside them
-    const double dt = (double)F[RH_DT], G = (double)a.gravity;
-    edge_widen(F, F + X_T, S, lane);
-    edge_velocity_position(S, lane, G, dt);                                       // ev, ep and Rb1w*R2
-    edge_rotation(S, lane);
-    if (g == 2) S[D_T3 + q] = dm3nt(S + D_INVJ, S + D_R2, i, j);                  // (-invJr) * R2^T
-    // ---- chi2, the Huber kernel (g2o's RobustKernelHuber), the walks
-    const double chi = edge_chi2(S, lane);
-    double rho1 = 1.0;
-    if (a.delta > 0.0 && chi > dmul(a.delta, a.delta)) rho1 = a.delta / sqrt(chi);
-    double we[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, wchi[2] = {0.0, 0.0};
-    if (flags & ORBI_EDGE_WALKS) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const double *W = a.walk_info + 18 * (size_t)e + 9 * b;
-            const double e0 = S[D_B2 + 3 * b] - S[D_B1 + 3 * b], e1 = S[D_B2 + 3 * b + 1] - S[D_B1 + 3 * b + 1], e2 = S[D_B2 + 3 * b + 2] - S[D_B1 + 3 * b + 2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) we[b][k] = dsum3(dmul(W[3 * k], e0), dmul(W[3 * k + 1], e1), dmul(W[3 * k + 2], e2));
-            wchi[b] = dsum3(dmul(e0, we[b][0]), dmul(e1, we[b][1]), dmul(e2, we[b][2]));
-        }
-    }
-    if (lane < 9) a.err[9 * (size_t)e + lane] = S[D_E + lane];
-    if (lane < 3) a.chi2[3 * (size_t)e + lane] = lane == 0 ? chi : lane == 1 ? wchi[0] : wchi[1];
-    if (lane == 0) work[W_STATUS] = (double)ST_OK, work[W_RHO1] = rho1;
-    if (lane < 6) work[W_WALK + lane] = lane == 0 ? we[0][0] : lane == 1 ? we[0][1] : lane == 2 ? we[0][2] : lane == 3 ? we[1][0] : lane == 4 ? we[1][1] : we[1][2];
-    if (a.mode != 0) return;
-    // ---- the Jacobian: raw to d_J, with the columns of fixed dof zeroed to LDS
-#pragma unroll
-    for (int h = 0; h < 5; ++h) {
-        const int x = lane + 64 * h;
-        if (x < 270) {
-            const int r = x / 30, c = x - 30 * r;
-            const double v = jac_entry(S, dt, r, c);
-            if (a.J) a.J[270 * (size_t)e + x] = v;
-            S[D_J + x] = dof_fixed(c < 15 ? fix_i : fix_j, c < 15 ? c : c - 15) ? 0.0 : v;
-        }
-    }
-    WSYNC();
-    // W = rho1 * Omega: H_ii and H_jj, b_i and b_j to the workspace; H_ij, with the walks' -W, to d_H_off
-    edge_quadratic_form<30>(S, S + D_J, S + D_WJ, rho1, work + W_HII, work + W_B, lane);
-    for (int y = lane; y < 225; y += 64) {
-        const int r = y / 15, c = y - 15 * r;
-        double s = edge_jtwj<30>(S + D_J, S + D_WJ, r, 15 + c);
-        if ((flags & ORBI_EDGE_WALKS) && r >= 9 && c >= 9 && r / 3 == c / 3 && !dof_fixed(fix_i, r) && !dof_fixed(fix_j, c))
-            s = s - a.walk_info[18 * (size_t)e + 9 * (r / 3 - 3) + 3 * (r % 3) + c % 3];
-        a.H_off[225 * (size_t)e + y] = s;
-    }
+    fac_edge_wave(a, a.mode, e, s_d[wave], s_f[wave], lane);
 }
 
 // mode 0: waves [0, n_states) gather a state each; the last wave (the only one of mode 1) does the priors' chi2, the totals, d_result
@@ -426,117 +300,10 @@ __global__ __launch_bounds__(FAC_T) void k_fac_gather(const LinArgs a)
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n_gather = a.mode == 0 ? a.g.n_states : 0;
     const int s = blockIdx.x * FAC_WAVES + wave;
-    if (s < n_gather) {
-        const int fixed = a.g.fixed[s];
-        double h[4] = {0.0, 0.0, 0.0, 0.0}, bb = 0.0;       // entries lane + 64k of the 15 x 15 block; entry `lane` of b
-        int hr[4], hc[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) hr[k] = (lane + 64 * k) / 15, hc[k] = (lane + 64 * k) % 15;
-        for (int c0 = 0; c0 < a.n_edges; c0 += 64) {
-            const int e = c0 + lane;
-            int side = 0;                                     // 1: this state is the edge's i, 2: its j
-            if (e < a.n_edges && a.work[(size_t)ORBI_EDGE_WORK * e + W_STATUS] == (double)ST_OK) side = a.edges[e].i == s ? 1 : a.edges[e].j == s ? 2 : 0;
-            unsigned long long mi = __ballot(side == 1), mj = __ballot(side == 2), m = mi | mj;
-            while (m) {
-                const int bit = __builtin_ctzll(m);
-                m &= m - 1;
-                const int ee = c0 + bit;
-                const bool first = (mi >> bit) & 1;
-                const double *w = a.work + (size_t)ORBI_EDGE_WORK * ee;
-                const int fl = a.edges[ee].flags;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (lane + 64 * k < 225) h[k] = h[k] + w[(first ? W_HII : W_HJJ) + lane + 64 * k];
-                if (lane < 15) bb = bb + w[W_B + (first ? 0 : 15) + lane];
-                if (fl & ORBI_EDGE_WALKS) {                   // J = -I (first) / +I: H += W, b -= J^T * (W*e)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (lane + 64 * k < 225 && hr[k] >= 9 && hc[k] >= 9 && hr[k] / 3 == hc[k] / 3 && !dof_fixed(fixed, hr[k]))
-                            h[k] = h[k] + a.walk_info[18 * (size_t)ee + 9 * (hr[k] / 3 - 3) + 3 * (hr[k] % 3) + hc[k] % 3];
-                    if (lane >= 9 && lane < 15 && !dof_fixed(fixed, lane)) bb = first ? bb + w[W_WALK + lane - 9] : bb - w[W_WALK + lane - 9];
-                }
-            }
-        }
-        for (int c0 = 0; c0 < a.n_pjobs; c0 += 64) {
-            const int p = c0 + lane;
-            bool hit = false;
-            if (p < a.n_pjobs) hit = a.pjobs[p].state == s && a.pjobs[p].prior >= 0 && a.pjobs[p].prior < a.n_priors;
-            unsigned long long m = __ballot(hit);
-            while (m) {
-                const int bit = __builtin_ctzll(m);
-                m &= m - 1;
-                const orbi_prior_job pj = a.pjobs[c0 + bit];
-                const orbi_prior *pr = a.priors + pj.prior;
-#pragma unroll
-                for (int v = 0; v < 3; ++v) {                 // velocity, gyro, acc: e = priori - estimate, J = -I
-                    if (!((pj.mask >> v) & 1) || ((fixed >> (v + 1)) & 1)) continue;
-                    const float *Om = v == 0 ? pr->velo_info : (v == 1 || (pj.mask & ORBI_PRIOR_ACC_GYRO_INFO)) ? pr->gyro_info : pr->acc_info;
-                    const float *me = v == 0 ? pr->velo_priori : pr->bias_priori + 3 * (v - 1);
-                    const double *est = (v == 0 ? a.g.v : v == 1 ? a.g.bg : a.g.ba) + 3 * (size_t)s;
-                    const int base = 6 + 3 * v;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if (lane + 64 * k < 225 && hr[k] >= base && hr[k] < base + 3 && hc[k] >= base && hc[k] < base + 3)
-                            h[k] = h[k] + (double)Om[3 * (hr[k] - base) + hc[k] - base];
-                    if (lane >= base && lane < base + 3) {
-                        const int r = lane - base;
-                        bb = bb + dsum3(dmul((double)Om[3 * r], (double)me[0] - est[0]), dmul((double)Om[3 * r + 1], (double)me[1] - est[1]),
-                                        dmul((double)Om[3 * r + 2], (double)me[2] - est[2]));
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (lane + 64 * k < 225) a.H_diag[225 * (size_t)s + lane + 64 * k] = h[k];
-        if (lane < 15) a.b[15 * (size_t)s + lane] = bb;
-    }
+    if (s < n_gather) fac_gather_state(a, s, lane);
     if (s != n_gather) return;                                // uniform per wave; the tail wave alone uses s_cnt
-    if (lane < 8) s_cnt[lane] = 0;
-    WSYNC();
-    for (int p = lane; p < a.n_pjobs; p += 64) {
-        const orbi_prior_job pj = a.pjobs[p];
-        double c[3] = {0.0, 0.0, 0.0};
-        const bool ok = pj.state >= 0 && pj.state < a.g.n_states && pj.prior >= 0 && pj.prior < a.n_priors;
-        if (ok) {
-            const orbi_prior *pr = a.priors + pj.prior;
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                if (!((pj.mask >> v) & 1)) continue;
-                const float *Om = v == 0 ? pr->velo_info : (v == 1 || (pj.mask & ORBI_PRIOR_ACC_GYRO_INFO)) ? pr->gyro_info : pr->acc_info;
-                const float *me = v == 0 ? pr->velo_priori : pr->bias_priori + 3 * (v - 1);
-                const double *est = (v == 0 ? a.g.v : v == 1 ? a.g.bg : a.g.ba) + 3 * (size_t)pj.state;
-                const double e0 = (double)me[0] - est[0], e1 = (double)me[1] - est[1], e2 = (double)me[2] - est[2];
-                double we[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) we[k] = dsum3(dmul((double)Om[3 * k], e0), dmul((double)Om[3 * k + 1], e1), dmul((double)Om[3 * k + 2], e2));
-                c[v] = dsum3(dmul(e0, we[0]), dmul(e1, we[1]), dmul(e2, we[2]));
-            }
-        }
-#pragma unroll
-        for (int v = 0; v < 3; ++v) a.chi2_prior[3 * (size_t)p + v] = c[v];
-        atomicAdd(&s_cnt[ok ? ORBI_R_PRIOR_DONE : ORBI_R_PRIOR_RANGE], 1);
-    }
-    for (int e = lane; e < a.n_edges; e += 64) atomicAdd(&s_cnt[(int)a.work[(size_t)ORBI_EDGE_WORK * e + W_STATUS]], 1);
-    __threadfence();                                          // lane 0 reads what the other lanes wrote to d_chi2_prior
-    WSYNC();
+    fac_gather_tail(a, s_cnt, lane);
     if (lane < 8) a.result[lane] = s_cnt[lane];
-    if (lane == 0) {                                          // the totals in their one order
-        double plain = 0.0, robust = 0.0;
-        const double dsqr = dmul(a.delta, a.delta);
-        for (int e = 0; e < a.n_edges; ++e) {
-            const double c0 = a.chi2[3 * (size_t)e], c1 = a.chi2[3 * (size_t)e + 1], c2 = a.chi2[3 * (size_t)e + 2];
-            const double r0 = (a.delta > 0.0 && c0 > dsqr) ? dmul(dmul(2.0, sqrt(c0)), a.delta) - dsqr : c0;
-            plain = ((plain + c0) + c1) + c2;
-            robust = ((robust + r0) + c1) + c2;
-        }
-        for (int p = 0; p < a.n_pjobs; ++p)
-            for (int v = 0; v < 3; ++v) {
-                const double c = a.chi2_prior[3 * (size_t)p + v];
-                plain = plain + c, robust = robust + c;
-            }
-        a.total[0] = plain, a.total[1] = robust;
-    }
 }
 
 int check_graph(const orbi_graph &g, const void *result)
