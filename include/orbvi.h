@@ -114,7 +114,7 @@
  * orbvi_loop.h, which includes this header; the chain is
  *   orbi_graph_init_device -> orbi_edge_information_device -> orbvi_pose_optimize_device -> orbi_graph_recover_device
  *   (-> orbba_pose_drop_outliers_device)
- * The window loops (localFullBundleAdjustment) and initializeIMU's loops are not in the product.
+ * localFullBundleAdjustment's loop is closed by the host in orbwl.h (it waits once per trial); initializeIMU's loops are not in the product.
  */
 #ifndef ORBVI_H
 #define ORBVI_H

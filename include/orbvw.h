@@ -20,6 +20,7 @@
  * (getRecentKeyFrames) and the job list of the setPrioriInformation chaining behind the optimisation are
  * orbm_inertial_window_problem_device (orbm.h, "The inertial local BA window on the device-resident map"), which leaves its arrays in
  * the layout of the calls below.  Not here: inertialOptimize / fullInertialOptimize.
+ * A caller that does not want to close the loop itself: orbwl.h (orbwl_window_optimize_device) closes it over these calls, and waits.
  *
  * This header includes orbvi.h and nothing includes it.  Same rules as there: handle-less `*_device` entry points under the one
  * stream rule of orbx.h ("Streams and threads") -- a call enqueues on exactly the `stream` it is given (a hipStream_t; NULL is stream

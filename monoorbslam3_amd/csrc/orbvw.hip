@@ -673,3 +673,171 @@ extern "C" int orbvw_backsub_device(int n_solve, int n_points, int cap_edges, co
     ORB_TRY(hipGetLastError());
     return ORBX_OK;
 }
+
+// =====================================================================================================================
+// The window loop (include/orbwl.h): localFullBundleAdjustment's Levenberg-Marquardt loop closed by the host over the staged entry
+// points above and orbi.h's, which it CALLS -- no stage kernel is launched or restated here.  The host driver lives in this file
+// because this is the one source that includes orbvw.h; what runs on the device between the stage calls (the policy, push and pop,
+// the trace, the counters) is orbwl.hip's, reached through orbwl_kernels.h.  It waits on the caller's stream once per trial, for one
+// 16-byte verdict in page-locked memory, and once at the end.
+// =====================================================================================================================
+#include "orbwl_kernels.h"
+
+static_assert(ORBWL_R_OUTLIER == ORBVW_R_OUTLIER && ORBWL_R_POINT_SINGULAR == ORBVW_R_POINT_SINGULAR && ORBWL_R_REJECTED == ORBI_R_DUPLICATE,
+              "orbwl.h restates these slots of a d_result");
+
+namespace {
+
+// the caller's scratch carved into the intermediates of the chain, in doubles; every slice starts on an even double
+enum { WLR_LIN_I, WLR_LIN_V, WLR_REDUCE, WLR_SOLVE, WLR_BACKSUB, WLR_OPLUS, WLR_TRY_I, WLR_TRY_V, WLR_CLASSIFY, WLR_SLOTS };
+struct WlPlan {
+    int64_t n = 0;
+    int64_t H_diag, H_off, b, iwork, ierr, ichi2, ichi2_prior, itotal, vwork, verr, vtotal, Hll, bl, Hlp, point_off, S, rhs, Hll_inv, tl, dx, xl, points2,
+        out, out_points, lambda, saved, saved_iter, ctrl, results;
+    int64_t add(int64_t doubles) { const int64_t o = n; n += (doubles + 1) & ~(int64_t)1; return o; }
+    WlPlan(int64_t S_, int64_t ns, int64_t L, int64_t E, int64_t J, int64_t P)
+    {
+        const int64_t N = 15 * ns;
+        H_diag = add(225 * S_), H_off = add(225 * J), b = add(15 * S_);
+        iwork = add(ORBI_EDGE_WORK * J), ierr = add(9 * J), ichi2 = add(3 * J), ichi2_prior = add(3 * P), itotal = add(4);
+        vwork = add(ORBVW_EDGE_WORK * E), verr = add(2 * E), vtotal = add(4), Hll = add(9 * L), bl = add(3 * L), Hlp = add(18 * E), point_off = add((L + 1 + 1) / 2);
+        S = add(N * N), rhs = add(N), Hll_inv = add(9 * L), tl = add(3 * L), dx = add(N), xl = add(3 * L);
+        points2 = add(3 * L);
+        out = add(3), out_points = add(1), lambda = add(1);
+        saved = add(21 * ns), saved_iter = add((ns + 1) / 2);
+        ctrl = add(WL_CTRL_DOUBLES);
+        results = add(8 * WLR_SLOTS / 2);
+    }
+};
+
+// a page-locked block for the verdict, leased for a call and pooled per device: nothing is allocated per call
+struct WlWork {
+    int device = 0;
+    hipStream_t stream = nullptr;          // none of its own: the call runs on the caller's stream
+    PinBuf h;
+    hipError_t init() { return h.need(64, 64); }
+};
+LeasePool<WlWork> g_wl_work; // per process, keyed by device; never freed: the HIP runtime may be gone when static destructors run
+
+inline bool wl_number(double x) { return x == x; }
+
+} // namespace
+
+extern "C" int64_t orbwl_window_work_doubles(int n_states, int n_solve, int n_points, int cap_edges, int n_edges, int n_prior_jobs)
+{
+    if (n_states < 1 || n_solve < 1 || n_solve > n_states || n_points < 1 || cap_edges < 0 || n_edges < 0 || n_prior_jobs < 0) return -1;
+    return WlPlan(n_states, n_solve, n_points, cap_edges, n_edges, n_prior_jobs).n;
+}
+
+extern "C" int orbwl_window_optimize_device(orbi_graph graph, int32_t *d_iter, const orbi_record *d_bank, int cap, const orbi_edge *d_edges, int n_edges,
+                                            const double *d_info, const double *d_walk_info, const orbi_prior *d_priors, int n_priors,
+                                            const orbi_prior_job *d_prior_jobs, int n_prior_jobs, orbi_calib calib, orbvi_camera camera, int n_solve,
+                                            int n_points, int cap_edges, double *d_points, const int32_t *d_edge_state, const int32_t *d_edge_point,
+                                            const double *d_edge_z, const double *d_edge_inv_sigma2, const uint8_t *d_active, orbwl_loop_options options,
+                                            double *d_work, double *d_chi2, uint8_t *d_outlier, double *d_trace, int cap_trace, double *d_summary,
+                                            int32_t *d_result, const volatile int32_t *stop, void *stream)
+{
+    const orbwl_loop_options &o = options;
+    if (!graph.Rwb || !graph.twb || !graph.v || !graph.bg || !graph.ba || !graph.fixed || graph.n_states < 0 || !d_result)
+        return orbx_set_error(ORBX_E_ARG, "null graph array or result, or a negative state count");
+    if (!d_iter || !d_bank || cap < 1 || !d_edges || n_edges < 0 || !d_info || !d_walk_info)
+        return orbx_set_error(ORBX_E_ARG, "null d_iter, bank, inertial edge list or information, cap < 1, or a negative inertial edge count");
+    if (n_prior_jobs < 0 || n_priors < 0 || (n_prior_jobs > 0 && (!d_prior_jobs || !d_priors)))
+        return orbx_set_error(ORBX_E_ARG, "prior jobs without their list or the priors, or a negative count");
+    if (n_points < 1 || cap_edges < 0 || !d_points || !d_edge_state || !d_edge_point || !d_edge_z || !d_edge_inv_sigma2)
+        return orbx_set_error(ORBX_E_ARG, "null point or EdgeMono array, n_points < 1 or a negative cap_edges");
+    if (n_solve < 1 || n_solve > graph.n_states) return orbx_set_error(ORBX_E_ARG, "n_solve outside [1, n_states]");
+    if (!d_work || ((uintptr_t)d_work & 15)) return orbx_set_error(ORBX_E_ARG, "d_work is null or not 16-byte aligned");
+    if (!d_chi2 || !d_outlier || !d_summary || cap_trace < 0 || (cap_trace > 0 && !d_trace))
+        return orbx_set_error(ORBX_E_ARG, "null d_chi2, d_outlier, summary or trace, or a negative cap_trace");
+    if (o.iterations < 1 || o.max_trials < 1) return orbx_set_error(ORBX_E_ARG, "iterations or max_trials < 1");
+    if (!wl_number(o.lambda_init) || !wl_number(o.huber_delta_visual) || !wl_number(o.huber_delta_inertial) || !wl_number(o.chi2_threshold) || !wl_number(o.gravity))
+        return orbx_set_error(ORBX_E_ARG, "lambda_init, a huber_delta, chi2_threshold or gravity is not a number");
+    if (camera.camera_model != 0 && camera.camera_model != 1) return orbx_set_error(ORBX_E_ARG, "camera_model is 0 (Pinhole) or 1 (Kannala-Brandt)");
+    if (n_solve > ORBVW_MAX_SOLVE_STATES) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBVW_MAX_SOLVE_STATES (32) solve states");
+    if (cap_edges > ORBVW_MAX_EDGES || n_points > ORBVW_MAX_POINTS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBVW_MAX_EDGES (2^20) edges or ORBVW_MAX_POINTS (2^18) points");
+    if (graph.n_states > ORBI_MAX_JOBS || n_edges > ORBI_MAX_JOBS || n_prior_jobs > ORBI_MAX_JOBS)
+        return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBI_MAX_JOBS (4096) states, inertial edges or prior jobs");
+    if (o.iterations > ORBWL_MAX_ITERATIONS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBWL_MAX_ITERATIONS (100) iterations");
+    if (o.max_trials > ORBWL_MAX_TRIALS) return orbx_set_error(ORBX_E_UNSUPPORTED, "more than ORBWL_MAX_TRIALS (10) trials in an iteration");
+    if (o.lambda_init == 0) return orbx_set_error(ORBX_E_UNSUPPORTED, "lambda_init == 0 (computeLambdaInit): this optimiser always sets a user value");
+    int device = -1;
+    if (int rc = orb_need_device(&device)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    Lease<WlWork> lease(g_wl_work);
+    ORB_TRY(lease.acquire(device));
+    lease.stream = s;                      // the call runs on the caller's stream: that one is waited on before the block goes back
+    volatile int32_t *const verdict = lease.w->h.as<int32_t>();
+    int32_t *d_verdict = nullptr;
+    ORB_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_verdict), lease.w->h.p, 0));
+
+    const WlPlan q(graph.n_states, n_solve, n_points, cap_edges, n_edges, n_prior_jobs);
+    double *const w = d_work;
+    int32_t *const slots = reinterpret_cast<int32_t *>(w + q.results);
+    auto slot = [&](int k) { return slots + 8 * k; };
+    int32_t *const point_off = reinterpret_cast<int32_t *>(w + q.point_off);
+    int32_t *const saved_iter = reinterpret_cast<int32_t *>(w + q.saved_iter);
+    double *pts[2] = {d_points, w + q.points2};
+    orbi_graph solve_states = graph;       // the update reaches the states [0, n_solve) only
+    solve_states.n_states = n_solve;
+
+    // both linearisations at the estimate (mode 0) or their errors at the trial point (mode 1, on `points`)
+    auto evaluate = [&](int mode, const double *points) -> int {
+        double *const ti = w + q.itotal + 2 * mode, *const tv = w + q.vtotal + 2 * mode;
+        if (int rc = orbi_linearize_device(graph, d_bank, cap, o.gravity, d_edges, n_edges, d_info, d_walk_info, d_priors, n_priors, d_prior_jobs, n_prior_jobs,
+                                           o.huber_delta_inertial, mode, w + q.iwork, w + q.ierr, w + q.ichi2, w + q.ichi2_prior, ti, mode ? nullptr : w + q.H_diag,
+                                           mode ? nullptr : w + q.H_off, mode ? nullptr : w + q.b, nullptr, nullptr, slot(mode ? WLR_TRY_I : WLR_LIN_I), stream))
+            return rc;
+        return orbvw_linearize_device(graph, calib, camera, n_solve, n_points, cap_edges, points, d_edge_state, d_edge_point, d_edge_z, d_edge_inv_sigma2, d_active,
+                                      o.huber_delta_visual, o.chi2_threshold, mode, point_off, mode ? nullptr : w + q.vwork, w + q.verr, d_chi2, tv,
+                                      mode ? nullptr : w + q.H_diag, mode ? nullptr : w + q.b, mode ? nullptr : w + q.Hll, mode ? nullptr : w + q.bl,
+                                      mode ? nullptr : w + q.Hlp, nullptr, slot(mode ? WLR_TRY_V : WLR_LIN_V), stream);
+    };
+    auto raised = [&]() { return stop && *stop != 0; };
+
+    ORB_TRY(wl_launch_begin(w + q.ctrl, d_summary, w + q.lambda, o.lambda_init > 0 ? o.lambda_init : 0.0, s));
+    WlDecide dc = {};
+    dc.g = solve_states, dc.iter = d_iter, dc.n_solve = n_solve;
+    dc.lin_inertial = w + q.itotal, dc.lin_visual = w + q.vtotal, dc.try_inertial = w + q.itotal + 2, dc.try_visual = w + q.vtotal + 2;
+    dc.out = w + q.out, dc.out_points = w + q.out_points, dc.solve_result = slot(WLR_SOLVE), dc.lambda = w + q.lambda, dc.ctrl = w + q.ctrl;
+    dc.saved = w + q.saved, dc.saved_iter = saved_iter, dc.trace = d_trace, dc.cap_trace = cap_trace, dc.max_trials = o.max_trials, dc.iterations = o.iterations;
+    dc.verdict = d_verdict;
+    int live = 0, stopped = 0, next = WL_NEXT_ITERATION;
+    for (int it = 0; it < o.iterations && next == WL_NEXT_ITERATION; ++it) {
+        if (raised()) { stopped = 1; break; }
+        if (int rc = evaluate(0, pts[live])) return rc;
+        next = WL_NEXT_TRIAL;
+        for (int trial = 0; trial < o.max_trials && next == WL_NEXT_TRIAL; ++trial) {
+            if (trial > 0 && raised()) { stopped = 1; break; }
+            if (int rc = orbvw_reduce_device(n_solve, graph.fixed, d_edges, n_edges, cap, w + q.H_diag, w + q.H_off, w + q.b, w + q.lambda, n_points, cap_edges, point_off,
+                                             d_edge_state, w + q.Hll, w + q.bl, w + q.Hlp, w + q.S, w + q.rhs, w + q.Hll_inv, w + q.tl, w + q.out, slot(WLR_REDUCE), stream))
+                return rc;
+            if (int rc = orbvw_solve_device(n_solve, w + q.S, w + q.rhs, w + q.b, w + q.lambda, w + q.dx, w + q.out, slot(WLR_SOLVE), stream)) return rc;
+            if (int rc = orbvw_backsub_device(n_solve, n_points, cap_edges, point_off, d_edge_state, w + q.Hlp, w + q.Hll_inv, w + q.bl, w + q.dx, w + q.lambda, pts[live],
+                                              w + q.xl, pts[1 - live], w + q.out_points, slot(WLR_BACKSUB), stream))
+                return rc;
+            if (trial == 0) ORB_TRY(wl_launch_push(solve_states, d_iter, n_solve, w + q.saved, saved_iter, s));   // a popped estimate is the pushed one
+            if (int rc = orbi_graph_oplus_device(solve_states, w + q.dx, d_iter, slot(WLR_OPLUS), stream)) return rc;
+            if (int rc = evaluate(1, pts[1 - live])) return rc;
+            dc.first = trial == 0;
+            verdict[WLV_NEXT] = -1;
+            ORB_TRY(wl_launch_decide(dc, s));
+            ORB_TRY(hipStreamSynchronize(s));                      // the wait of a trial: the verdict is in host memory
+            next = verdict[WLV_NEXT];
+            if (next != WL_NEXT_TRIAL && next != WL_NEXT_ITERATION && next != WL_NEXT_END)
+                return orbx_set_error(ORBX_E_NO_DEVICE, "the trial's verdict did not reach the page-locked block");
+            if (verdict[WLV_ACCEPTED]) live = 1 - live;            // the updated points are the estimate
+        }
+        if (stopped) break;
+    }
+    if (live != 0) ORB_TRY(hipMemcpyAsync(d_points, pts[1], 24 * (size_t)n_points, hipMemcpyDeviceToDevice, s));
+    // step 5 of the reference at the final estimate, whatever ended the loop
+    if (int rc = orbvw_linearize_device(graph, calib, camera, n_solve, n_points, cap_edges, d_points, d_edge_state, d_edge_point, d_edge_z, d_edge_inv_sigma2, nullptr,
+                                        o.huber_delta_visual, o.chi2_threshold, 2, point_off, nullptr, w + q.verr, d_chi2, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr, d_outlier, slot(WLR_CLASSIFY), stream))
+        return rc;
+    const WlEnd e = {w + q.lambda, w + q.ctrl, slot(WLR_CLASSIFY), slot(WLR_TRY_I), slot(WLR_REDUCE), cap_trace, stopped, d_summary, d_result};
+    ORB_TRY(wl_launch_end(e, s));
+    ORB_TRY(hipStreamSynchronize(s));      // the wait at the end: the page-locked block goes back to the pool
+    return ORBX_OK;
+}

@@ -4,7 +4,8 @@ Optimize::localFullBundleAdjustment (reference modules/Backend/Optimize.cpp:1064
 Levenberg-Marquardt loop: EdgeMono (G2oTypes.cpp:59-69) linearised on the VertexPose of an imu.Graph and on the map points, the Schur
 complement over the points, the ordered Cholesky solve of the reduced system and the back-substitution.  Every wrapper takes torch
 device tensors, enqueues on `stream` (torch's current stream when None, _lib.stream_arg) and neither copies nor waits.  The graph, the
-calibration, the camera and the inertial edges are imu.Graph, imu.Calib, vi.Camera and imu.EDGE.
+calibration, the camera and the inertial edges are imu.Graph, imu.Calib, vi.Camera and imu.EDGE.  For a caller who does not keep the
+loop: window_optimize_device (include/orbwl.h) closes it over these calls on the host, and is the one wrapper here that WAITS.
 """
 import ctypes as C
 
@@ -28,6 +29,53 @@ _SIGS = {
     "orbvw_backsub_device": [_i32, _i32, _i32] + [_vp] * 13,
 }
 _L = _lib.binder(_SIGS)
+
+# the window loop (include/orbwl.h): the four calls above closed into optimizer.optimize() by the library
+LOOP_MAX_ITERATIONS, LOOP_MAX_TRIALS, LOOP_TRACE, LOOP_SUMMARY = 100, 10, 13, 8
+R_REJECTED = 2
+
+
+class WindowLoopOptions(C.Structure):
+    """orbwl_loop_options: the iterations, g2o's trial bound, the user lambda init and the thresholds of window_optimize_device"""
+    _fields_ = [("iterations", C.c_int32), ("max_trials", C.c_int32), ("lambda_init", C.c_double), ("huber_delta_visual", C.c_double),
+                ("huber_delta_inertial", C.c_double), ("chi2_threshold", C.c_double), ("gravity", C.c_float), ("pad", C.c_float)]
+
+    @classmethod
+    def make(cls, gravity, iterations=10, lambda_init=1e0, max_trials=10, huber_delta_visual=HUBER_MONO, huber_delta_inertial=0.0, chi2_threshold=CHI2_MONO):
+        """localFullBundleAdjustment's defaults; beLarge is iterations=25, lambda_init=1e-2.  lambda_init > 0: setUserLambdaInit, < 0:
+        exactly 0, which g2o cannot reach (the refused-solve path); 0 is refused (ORBX_E_UNSUPPORTED)"""
+        return cls(int(iterations), int(max_trials), float(lambda_init), float(huber_delta_visual), float(huber_delta_inertial), float(chi2_threshold),
+                   float(gravity), 0.0)
+
+
+_LOOP_SIGS = {
+    "orbwl_window_work_doubles": (C.c_int64, [_i32] * 6),
+    "orbwl_window_optimize_device": [Graph, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, Calib, Camera, _i32, _i32, _i32] + [_vp] * 6
+                                    + [WindowLoopOptions] + [_vp] * 4 + [_i32] + [_vp] * 4,
+}
+_LL = _lib.binder(_LOOP_SIGS)
+
+
+def window_work_doubles(n_states, n_solve, n_points, cap_edges, n_edges, n_prior_jobs):
+    """orbwl_window_work_doubles: the doubles of window_optimize_device's d_work; host arithmetic, negative on a bad count"""
+    return int(_LL().orbwl_window_work_doubles(n_states, n_solve, n_points, cap_edges, n_edges, n_prior_jobs))
+
+
+def window_optimize_device(graph, d_iter, d_bank, cap, d_edges, n_edges, d_info, d_walk_info, d_priors, n_priors, d_prior_jobs, n_prior_jobs, calib, camera,
+                           n_solve, n_points, cap_edges, d_points, d_edge_state, d_edge_point, d_edge_z, d_edge_inv_sigma2, d_active, options, d_work, d_chi2,
+                           d_outlier, d_trace, cap_trace, d_summary, d_result, stop=None, stream=None):
+    """orbwl_window_optimize_device: localFullBundleAdjustment's optimize(iterations) and classification whole -- g2o's policy, push / pop,
+    the trace and the counters on the device, the loop closed by the host.  UNLIKE THE CALLS ABOVE IT WAITS on `stream`, once per trial and
+    once at the end.  d_iter i32 [n_states]; d_edges: imu.EDGE records with d_info / d_walk_info of imu.edge_information_device; options:
+    WindowLoopOptions; f64: d_points [n_points, 3] (in and out), d_work [window_work_doubles(...)] (scratch, 16-byte aligned), d_chi2
+    [cap_edges], d_trace [cap_trace, LOOP_TRACE] (a row per trial: inertial_loop.FIELDS), d_summary [LOOP_SUMMARY]; u8: d_active (None: every
+    edge), d_outlier [cap_edges]; stop: a ctypes c_int32 in HOST memory (or its address) that another thread raises, None for no flag."""
+    if stop is not None and not isinstance(stop, int):
+        stop = C.addressof(stop)
+    _lib.check(_LL().orbwl_window_optimize_device(graph, _p(d_iter), _p(d_bank), cap, _p(d_edges), n_edges, _p(d_info), _p(d_walk_info), _p(d_priors), n_priors,
+                                                  _p(d_prior_jobs), n_prior_jobs, calib, camera, n_solve, n_points, cap_edges, _p(d_points), _p(d_edge_state),
+                                                  _p(d_edge_point), _p(d_edge_z), _p(d_edge_inv_sigma2), _p(d_active), options, _p(d_work), _p(d_chi2),
+                                                  _p(d_outlier), _p(d_trace), cap_trace, _p(d_summary), _p(d_result), stop, _lib.stream_arg(stream)))
 
 
 def linearize_device(graph, calib, camera, n_solve, n_points, cap_edges, d_points, d_edge_state, d_edge_point, d_edge_z, d_edge_inv_sigma2,
