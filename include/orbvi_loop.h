@@ -40,8 +40,9 @@
  *     THAT VALUE; it exists so that the refusal path is reachable from the ABI, as forced_lambda_init is in tests/inertial_loop.py.  Then
  *     up to max_trials trials: push (Rwb, twb, v, bg, ba AND d_iter of both states), the damped solve, oplus, both error evaluations (mode
  *     1) at the trial point, temp = their totals, or DBL_MAX behind a refused solve; scale = computeScale + 1e-3; rho = (current - temp) /
- *     scale; accepted when rho > 0 and temp is finite: lambda *= max(1/3, min(1 - x*x*x, 2/3)) with x = 2*rho - 1 -- THE CUBE IS x*x*x, as
- *     k_pose_optimize (orbba.hip) has it, not pow --, nu = 2; otherwise lambda *= nu, nu *= 2 and the pop, which restores d_iter as well;
+ *     scale; accepted when rho > 0 and temp is finite: lambda *= max(1/3, min(1 - x*x*x, 2/3)) with x = 2*rho - 1 -- THE CUBE IS x*x*x,
+ *     not pow: csrc/orb_lm_policy.h's lm_cube, and k_pose_optimize's (orbba.hip) in its own copy of the policy --, nu = 2; otherwise
+ *     lambda *= nu, nu *= 2 and the pop, which restores d_iter as well;
  *     the iteration ends when rho >= 0 or the trials run out, the round when trials == max_trials, rho == 0 or lambda is not finite;
  *   - every edge is classified against chi2_threshold (mode 2), and d_active is the next round's level.
  * The policy's arithmetic is IEEE double in the expression order of inertial_loop.optimize, by ONE lane, published through LDS.

@@ -11,9 +11,7 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cmath>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <vector>
 
@@ -21,6 +19,7 @@
 #include "../../include/orbx.h"
 #include "orb_device.h"
 #include "orb_host.h"
+#include "orb_lm_policy.h"
 #include "orbba_camera.h"
 #include "orbba_problem.h"
 
@@ -725,30 +724,31 @@ int lm_loop(const LmPlan &q, const Arena &a, double *rb, hipStream_t s, const Ba
     };
     auto sum = [&](int from, int n) { return lm_sum(rb, from, n); };
 
-    double lam = 0.0, ni = 2.0, chi_initial = 0.0, current = 0.0;
+    LmPolicy p = {0.0, 2.0, 0.0, 0.0, 0, o.lower, o.upper};
+    double chi_initial = 0.0;
     int its = 0, trials_total = 0, rc = ORBX_OK;
     for (int it = 0; it < o.max_iterations; ++it) {
         evaluate(true, q.RB_CUR);
         bool have_current = false;
         if (it == 0) {
-            if (o.user_lambda_init > 0) lam = o.user_lambda_init;
+            if (o.user_lambda_init > 0) p.lam = o.user_lambda_init;
             else { // computeLambdaInit: tau * max |H_jj| over the free vertices
                 hipLaunchKernelGGL(k_lm_diag_max, dim3(1), dim3(256), 0, s, q.NF, a.I(q.ofree), a.D(q.oHpp), q.NL, a.D(q.oHll),
                                    a.D(q.orb) + q.RB_MAX);
                 if ((rc = read_back())) return rc;
-                lam = o.tau * rb[q.RB_MAX];
-                current = sum(q.RB_CUR, q.EB);
+                p.lam = o.tau * rb[q.RB_MAX];
+                p.current = sum(q.RB_CUR, q.EB);
                 have_current = true;
             }
-            ni = 2.0;
+            p.ni = 2.0;
         }
-        double rho = 0.0;
-        int qmax = 0;
+        lm_policy_iteration(p, p.current); // `current` itself arrives with the first trial's read-back, unless computeLambdaInit has fetched it
+        LmTrial t;
         do {
             // push(): keep the estimates
             ORB_TRY(hipMemcpyAsync(a.at(q.oRb), a.at(q.oR), q.est_bytes, hipMemcpyDeviceToDevice, s)); // R, t, P and their copies are laid out alike
-            hipLaunchKernelGGL(k_lm_points, dim3(q.LB), dim3(256), 0, s, q.NL, lam, a.D(q.oHll), a.D(q.obl), a.D(q.oinv), a.D(q.otl));
-            hipLaunchKernelGGL(k_lm_schur, dim3(q.NF * (q.NF + 1) / 2), dim3(256), 0, s, q.NF, q.NL, lam, a.I(q.ofree), a.I(q.oeo), a.D(q.oHpp),
+            hipLaunchKernelGGL(k_lm_points, dim3(q.LB), dim3(256), 0, s, q.NL, p.lam, a.D(q.oHll), a.D(q.obl), a.D(q.oinv), a.D(q.otl));
+            hipLaunchKernelGGL(k_lm_schur, dim3(q.NF * (q.NF + 1) / 2), dim3(256), 0, s, q.NF, q.NL, p.lam, a.I(q.ofree), a.I(q.oeo), a.D(q.oHpp),
                                a.D(q.obp), a.D(q.oHlp), a.D(q.oinv), a.D(q.otl), a.D(q.oS), a.D(q.orhs));
             int *const d_flag = reinterpret_cast<int *>(a.D(q.orb) + q.RB_FLAG);
             // ORBBA_VAR_CHOL = 1: the global-memory kernel, the parity twin (read per call)
@@ -767,45 +767,31 @@ int lm_loop(const LmPlan &q, const Arena &a, double *rb, hipStream_t s, const Ba
                 hipLaunchKernelGGL(k_lm_chol_solve, dim3(1), dim3(256), 0, s, q.N, a.D(q.oS), a.D(q.orhs), a.D(q.oxp), d_flag);
                 ORB_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(k_lm_backsub, dim3(q.LB), dim3(256), 0, s, q.NL, lam, a.I(q.olo), a.I(q.oep), a.I(q.oslot), a.D(q.oHlp), a.D(q.oxp),
+            hipLaunchKernelGGL(k_lm_backsub, dim3(q.LB), dim3(256), 0, s, q.NL, p.lam, a.I(q.olo), a.I(q.oep), a.I(q.oslot), a.D(q.oHlp), a.D(q.oxp),
                                a.D(q.obl), a.D(q.oinv), a.D(q.oxl), a.D(q.orb) + q.RB_SCL);
-            hipLaunchKernelGGL(k_lm_update_poses, dim3(1), dim3(256), 0, s, q.NF, lam, a.I(q.ofree), a.D(q.oxp), a.D(q.obp), a.D(q.oR), a.D(q.ot),
+            hipLaunchKernelGGL(k_lm_update_poses, dim3(1), dim3(256), 0, s, q.NF, p.lam, a.I(q.ofree), a.D(q.oxp), a.D(q.obp), a.D(q.oR), a.D(q.ot),
                                a.D(q.orb) + q.RB_POSE);
             hipLaunchKernelGGL(k_lm_update_points, dim3((3 * q.NL + 255) / 256), dim3(256), 0, s, 3 * q.NL, a.D(q.oxl), a.D(q.oP));
             evaluate(false, q.RB_TRY);
             if ((rc = read_back())) return rc;
-            if (!have_current) { current = sum(q.RB_CUR, q.EB); have_current = true; }
-            if (it == 0 && qmax == 0) chi_initial = current;
-            double temp = sum(q.RB_TRY, q.EB);
+            if (!have_current) { p.current = sum(q.RB_CUR, q.EB); have_current = true; }
+            if (it == 0 && p.qmax == 0) chi_initial = p.current;
+            const double temp = sum(q.RB_TRY, q.EB);
             int ok2 = 0;
             memcpy(&ok2, rb + q.RB_FLAG, sizeof(int));
-            if (!ok2) temp = std::numeric_limits<double>::max();
             double scale = rb[q.RB_POSE]; // poses first, then the points block by block
             for (int b = 0; b < q.LB; ++b) scale += rb[q.RB_SCL + b];
-            scale += 1e-3;
-            rho = (current - temp) / scale;
+            // one total and the whole of computeScale, summed in its order: the policy's + 0.0 on each is exact
+            t = lm_policy_trial(p, ok2 != 0, temp, 0.0, scale, 0.0);
             ++trials_total;
-            if (rho > 0 && std::isfinite(temp)) {
-                double alpha = 1.0 - std::pow(2 * rho - 1, 3);
-                alpha = std::min(alpha, o.upper);
-                lam *= std::max(o.lower, alpha);
-                ni = 2.0;
-                current = temp;
-            } else {
-                lam *= ni;
-                ni *= 2;
-                // pop(): restore
-                ORB_TRY(hipMemcpyAsync(a.at(q.oR), a.at(q.oRb), q.est_bytes, hipMemcpyDeviceToDevice, s));
-                if (!std::isfinite(lam)) break;
-            }
-            ++qmax;
-        } while (rho < 0 && qmax < o.max_trials);
+            if (!t.accepted) ORB_TRY(hipMemcpyAsync(a.at(q.oR), a.at(q.oRb), q.est_bytes, hipMemcpyDeviceToDevice, s)); // pop(): restore
+        } while (lm_policy_again(p, t, o.max_trials));
         ++its;
-        if (qmax == o.max_trials || rho == 0 || !std::isfinite(lam)) break; // Terminate
+        if (lm_policy_terminate(p, o.max_trials)) break;
     }
     evaluate(false, q.RB_TRY);
     ORB_TRY(hipGetLastError());
-    out->iterations = its, out->trials = trials_total, out->lambda = lam, out->chi_initial = chi_initial;
+    out->iterations = its, out->trials = trials_total, out->lambda = p.lam, out->chi_initial = chi_initial;
     return ORBX_OK;
 }
 
@@ -1340,6 +1326,8 @@ __global__ __launch_bounds__(256) void k_pose_optimize(BaCam cam, int rounds, in
                         lam = 1e-5 * mx;
                         ni = 2.0;
                     }
+                    // g2o's trial policy, by every lane: THE ONE COPY that is not orb_lm_policy.h's.  With the header's calls the kernel
+                    // kept its registers and every byte of its results and took 1.5 to 3.5 % longer ("The policy, written once")
                     double rho = 0.0;
                     int qmax = 0;
                     do {

@@ -4,8 +4,9 @@
 // ONE WORKGROUP of 512 threads runs the whole optimisation in one launch.  Every stage of an iteration is a device function of
 // csrc/orbvi_stages.h, the one the staged call's kernel runs (orbi_linearize_device, orbvi_linearize_device, orbvi_solve_device,
 // orbi_graph_oplus_device): no formula is restated here, so a linearisation, a solve and an update inside the loop give the bytes of the
-// staged calls on the same input.  What is here is the policy (tests/inertial_loop.py's optimize / pose_full / pose_inertial line by
-// line, in double), the vertices' push and pop with their update counters, the reset of the frame's pose ahead of a round and the trace.
+// staged calls on the same input.  Nor is the trial policy's arithmetic: it is orb_lm_policy.h's, run by one lane.  What is here is the
+// step machine around it (tests/inertial_loop.py's pose_full / pose_inertial and the shape of its optimize), the vertices' push and pop
+// with their update counters, the reset of the frame's pose ahead of a round and the trace.
 //
 // Shape.  The loop is a sequence of STEPS, each of one kind: LIN evaluates both linearisations at the estimate (mode 0), TRIAL their
 // errors at a trial point (mode 1), CLASSIFY the inliers behind a round (mode 2).  Behind the evaluation ONE LANE (thread 0) takes the
@@ -32,6 +33,7 @@
 #include "../../include/orbx.h"
 #include "orb_device.h"
 #include "orb_host.h"
+#include "orb_lm_policy.h"
 #include "orb_math.h"
 #include "orbi_graph_device.h"
 #include "orbvi_stages.h"
@@ -54,7 +56,7 @@ enum { F_WORK = 0, F_ERR = F_WORK + ORBI_EDGE_WORK, F_CHI2 = F_ERR + 9, F_TOTAL 
 static_assert(F_WORDS <= ORBVI_LOOP_FIXED_WORK, "orbvi_loop.h states the fixed part of the scratch");
 static_assert(ORBVI_LOOP_EDGE_WORK == ORBVI_EDGE_WORK + 2, "an edge's row of orbvi_linearize_device and its error");
 enum { SUM_ROUND = 6, SUM_TRIALS = 24, SUM_OVERFLOW = 25 };
-static_assert(SUM_OVERFLOW < ORBVI_LOOP_SUMMARY && 13 == ORBVI_LOOP_TRACE, "orbvi_loop.h states the summary and a row of the trace");
+static_assert(SUM_OVERFLOW < ORBVI_LOOP_SUMMARY && LM_TRACE_ROW == ORBVI_LOOP_TRACE, "orbvi_loop.h states the summary and a row of the trace, which lm_trace_row writes");
 constexpr int LOOP_N = 2;                                       // key frame, frame
 constexpr int LOOP_VT = 2, LOOP_T = VI_T / LOOP_VT;             // the threads of the workgroup, each two of the visual stage's 1024
 constexpr int LOOP_STEPS_CAP = ORBVI_LOOP_MAX_ROUNDS * (ORBVI_LOOP_MAX_ITERATIONS * (1 + ORBVI_LOOP_MAX_TRIALS) + 1);
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(LOOP_T) void k_vi_pose_loop(const LoopArgs)     // 
             vi_linearize_group<LOOP_VT>(fresh_args().vi, uniform(s_q[Q_KIND]), 0, fresh_tid(), s_part, s_pose, s_vcnt, s_i);
             __syncthreads();
         }
-        if (fresh_tid() == 0) {                                    // ---- the policy: tests/inertial_loop.py's optimize, in its expression order
+        if (fresh_tid() == 0) {                                    // ---- the decision: orb_lm_policy.h's arithmetic, in inertial_loop.optimize's shape
             const LoopArgs &a = fresh_args();
             const int kind = s_q[Q_KIND], visual = s_q[Q_VISUAL];
             const int round = s_q[Q_ROUND];
@@ -175,49 +177,27 @@ __global__ __launch_bounds__(LOOP_T) void k_vi_pose_loop(const LoopArgs)     // 
             s_q[Q_POP] = s_q[Q_PUSH] = s_q[Q_SOLVE] = s_q[Q_INIT] = s_q[Q_RESET] = 0;
             if (kind == K_LIN) {                                   // computeActiveErrors, activeRobustChi2, buildSystem
                 const double ti = a.fac.total[1];
-                s_p[P_CUR] = visual ? ti + a.vi.total[1] : ti;
+                LmPolicy p = {};                                   // lambda and nu stay where they are, in LDS
+                lm_policy_iteration(p, visual ? ti + a.vi.total[1] : ti);
+                s_p[P_CUR] = p.current, s_p[P_RHO] = p.rho, s_q[Q_QMAX] = p.qmax;
                 if (it == 0) s_q[Q_INIT] = 1, s_p[P_NI] = 2.0;     // computeLambdaInit: the value is taken behind the assembly
-                s_p[P_RHO] = 0.0, s_q[Q_QMAX] = 0;
                 s_q[Q_PUSH] = 1, s_q[Q_SOLVE] = 1, s_q[Q_KIND] = K_TRIAL;
             } else if (kind == K_TRIAL) {
-                double lam = s_p[P_LAM], ni = s_p[P_NI];
-                const double current = s_p[P_CUR];
+                LmPolicy p = {s_p[P_LAM], s_p[P_NI], s_p[P_CUR], s_p[P_RHO], qmax};
+                const double lam = p.lam, current = p.current;
                 const bool ok = !s_q[Q_REFUSED];
-                const double ti = a.fac.total[1], tv = visual ? a.vi.total[1] : 0.0;
-                const double temp = ok ? ti + tv : DBL_MAX;        // a refused solve
-                const double scale_pose = s_out[0];
-                const double scale = (scale_pose + 0.0) + 1e-3;    // computeScale + 1e-3
-                const double rho = (current - temp) / scale;
-                const bool accepted = rho > 0 && isfinite(temp);
+                const double ti = a.fac.total[1], tv = visual ? a.vi.total[1] : 0.0, scale_pose = s_out[0];
+                const LmTrial t = lm_policy_trial(p, ok, ti, tv, scale_pose, 0.0);   // computeScale has no points' side here
                 const int row = s_q[Q_ROWS];
-                if (row < a.cap_trace) {
-                    double *r = a.trace + (size_t)ORBVI_LOOP_TRACE * row;
-                    r[0] = it, r[1] = qmax, r[2] = lam, r[3] = current, r[4] = temp, r[5] = scale, r[6] = rho, r[7] = ok ? 1.0 : 0.0;
-                    r[8] = ti, r[9] = tv, r[10] = scale_pose, r[11] = 0.0, r[12] = accepted ? 1.0 : 0.0;
-                }
+                if (row < a.cap_trace) lm_trace_row(a.trace + (size_t)ORBVI_LOOP_TRACE * row, it, qmax, lam, current, t, ok, ti, tv, scale_pose, 0.0);
                 s_q[Q_ROWS] = row + 1, ++s_q[Q_TRIALS];
-                bool left = false;                                 // the trial loop was left on a lambda that is not finite
-                if (accepted) {
-                    const double x = 2 * rho - 1, alpha = 1.0 - x * x * x;
-                    const double m = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;
-                    lam = lam * (m > (1.0 / 3.0) ? m : (1.0 / 3.0));
-                    ni = 2.0;
-                    s_p[P_CUR] = temp;
-                    ++s_q[Q_ACCEPTED], ++s_q[Q_ALL_ACCEPTED];
-                } else {
-                    lam = lam * ni;
-                    ni = ni * 2;
-                    s_q[Q_POP] = 1;                                // pop: the vertices and their update counters
-                    ++s_q[Q_ALL_REJECTED];
-                    left = !isfinite(lam);
-                }
-                if (!left) ++qmax;
-                s_p[P_LAM] = lam, s_p[P_NI] = ni, s_p[P_RHO] = rho, s_q[Q_QMAX] = qmax;
-                if (!left && rho < 0 && qmax < a.o.max_trials) s_q[Q_SOLVE] = 1;      // the next trial from the popped estimate: the push still holds
+                if (t.accepted) ++s_q[Q_ACCEPTED], ++s_q[Q_ALL_ACCEPTED];
+                else s_q[Q_POP] = 1, ++s_q[Q_ALL_REJECTED];        // pop: the vertices and their update counters
+                s_p[P_LAM] = p.lam, s_p[P_NI] = p.ni, s_p[P_CUR] = p.current, s_p[P_RHO] = p.rho, s_q[Q_QMAX] = p.qmax;
+                if (lm_policy_again(p, t, a.o.max_trials)) s_q[Q_SOLVE] = 1;          // the next trial from the popped estimate: the push still holds
                 else {
                     ++s_q[Q_ITS], ++it;
-                    const bool terminate = qmax == a.o.max_trials || rho == 0 || !isfinite(lam);
-                    if (terminate || it >= a.o.iterations[round]) round_ends = true;
+                    if (lm_policy_terminate(p, a.o.max_trials) || it >= a.o.iterations[round]) round_ends = true;
                     else s_q[Q_IT] = it, s_q[Q_KIND] = K_LIN;
                 }
             }

@@ -15,7 +15,7 @@
 #pragma clang fp contract(off)
 
 static_assert(sizeof(orbwl_loop_options) == 48, "orbwl.h fixes this layout");
-static_assert(ORBWL_TRACE == 13 && ORBWL_SUMMARY == 8, "orbwl.h states a row of the trace and the summary");
+static_assert(ORBWL_TRACE == LM_TRACE_ROW && ORBWL_SUMMARY == 8, "orbwl.h states a row of the trace, which lm_trace_row writes, and the summary");
 
 namespace {
 
@@ -57,11 +57,7 @@ __global__ __launch_bounds__(WL_T) void k_vwl_decide(const WlDecide a)
         const double ti = a.try_inertial[1], tv = a.try_visual[1], scale_pose = a.out[0], scale_points = a.out_points[0];
         const LmTrial t = lm_policy_trial(p, ok, ti, tv, scale_pose, scale_points);
         const int row = q[WLI_ROWS];
-        if (row < a.cap_trace) {
-            double *r = a.trace + (size_t)ORBWL_TRACE * row;
-            r[0] = it, r[1] = trial, r[2] = lam, r[3] = current, r[4] = t.temp, r[5] = t.scale, r[6] = t.rho, r[7] = ok ? 1.0 : 0.0;
-            r[8] = ti, r[9] = tv, r[10] = scale_pose, r[11] = scale_points, r[12] = t.accepted ? 1.0 : 0.0;
-        }
+        if (row < a.cap_trace) lm_trace_row(a.trace + (size_t)ORBWL_TRACE * row, it, trial, lam, current, t, ok, ti, tv, scale_pose, scale_points);
         q[WLI_ROWS] = row + 1;
         if (t.accepted) ++q[WLI_ACCEPTED]; else ++q[WLI_REJECTED];
         if (!ok) ++q[WLI_REFUSED];

@@ -166,7 +166,10 @@ def test_the_documents_say_what_the_call_does_and_that_it_waits():
     assert "orbvw" not in header("orbwl.h")                          # like orbm.h it names the visual window's calls by what they do
     for doc, name in ((readme, "README.md"), (design, "DESIGN.md"), (integ, "INTEGRATION.md")):
         assert NAME in doc and "orbwl.h" in doc, name
-    assert "The window loop closed by the host" in design and "tools/vw_window_loop_latency.py" in design and "two copies" in design
+    assert "The window loop closed by the host" in design and "tools/vw_window_loop_latency.py" in design
+    # the policy stands once: DESIGN.md names the header as the one definition, the loops that call it, and the one that measured slower with it
+    assert ("`csrc/orb_lm_policy.h` is the one definition of g2o's trial policy" in design and "`k_vwl_decide`, `k_vi_pose_loop` and the host's `lm_loop` call it" in design
+            and "`k_pose_optimize` alone keeps its copy" in design and "two copies" not in design and "profiles/lm_policy_shared.txt" in design)
     assert "once per trial and once at the end" in design and "once per trial and once at the end" in integ
     order = ["orbm_inertial_window_problem_device", "orbi_graph_init_device", "orbi_edge_information_device", NAME, "orbi_graph_recover_device",
              "orbm_local_ba_apply_device", "orbi_prior_information_device"]

@@ -38,7 +38,10 @@ def test_the_stages_and_the_policy_are_written_once():
     for fn in POLICY:
         assert len(re.findall(r"^__host__ __device__ __forceinline__ \w+ %s\(" % fn, policy, re.M)) == 1, fn
         assert not defines_itself(loop, fn) and re.search(r"\b%s\(" % fn, code), fn
-    assert "x * x * x" in policy and "pow" not in re.sub(r"//[^\n]*", "", policy) and "DBL_MAX" in policy and "1e-3" in policy
+    # the cube stands once, behind lm_cube: x * x * x in its device branch, and the header's only pow( is its host branch
+    bare = re.sub(r"//[^\n]*", "", policy)
+    cube = re.search(r"double lm_cube\(double x\)\s*\{\s*#ifdef __HIP_DEVICE_COMPILE__\s*return x \* x \* x;\s*#else\s*return pow\(x, 3\);\s*#endif\s*\}", bare)
+    assert cube and bare.count("pow") == 1 and bare.count("x * x * x") == 1 and "DBL_MAX" in policy and "1e-3" in policy
     # the driver: behind its banner nothing but calls of the staged entry points and of orbwl.hip's four launches
     driver = re.sub(r"//[^\n]*", "", host[host.index('#include "orbwl_kernels.h"'):])
     assert "hipLaunchKernelGGL" not in driver and "__global__" not in driver and "__device__" not in driver
