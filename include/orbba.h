@@ -139,7 +139,7 @@ int orbba_local_bundle_adjustment_device(const orbba_problem *p, orbba_lm_result
  * correspondences come back unchanged with n_inliers = 0 (:491). */
 typedef struct orbba_pose_problem {
     double fx, fy, cx, cy;
-    double huber_delta;             /* (double)sqrtf(5.991), :466 */
+    double huber_delta;             /* (double)sqrtf(5.991), :466; <= 0 disables the robust kernel, as for orbba_problem */
     int32_t n_frames;
     int32_t rounds, iterations;     /* 0 = the reference's 4 and 10 (:495) */
     const int32_t *edge_off;        /* n_frames + 1: frame f owns edges [edge_off[f], edge_off[f+1]) */

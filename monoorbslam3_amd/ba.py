@@ -173,9 +173,11 @@ _SIGS = {
 _L = _lib.binder(_SIGS)   # the library with the orbba_* signatures set, once (include/orbba.h)
 
 
-def pose_optimize_batch(cam, pose_R, pose_t, edge_off, points, edge_z, edge_inv_sigma2, huber_delta=HUBER_MONO, device=-1):
+def pose_optimize_batch(cam, pose_R, pose_t, edge_off, points, edge_z, edge_inv_sigma2, huber_delta=HUBER_MONO, device=-1, rounds=0,
+                        iterations=0):
     """Optimize::poseOptimize (Optimize.cpp:444-545) for many frames at once; frame f owns edges
-    edge_off[f]:edge_off[f+1].  Returns dict(pose_R, pose_t, inlier, n_inliers, chi2, kernel_ms)."""
+    edge_off[f]:edge_off[f+1].  rounds, iterations: orbba_pose_problem's fields (0 = the reference's 4 and 10).  Returns
+    dict(pose_R, pose_t, inlier, n_inliers, chi2, kernel_ms)."""
     fn = _L().orbba_pose_optimize_batch
     f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)  # noqa: E731
     R, t = f8(pose_R).reshape(-1, 9), f8(pose_t).reshape(-1, 3)
@@ -185,7 +187,7 @@ def pose_optimize_batch(cam, pose_R, pose_t, edge_off, points, edge_z, edge_inv_
     out = {"pose_R": np.zeros((B, 3, 3)), "pose_t": np.zeros((B, 3)), "inlier": np.zeros(max(ne, 1), np.uint8),
            "n_inliers": np.zeros(B, np.int32), "chi2": np.zeros(max(ne, 1))}
     vp = lambda a: a.ctypes.data  # noqa: E731
-    prob = _PoseProblem(cam[0], cam[1], cam[2], cam[3], huber_delta, B, 0, 0, vp(off), vp(R), vp(t), vp(P), vp(z), vp(w), *_cam_tail(cam))
+    prob = _PoseProblem(cam[0], cam[1], cam[2], cam[3], huber_delta, B, rounds, iterations, vp(off), vp(R), vp(t), vp(P), vp(z), vp(w), *_cam_tail(cam))
     res = _PoseResult(vp(out["pose_R"]), vp(out["pose_t"]), vp(out["inlier"]), vp(out["n_inliers"]), vp(out["chi2"]), 0.0)
     _lib.check(fn(C.byref(prob), C.byref(res), device))
     out["inlier"] = out["inlier"][:ne].astype(bool)
@@ -209,10 +211,11 @@ def pose_drop_outliers_device(n2, d_edge_off, d_edge_kp, d_inlier, d_frame_mp, s
 
 
 def pose_optimize_batch_device(cam, d_R, d_t, d_edge_off, d_points, d_z, d_w, d_R_out, d_t_out, d_inlier, d_n_inliers, d_chi2,
-                               n_frames=1, huber_delta=HUBER_MONO, stream=None):
-    """orbba_pose_optimize_batch_device: every array a torch device tensor (float64 / int32 / uint8), nothing copied."""
+                               n_frames=1, huber_delta=HUBER_MONO, stream=None, rounds=0, iterations=0):
+    """orbba_pose_optimize_batch_device: every array a torch device tensor (float64 / int32 / uint8), nothing copied.  rounds,
+    iterations: as for pose_optimize_batch."""
     fn = _L().orbba_pose_optimize_batch_device
-    prob = _PoseProblem(cam[0], cam[1], cam[2], cam[3], huber_delta, n_frames, 0, 0, d_edge_off.data_ptr(), d_R.data_ptr(),
+    prob = _PoseProblem(cam[0], cam[1], cam[2], cam[3], huber_delta, n_frames, rounds, iterations, d_edge_off.data_ptr(), d_R.data_ptr(),
                         d_t.data_ptr(), d_points.data_ptr(), d_z.data_ptr(), d_w.data_ptr(), *_cam_tail(cam))
     res = _PoseResult(d_R_out.data_ptr(), d_t_out.data_ptr(), d_inlier.data_ptr(), d_n_inliers.data_ptr(), d_chi2.data_ptr(), 0.0)
     _lib.check(fn(C.byref(prob), C.byref(res), _lib.stream_arg(stream)))

@@ -253,7 +253,9 @@ def pose_optimize(cam, R0, t0, Pw, z, inv_sigma2, huber_delta, rounds=4, iterati
     EdgeSE3Project3DOnlyPose (G2oTypes.h:209-236, G2oTypes.cpp:27-34) per matched map point, Huber kernel on every edge;
     four rounds of optimize(10), each restarted from the initial pose (:497) on the edges classified as inliers by the
     previous round (chi2 <= 5.991, :506-516; the `iter == 2` test at :518 never fires, so the kernel stays).  The LM loop
-    is g2o 20201223's OptimizationAlgorithmLevenberg on the 6x6 system.  Returns dict(R, t, inlier, n_inliers, chi2)."""
+    is g2o 20201223's OptimizationAlgorithmLevenberg on the 6x6 system.  huber_delta <= 0: no robust kernel, as in
+    robust_chi2.  Returns dict(R, t, inlier, n_inliers, chi2, trace); trace holds one tuple per trial: (round, iteration,
+    trial within it, lambda used, current chi2, the trial's chi2, computeScale() + 1e-3, rho, the solve succeeded)."""
     R0 = np.array(R0, np.float64).reshape(3, 3)
     t0 = np.array(t0, np.float64).reshape(3)
     Pw = np.asarray(Pw, np.float64).reshape(-1, 3)
@@ -261,6 +263,8 @@ def pose_optimize(cam, R0, t0, Pw, z, inv_sigma2, huber_delta, rounds=4, iterati
     om = np.asarray(inv_sigma2, np.float64)
     n = len(Pw)
     inlier = np.ones(n, bool)
+    trace = []
+
     def err(R, t):
         Pc = Pw @ R.T + t
         e = z - project(cam, Pc)
@@ -271,9 +275,9 @@ def pose_optimize(cam, R0, t0, Pw, z, inv_sigma2, huber_delta, rounds=4, iterati
         return om * (e * e).sum(1)
 
     if n < 3:  # :491
-        return {"R": R0, "t": t0, "inlier": inlier, "n_inliers": 0, "chi2": chi_of(R0, t0)}
+        return {"R": R0, "t": t0, "inlier": inlier, "n_inliers": 0, "chi2": chi_of(R0, t0), "trace": trace}
     R, t = R0, t0
-    for _ in range(rounds):
+    for rnd in range(rounds):
         R, t = R0.copy(), t0.copy()  # vPose->setEstimate(Tcw) (:497)
         act = inlier.copy()          # initializeOptimization(0): level-0 edges
         lam, ni = 0.0, 2.0
@@ -285,8 +289,9 @@ def pose_optimize(cam, R0, t0, Pw, z, inv_sigma2, huber_delta, rounds=4, iterati
                 Jp = proj_jacobian(cam, Pc)
                 Jq = np.concatenate([Jp @ hat(Pc), -Jp], axis=2)
                 rw = np.ones(n)
-                out = chi > huber_delta * huber_delta
-                rw[out] = huber_delta / np.sqrt(chi[out])
+                if huber_delta > 0:
+                    out = chi > huber_delta * huber_delta
+                    rw[out] = huber_delta / np.sqrt(chi[out])
                 W = np.where(act, rw * om, 0.0)
                 H = np.einsum("e,eki,ekj->ij", W, Jq, Jq)
                 b = -np.einsum("e,eki,ek->i", W, Jq, e)
@@ -306,6 +311,7 @@ def pose_optimize(cam, R0, t0, Pw, z, inv_sigma2, huber_delta, rounds=4, iterati
                     temp = robust_chi2(chi_of(R, t), huber_delta, act) if ok2 else np.finfo(np.float64).max
                     scale = float((x * (lam * x + b)).sum()) + 1e-3
                     rho = (current - temp) / scale
+                    trace.append((rnd, it, qmax, lam, current, temp, scale, rho, ok2))
                     if rho > 0 and np.isfinite(temp):
                         lam *= max(lower, min(1.0 - (2 * rho - 1) ** 3, upper))
                         ni = 2.0
@@ -322,4 +328,4 @@ def pose_optimize(cam, R0, t0, Pw, z, inv_sigma2, huber_delta, rounds=4, iterati
                 if qmax == max_trials or rho == 0 or not np.isfinite(lam):
                     break
         inlier = ~(chi_of(R, t) > 5.991)  # :503-516 (outliers get computeError() first, so every edge is re-evaluated)
-    return {"R": R, "t": t, "inlier": inlier, "n_inliers": int(inlier.sum()), "chi2": chi_of(R, t)}
+    return {"R": R, "t": t, "inlier": inlier, "n_inliers": int(inlier.sum()), "chi2": chi_of(R, t), "trace": trace}

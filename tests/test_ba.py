@@ -294,23 +294,24 @@ def test_gpu_ba_entry_points_lease_their_workspace():
 
 # ---------------------------------------------------------------------------------------------------------------
 # Optimize::poseOptimize for a batch of frames (a14b)
-def _pose_frames(sizes, seed, outlier_frac=0.1):
+def _pose_frames(sizes, seed, outlier_frac=0.1, rot=0.01, trans=0.05, depth=(6, 30)):
     """Per frame: a true pose, points in front of it, exact projections + noise of one pixel times the level scale,
-    weights 1/scale^2, a share of gross outliers, and a perturbed initial pose."""
+    weights 1/scale^2, a share of gross outliers, and a perturbed initial pose (sigmas rot rad / trans m).  depth: the range
+    of the points' depths; their lateral spread shrinks with its upper end, so they stay inside the same field of view."""
     from oracle import ba_ref
     cam = (718.856, 718.856, 607.19, 185.22)
     rng = np.random.RandomState(seed)
     R0, t0, P, Z, W, off = [], [], [], [], [], [0]
     for n in sizes:
         Rt, tt = ba_ref.se3_exp(np.concatenate([rng.normal(0, 0.2, 3), rng.normal(0, 1.0, 3)]))
-        Pc = np.stack([rng.uniform(-8, 8, n), rng.uniform(-3, 3, n), rng.uniform(6, 30, n)], 1)
+        Pc = np.stack([rng.uniform(-8, 8, n) * depth[1] / 30, rng.uniform(-3, 3, n) * depth[1] / 30, rng.uniform(depth[0], depth[1], n)], 1)
         Pw = (Pc - tt) @ Rt  # Pc = R Pw + t
         scale = 1.2 ** rng.randint(0, 8, n)
         z = np.stack([cam[0] * Pc[:, 0] / Pc[:, 2] + cam[2], cam[1] * Pc[:, 1] / Pc[:, 2] + cam[3]], 1)
         z += rng.normal(0, 1, (n, 2)) * scale[:, None]
         bad = rng.uniform(size=n) < outlier_frac
         z[bad] += rng.uniform(15, 80, (int(bad.sum()), 2)) * rng.choice([-1, 1], (int(bad.sum()), 2))
-        dR, dt = ba_ref.se3_exp(np.concatenate([rng.normal(0, 0.01, 3), rng.normal(0, 0.05, 3)]))
+        dR, dt = ba_ref.se3_exp(np.concatenate([rng.normal(0, rot, 3), rng.normal(0, trans, 3)]))
         R0.append(dR @ Rt); t0.append(dR @ tt + dt)
         P.append(Pw); Z.append(z); W.append(1.0 / (scale * scale)); off.append(off[-1] + n)
     cat = lambda xs, w: np.concatenate(xs) if off[-1] else np.zeros((0, w))  # noqa: E731
