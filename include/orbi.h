@@ -88,7 +88,8 @@
  * What poseInertialOptimize, poseFullOptimize, localInertialBundleAdjustment and localFullBundleAdjustment (Optimize.cpp:547-608,
  * :610-760, :960-1060, :1090-1250) do per iteration with their inertial edges, for a caller who keeps g2o's solver (orbba_linearize is
  * the same layer for the visual edges): computeError, linearizeOplus, the information matrices and constructQuadraticForm.  The loops
- * themselves, the visual edges in the IMU-pose parametrisation and the edges of the IMU initialisation are not here.  Same rules as
+ * themselves, the visual edges in the IMU-pose parametrisation and the edges of the IMU initialisation are not here.  (Since then localInertialBundleAdjustment's
+ * loop is orbil.h's, whole in one launch on the stage code of these calls, and the tracker's two are in the library as well.)  Same rules as
  * above: handle-less, one stream, no allocation, no host wait, arguments first (ORBX_E_ARG), then ORBX_E_NO_DEVICE, no CPU path,
  * d_result 8 x int32 written by every call.
  *

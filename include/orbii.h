@@ -9,7 +9,8 @@
  * recovery, for a caller whose pose table, state rows, record bank and prior slots live in device memory.  The solve of the damped system
  * is the ordered Cholesky for N <= 480 that the library already has (INTEGRATION.md names the call and spells the chain out); THE LOOP
  * ITSELF IS NOT HERE: the accept / reject decision of a trial is the caller's, who reads two scalars back per trial.
- * fullInertialOptimize and gravityOptimize are not here either.
+ * fullInertialOptimize and gravityOptimize are not here either.  (localInertialBundleAdjustment, the mapper's other optimiser on inertial
+ * edges alone, is whole in the library, loop included: orbil.h.)
  *
  * Rules: those of orbi.h.  Handle-less `*_device` entry points, one stream (NULL is stream 0 itself), nothing allocated, no host wait.
  * Arguments are checked first (ORBX_E_ARG: a null pointer, a negative or zero capacity, fewer than two key frames, a kind or mode that

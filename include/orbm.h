@@ -1078,7 +1078,8 @@ int orbm_cull_map_points_device(orbm_t *h, int32_t *d_recent, int32_t *d_n_recen
  *   orbm_inertial_window_velocity_prior_device
  *   orbm_build_observations_device -> orbm_refresh_points_device (d_sel = d_point_row; mp->update(), :1305)
  * (The recover runs ahead of the apply, which reads its poses; the other calls behind the loop are independent of each other.)
- * localInertialBundleAdjustment, inertialOptimize / fullInertialOptimize and the loop itself are not here.
+ * inertialOptimize / fullInertialOptimize and the loop itself are not here.  localInertialBundleAdjustment, what the mapper runs in front of
+ * this function when the tracker is RECENTLY_LOST, is the next section ("The inertial chain on the device-resident map") with orbil.h.
  * The two calls follow this header's rules for the map side, as "Local bundle adjustment on the device-resident map" states them:
  * device pointers only and deliberately NO host-pointer twin; no allocation, handle scratch or host wait; results written, not
  * accumulated; the same bytes on every run; every index that comes from device memory is distrusted -- dropped and counted, never
@@ -1167,6 +1168,60 @@ int orbm_inertial_window_problem_device(orbm_t *h, const orbm_kf_table *kf, cons
  * One launch of one wave.  ORBX_E_ARG: a null pointer, a negative count; then ORBX_E_NO_DEVICE.  Enqueued on `stream`. */
 int orbm_inertial_window_velocity_prior_device(orbm_t *h, struct orbi_prior *d_priors, int n_priors, const float *d_src, int n_src,
                                                const int32_t *d_recover_jobs, const int32_t *d_prior_jobs, int32_t *d_result, void *stream);
+
+/* ---- The inertial chain on the device-resident map ---------------------------------------------------------------------------------
+ * Optimize::localInertialBundleAdjustment (modules/Backend/Optimize.cpp:953-1062), which the mapper runs when the tracker is
+ * RECENTLY_LOST (LocalMapping.cpp:47-48), directly in front of localFullBundleAdjustment, for a caller whose key-frame table, state
+ * rows, record bank and priors live in device memory.  Its graph is the last min(n, 10 or 20) key frames with every pose a constant; its
+ * formulas are orbi_factors.h's and its optimisation is orbil.h's, one launch.  This section is the piece between the map and those calls:
+ *   orbm_inertial_chain_problem_device           :965-1029  steps 1 and 3: the states, their fixed flags, the edges and the job lists
+ *   orbm_inertial_chain_velocity_priors_device   :1044-1053 (KeyFrame::setVelocity)  velo_priori of EVERY window key frame
+ * and the mapper step is one chain on one stream
+ *   the assembly -> orbi_graph_init_device (d_init_jobs) -> orbi_edge_information_device (d_inertial_edges)
+ *     -> orbil_chain_optimize_device (d_fixed, d_inertial_edges) -> orbi_graph_recover_device (d_recover_jobs)
+ *     -> orbi_set_bias_device (d_bias_ids, the recover's d_bias) -> orbm_inertial_chain_velocity_priors_device (d_velo_jobs)
+ * in which the host knows every size (n_window states, n_window - 1 edges): THE CHAIN HAS NO READ-BACK AT ALL.  The rules are those of
+ * "The inertial local BA window on the device-resident map": device pointers only, no host-pointer twin, no allocation, handle scratch
+ * or host wait, results written, the same bytes on every run, every index from device memory distrusted.  This header does not include
+ * the headers of the calls above: the job lists are int32 arrays in their documented layouts.
+ *
+ * orbm_inertial_chain_problem_device.  d_window [n_window] (device): the slots of getRecentKeyFrames(numOpt), OLDEST FIRST; the caller
+ * computes numOpt = min(n, 10 or 20) (:959-963).  d_bad [n_kf]: the key-frame table's bad flags.  d_kf_imu [n_kf][3] (device) = per key
+ * frame (its row of the 15-float state array, its record of the orbi_record bank, its orbi_prior slot), held against the host ints n_src,
+ * cap_bank, n_priors -- the map the window assembly takes.  Outputs, state s = d_window[s]:
+ *     d_init_jobs [n_window][3]        orbi_graph_init_device: (s, state row, record)
+ *     d_fixed [n_window]               15 for state 0 -- setFixed(i == 0) on its three vertices (:992-1007); it has no pose vertex --,
+ *                                      ORBI_FIX_POSE (1) for the rest: the poses are constants of EdgeInertialOnly
+ *     d_inertial_edges [n_window - 1]  orbi_edge (4 x int32) {s, s + 1, record of key frame s, ORBI_EDGE_WALKS (1)}: :1012-1029 takes the
+ *                                      OLDER key frame's pre-integrator, and its C for both walks
+ *     d_recover_jobs [n_window][3]     orbi_graph_recover_device: (s, state row, 0): velocity and biases, no pose
+ *     d_bias_ids [n_window]            the records, orbi_set_bias_device's d_ids
+ *     d_velo_jobs [n_window][2]        the call below: (state row, prior slot)
+ *     d_state_kf [n_window]            the slots
+ *   Refusal.  The chain is positional, so NOTHING IS SKIPPED: a window entry outside [0, n_kf), a bad key frame, a key frame an earlier
+ *   entry named (bit 8 of d_result[1], counted in [2]) or a window key frame one of whose three d_kf_imu indices is out of range (bit
+ *   32, counted in [3]) REFUSES the whole call, AND THE REFUSAL IS HONOURED ON THE DEVICE: every entry of every job list is -1,
+ *   d_inertial_edges and d_state_kf included, and d_fixed is all 15, so every call behind it drops every job by its own distrust, the
+ *   optimisation finds no free vertex and no edge, and the state rows, the bank's biases and the priors keep their bytes.
+ *   d_result (int32 x 8, written): [0] n_window, [1] the refusal, a bit mask (8, 32: the window assembly's bits), [2] window entries
+ *   unusable, [3] key frames with a d_kf_imu index out of range; the rest 0.
+ *   Shape: ONE launch of ONE workgroup of 64 threads, a thread per position; integer work only.  ORBX_E_ARG: a null pointer, a negative
+ *   count, n_window < 2; ORBX_E_UNSUPPORTED: n_window > ORBM_IC_MAX_WINDOW (20, the reference's maxOpt with beLarge and orbil.h's cap);
+ *   then ORBX_E_NO_DEVICE.  Enqueued on `stream` (NULL: orbx.h, "Streams").
+ *
+ * orbm_inertial_chain_velocity_priors_device.  KeyFrame::setVelocity (KeyFrame.cpp:65-69) also sets velo_priori, and :1044-1053 call it
+ * for every window key frame.  For each of the n jobs (row, slot) of d_velo_jobs, d_priors[slot].velo_priori = d_src[15 * row + 12 ..),
+ * the three floats orbi_graph_recover_device left; nothing else of the slot is touched.  A row outside [0, n_src) or a slot outside
+ * [0, n_priors) is dropped.  d_result (int32 x 8, written): [0] written, [1] dropped.  One launch of one wave.  ORBX_E_ARG: a null
+ * pointer, a negative count; ORBX_E_UNSUPPORTED: n > ORBM_IC_MAX_WINDOW; then ORBX_E_NO_DEVICE.  Enqueued on `stream`.
+ * As compiled for gfx950 -- VGPRs / scratch / static LDS: k_ic_problem 22 / 0 / 192 B, k_ic_velocity_priors 14 / 0 / 32 B. */
+#define ORBM_IC_MAX_WINDOW 20
+int orbm_inertial_chain_problem_device(orbm_t *h, int n_kf, const uint8_t *d_bad, const int32_t *d_window, int n_window,
+                                       const int32_t *d_kf_imu, int n_src, int cap_bank, int n_priors, int32_t *d_init_jobs,
+                                       uint8_t *d_fixed, int32_t *d_inertial_edges, int32_t *d_recover_jobs, int32_t *d_bias_ids,
+                                       int32_t *d_velo_jobs, int32_t *d_state_kf, int32_t *d_result, void *stream);
+int orbm_inertial_chain_velocity_priors_device(orbm_t *h, struct orbi_prior *d_priors, int n_priors, const float *d_src, int n_src,
+                                               const int32_t *d_velo_jobs, int n, int32_t *d_result, void *stream);
 
 /* ---- The map rescaled and rotated on the device ------------------------------------------------------------------------------------
  * Map::applyScaleRotation (modules/BasicObject/Map.cpp:96-124), what LocalMapping::initializeIMU does with the gravity direction and

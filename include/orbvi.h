@@ -115,6 +115,8 @@
  *   orbi_graph_init_device -> orbi_edge_information_device -> orbvi_pose_optimize_device -> orbi_graph_recover_device
  *   (-> orbba_pose_drop_outliers_device)
  * localFullBundleAdjustment's loop is closed by the host in orbwl.h (it waits once per trial); initializeIMU's loops are not in the product.
+ * localInertialBundleAdjustment's loop is orbil_chain_optimize_device (orbil.h): one launch of one workgroup on the inertial stages of
+ * csrc/orbvi_stages.h, with the solve of this header replaced by a walk along the band of its chain (up to 20 states).
  */
 #ifndef ORBVI_H
 #define ORBVI_H

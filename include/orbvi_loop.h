@@ -73,6 +73,9 @@
  * registers across every stage, which 128 do not hold beside the visual stage's 126 (csrc/orbvi_loop.hip).  The visual sums keep the
  * order of 1024 threads: a thread does the work of the threads t and t + 512 of those, one behind the other, each under its own wave.
  * Latency-bound like the staged calls; tools/vi_pose_loop_latency.py records what a whole optimisation takes.
+ * The mapper's localInertialBundleAdjustment (up to 20 key frames, every pose fixed, no visual edge) is closed in the same shape by
+ * orbil_chain_optimize_device (orbil.h, which includes orbvi.h as this header does): the inertial stages of csrc/orbvi_stages.h, the
+ * policy of csrc/orb_lm_policy.h, and a solve along the band of the chain in place of the dense one.
  */
 #ifndef ORBVI_LOOP_H
 #define ORBVI_LOOP_H

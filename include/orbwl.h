@@ -76,6 +76,8 @@
  * Kernel resources (gfx950, VGPRs / scratch bytes / static LDS bytes; tests/test_vw_loop_resources.py reads them from the ISA):
  *   k_vwl_begin 4 / 0 / 0 B, k_vwl_push 18 / 0 / 0 B, k_vwl_decide 28 / 0 / 4 B, k_vwl_end 10 / 0 / 0 B.
  * Latency-bound like the staged calls; tools/vw_window_loop_latency.py records what a whole optimisation takes.
+ * localInertialBundleAdjustment, which the mapper runs directly in front of this function when the tracker is RECENTLY_LOST, has no
+ * points and no grid-sized stage: orbil_chain_optimize_device (orbil.h) runs it whole in one launch of one workgroup, without a wait.
  */
 #ifndef ORBWL_H
 #define ORBWL_H

@@ -549,4 +549,183 @@ __device__ __forceinline__ bool vi_solve_wave(int N, const double *__restrict__ 
     return refused;
 }
 
+// ---- orbil_chain_solve_device: the damped step of a chain, by a walk along its band -----------------------------------------------------
+// H of a chain is block-tridiagonal, and so is its Cholesky factor.  THE BAND (CS_BAND * n doubles of device memory, the caller's):
+// row i of the 15n has CS_ROW = 30 doubles, the columns of the block before its own (0 .. 14; zeros for block 0) and of its own (15 .. 29).
+// The assembly leaves A there without the damping, the walk replaces it by L, block column by block column: the 30 rows of blocks s and
+// s + 1 are one wave's tile in LDS (a lane per row), which it loads from the band, factorises as vi_solve_wave does a matrix, and stores
+// back; the backward substitution reads the finished blocks from the band behind the wave's fence.  The terms the dense order adds
+// outside the band are products with an exact zero, so for finite values the bytes are vi_solve_wave's.
+constexpr int CS_MAX_STATES = 20, CS_N = 15 * CS_MAX_STATES, CS_ROW = 30, CS_BAND = 15 * CS_ROW;   // CS_BAND doubles of band per state
+constexpr int CS_LD = CS_ROW + 1;                                                                   // a tile row's stride: 31 spreads a column over the banks
+constexpr int CS_TILE = 2 * 15 * CS_LD;                                                             // two blocks of rows, by the parity of the block
+
+// H of n states into the band by a workgroup of T >= 225 threads, t the thread's index, the identity rows and columns of the fixed dof
+// included, the damping not.  An edge takes part under edge_valid() when its states are neighbours; any other is skipped and counted:
+// s_cnt (8 ints) is zeroed, then ORBI_R_RANGE counts them.  s_fix (CS_N ints): the fixed flag per dof.  Workgroup barriers inside, every
+// one in uniform control flow; returns behind one
+template <int T>
+__device__ __forceinline__ void chain_solve_assemble(int t, int n, const uint8_t *__restrict__ fixed, const orbi_edge *__restrict__ edges, int n_edges, int cap,
+                                                     const double *__restrict__ H_diag, const double *__restrict__ H_off, double *band, int *s_fix, int *s_cnt)
+{
+    static_assert(T >= 225, "a thread per entry of an off-diagonal block");
+    const int N = 15 * n;
+    if (t < 8) s_cnt[t] = 0;
+    for (int i = t; i < N; i += T) s_fix[i] = dof_fixed(fixed[i / 15], i % 15);
+    for (int x = t; x < CS_ROW * N; x += T) {
+        const int i = x / CS_ROW, q = x - CS_ROW * i;
+        band[x] = q < 15 ? 0.0 : H_diag[225 * (size_t)(i / 15) + 15 * (i % 15) + q - 15];
+    }
+    __syncthreads();
+    for (int e = 0; e < n_edges; ++e) {          // ascending: several edges on one pair add up in edge order
+        const int i = edges[e].i, j = edges[e].j;
+        if (!edge_valid(i, j, edges[e].rec, n, cap) || (i - j != 1 && j - i != 1)) {   // uniform
+            if (t == 0) ++s_cnt[ORBI_R_RANGE];
+            continue;
+        }
+        if (t < 225) {                             // the block below the diagonal: the transpose of (i, j) when j is the later state
+            const int r = t / 15, c = t - 15 * r;
+            double *p = j > i ? band + (size_t)CS_ROW * (15 * j + c) + r : band + (size_t)CS_ROW * (15 * i + r) + c;
+            *p = *p + H_off[225 * (size_t)e + t];
+        }
+        __syncthreads();
+    }
+    for (int x = t; x < CS_ROW * N; x += T) {      // a fixed dof is an identity row and column
+        const int i = x / CS_ROW, q = x - CS_ROW * i, j = 15 * (i / 15) + q - 15;
+        if (j >= 0 && (s_fix[i] || s_fix[j])) band[x] = i == j ? 1.0 : 0.0;
+    }
+    __syncthreads();
+}
+
+// ONE wave on the assembled band: the largest H_jj over the free dof before damping, 0 when none is larger, in every lane
+__device__ __forceinline__ double chain_solve_largest(int N, const double *band, const int *s_fix, int lane)
+{
+    double m = 0.0;
+    for (int i = lane; i < N; i += 64) {
+        const double hjj = band[(size_t)CS_ROW * i + 15 + i % 15];
+        if (!s_fix[i] && hjj > m) m = hjj;
+    }
+    return wave_max(m);
+}
+
+// the damped Cholesky along the band and the substitutions by ONE wave, wave-level fences only: dx (15n doubles), out[0] (computeScale
+// without its + 1e-3) and out[2] (the smallest pivot, or the one that refused), in vi_solve_wave's orders: columns ascending, each inner
+// sum ascending over the columns of the band, one sqrt and one reciprocal per column, the forward substitution ascending, the backward one
+// descending, computeScale ascending over all 15n rows.  s_T (CS_TILE doubles), s_y, s_r and s_v (CS_N doubles each) are LDS.  True when
+// the solve was refused (the same in every lane): dx is then all zero and out[0] is 0
+__device__ __forceinline__ bool chain_solve_wave(int n, const double *__restrict__ b, double lam, double *__restrict__ dx, double *__restrict__ out, double *band,
+                                                 double *s_T, double *s_y, double *s_r, double *s_v, const int *s_fix, int lane)
+{
+    const int N = 15 * n;
+    const bool mine = lane < 15;                              // a row of block s; lanes 15 .. 29 have the rows of block s + 1
+    bool refused = false;
+    double pivot = INFINITY;
+    for (int s = 0; s < n && !refused; ++s) {                 // block column s: uniform
+        const bool theirs = lane >= 15 && lane < 30 && s + 1 < n;
+        wave_order();
+        for (int blk = s == 0 ? 0 : s + 1; blk <= s + 1 && blk < n; ++blk) {   // the rows that enter the tile, damped
+            double *T = s_T + (blk & 1) * 15 * CS_LD;
+            for (int x = lane; x < CS_BAND; x += 64) {
+                const int r = x / CS_ROW, q = x - CS_ROW * r, i = 15 * blk + r;
+                const double v = band[(size_t)CS_ROW * i + q];
+                T[r * CS_LD + q] = (q == 15 + r && !s_fix[i]) ? v + lam : v;
+            }
+        }
+        wave_order();
+        // a lane keeps its row in registers: w[k] is column k of the tile for a row of block s; a row of block s + 1 has its 15 columns of
+        // block s in w[15 ..) behind 15 zeros, so that one sum serves both -- the zeros add nothing to a sum that starts at +0.  LDS holds the
+        // rows of block s, which every lane reads as the column's row of L, a broadcast
+        double *own = s_T + (s & 1) * 15 * CS_LD, *nxt = s_T + ((s + 1) & 1) * 15 * CS_LD;
+        double w[CS_ROW];
+#pragma unroll
+        for (int k = 0; k < CS_ROW; ++k) w[k] = mine ? own[lane * CS_LD + k] : (theirs && k >= 15) ? nxt[(lane - 15) * CS_LD + k - 15] : 0.0;
+        double my_r = 0.0;
+#pragma unroll
+        for (int c = 0; c < 15; ++c) {                        // column 15s + c; its row of L is own + c * CS_LD.  Unrolled whole: w stays in registers
+            if (refused) continue;                            // the same in every lane: nothing behind the pivot that refused
+            const double *rc = own + c * CS_LD;
+            double a = 0.0;
+#pragma unroll
+            for (int k = 0; k < 15 + c; ++k) a = a + w[k] * rc[k];
+            const double v = w[15 + c] - a;
+            const double d = __shfl(v, c);
+            if (!(d > 0.0) || !isfinite(d)) {                 // the same in every lane
+                refused = true, pivot = d;
+                continue;
+            }
+            pivot = d < pivot ? d : pivot;
+            const double l = sqrt(d), r = 1.0 / l;
+            wave_order();
+            if (lane == c) w[15 + c] = l, my_r = r;
+            else if ((mine && lane > c) || theirs) w[15 + c] = v * r;
+            if (mine && lane >= c) own[lane * CS_LD + 15 + c] = w[15 + c];
+            wave_order();
+        }
+        if (refused) break;
+        // forward: y_i = (b_i - sum_{k<i} l_ik*y_k)*r_i, k ascending: the block before, then this one
+        const int i = 15 * s + (mine ? lane : 0);
+        const double bi = mine && !s_fix[i] ? b[i] : 0.0;
+        double a = 0.0, y = 0.0;
+        if (mine && s > 0) {
+#pragma unroll
+            for (int k = 0; k < 15; ++k) a = a + w[k] * s_y[15 * (s - 1) + k];
+        }
+#pragma unroll
+        for (int k = 0; k < 15; ++k) {
+            const double yk = __shfl((bi - a) * my_r, k);
+            if (lane == k) y = yk;
+            if (mine && lane > k) a = a + w[15 + k] * yk;
+        }
+        if (mine) s_y[i] = y, s_r[i] = my_r;
+        if (theirs) {                                         // L[s+1,s], the first 15 columns of the next step's rows
+#pragma unroll
+            for (int k = 0; k < 15; ++k) nxt[(lane - 15) * CS_LD + k] = w[15 + k];
+        }
+        wave_order();
+        for (int x = lane; x < CS_BAND; x += 64) {            // the finished rows of block s back to the band
+            const int r = x / CS_ROW, q = x - CS_ROW * r;
+            band[(size_t)CS_ROW * (15 * s + r) + q] = own[r * CS_LD + q];
+        }
+    }
+    if (!refused) {
+        __threadfence();                                      // a lane reads what the other lanes wrote to the band
+        wave_order();
+        for (int s = n - 1; s >= 0; --s) {                    // backward: x_i = (y_i - sum_{k>i} l_ki*x_k)*r_i, k descending
+            const int i = 15 * s + (mine ? lane : 0);
+            const double y = mine ? s_y[i] : 0.0, my_r = mine ? s_r[i] : 0.0;
+            double a = 0.0, x = 0.0;
+            double below[15], within[15];                     // column `lane` of L[s+1,s] and of L[s,s]: the loads ahead of the chain of sums
+#pragma unroll
+            for (int k = 0; k < 15; ++k) {
+                below[k] = mine && s + 1 < n ? band[(size_t)CS_ROW * (15 * (s + 1) + k) + lane] : 0.0;
+                within[k] = mine ? band[(size_t)CS_ROW * (15 * s + k) + 15 + lane] : 0.0;
+            }
+            if (mine && s + 1 < n) {
+#pragma unroll
+                for (int k = 14; k >= 0; --k) a = a + below[k] * s_y[15 * (s + 1) + k];
+            }
+#pragma unroll
+            for (int k = 14; k >= 0; --k) {
+                const double xk = __shfl((y - a) * my_r, k);
+                if (lane == k) x = xk;
+                if (mine && lane < k) a = a + within[k] * xk;
+            }
+            wave_order();
+            if (mine) s_y[i] = x;                             // x takes the place of y
+            wave_order();
+        }
+    }
+    for (int i = lane; i < N; i += 64) {
+        const double x = refused ? 0.0 : s_y[i], bi = s_fix[i] ? 0.0 : b[i];
+        dx[i] = x, s_v[i] = x * (lam * x + bi);
+    }
+    wave_order();
+    if (lane == 0) {
+        double a = 0.0;
+        for (int k = 0; k < N; ++k) a = a + s_v[k];
+        out[0] = refused ? 0.0 : a, out[2] = pivot;
+    }
+    return refused;
+}
+
 } // namespace

@@ -151,6 +151,8 @@ def _mlib():
             "orbm_inertial_window_problem_device": (i32, [vp, C.POINTER(KfTable), vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, i32,
                                                           i32, i32, i32] + [vp] * 20),
             "orbm_inertial_window_velocity_prior_device": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp]),
+            "orbm_inertial_chain_problem_device": (i32, [vp, i32, vp, vp, i32, vp, i32, i32, i32] + [vp] * 9),
+            "orbm_inertial_chain_velocity_priors_device": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp]),
             "orbm_apply_scale_rotation_device": (i32, [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp]),
             "orbm_update_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, vp, i32, i32, i32, vp, vp, vp]),
             "orbm_erase_connections_device": (i32, [vp, C.POINTER(CovisGraph), i32, vp, i32, vp, vp, vp, vp]),
@@ -714,6 +716,26 @@ class ORBMatcher:
         _lib.check(self._L.orbm_inertial_window_velocity_prior_device(
             self._hd._h, p("priors"), n_priors, p("src"), n_src, p("recover_jobs"), p("prior_jobs"), p("result"), _lib.stream_arg(stream)))
 
+    # -- Optimize::localInertialBundleAdjustment on the device-resident map: the chain assembled (Optimize.cpp:965-1029, :1044-1053) --
+    def InertialChainProblemDevice(self, d, n_kf, n_window, n_src, cap_bank, n_priors, stream=None):
+        """orbm_inertial_chain_problem_device: d = dict of torch device tensors -- in: bad u8 [n_kf], window i32 [n_window]
+        (getRecentKeyFrames, oldest first), kf_imu i32 [n_kf,3] (state row, record, prior slot); out: init_jobs i32 [n_window,3], fixed
+        u8 [n_window], inertial_edges i32 [n_window - 1,4], recover_jobs i32 [n_window,3], bias_ids i32 [n_window], velo_jobs i32
+        [n_window,2], state_kf i32 [n_window], result i32 [8] ([0] n_window, [1] refusal mask).  A refused call writes -1 into every
+        list and 15 into fixed.  Enqueues on `stream`; nothing is copied or synchronised, and the chain behind it needs no read-back."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_inertial_chain_problem_device(
+            self._hd._h, n_kf, p("bad"), p("window"), n_window, p("kf_imu"), n_src, cap_bank, n_priors, p("init_jobs"), p("fixed"),
+            p("inertial_edges"), p("recover_jobs"), p("bias_ids"), p("velo_jobs"), p("state_kf"), p("result"), _lib.stream_arg(stream)))
+
+    def InertialChainVelocityPriorsDevice(self, d, n_priors, n_src, n, stream=None):
+        """orbm_inertial_chain_velocity_priors_device: d = dict of torch device tensors -- in / out: priors (the orbi_prior array, 36
+        floats a slot); in: src f32 [n_src,15] (the state rows the recover wrote), velo_jobs i32 [n,2] (the assembly's); out: result i32
+        [8].  velo_priori of every window key frame takes its recovered velocity.  Enqueues on `stream`."""
+        p = lambda k: d[k].data_ptr()  # noqa: E731
+        _lib.check(self._L.orbm_inertial_chain_velocity_priors_device(
+            self._hd._h, p("priors"), n_priors, p("src"), n_src, p("velo_jobs"), n, p("result"), _lib.stream_arg(stream)))
+
     # -- Map::applyScaleRotation on the device-resident map (Map.cpp:96-124) --
     def ApplyScaleRotationDevice(self, calib, d, n_kf, n_src, n_priors, cap_points, be_first, min_scale=0.1, stream=None):
         """orbm_apply_scale_rotation_device: calib an imu.Calib.  d: dict of torch device tensors -- in / out: pose_R f64 [n_kf,9], pose_t
@@ -805,6 +827,16 @@ def inertial_window_problem_device(matcher, *args, **kwargs):
 def inertial_window_velocity_prior_device(matcher, *args, **kwargs):
     """ORBMatcher.InertialWindowVelocityPriorDevice (orbm_inertial_window_velocity_prior_device)"""
     return matcher.InertialWindowVelocityPriorDevice(*args, **kwargs)
+
+
+def inertial_chain_problem_device(matcher, *args, **kwargs):
+    """ORBMatcher.InertialChainProblemDevice (orbm_inertial_chain_problem_device)"""
+    return matcher.InertialChainProblemDevice(*args, **kwargs)
+
+
+def inertial_chain_velocity_priors_device(matcher, *args, **kwargs):
+    """ORBMatcher.InertialChainVelocityPriorsDevice (orbm_inertial_chain_velocity_priors_device)"""
+    return matcher.InertialChainVelocityPriorsDevice(*args, **kwargs)
 
 
 def apply_scale_rotation_device(matcher, *args, **kwargs):
