@@ -179,6 +179,8 @@ int orbm_window_lists_device(orbm_t *h, const void *d_kps, const uint8_t *d_desc
  *   d_kf_mp_ok [n1]   key-frame features that have a live map point (:141-146): the queries
  *   d_frame_mp [n2]   in / out as in the host entry point: -1 = free; a match writes the key-frame feature index
  *   d_has_mp1 / d_has_mp2: features that already have a map point (skipped, :452 / :466); d_matches12 [n1] receives the matches
+ *     (the flags are the caller's: orbm_triangulate_matches_device sets them for the rows it appends, no other call of the mapper step
+ *     touches them, so ahead of a step's first search they are derived from the key frame's slot row: slot >= 0)
  * A feature of side 2 lies in one vocabulary node, so the reference's order-dependent loop only couples queries of the same
  * node: every node is resolved by its own workgroup with the fixed point of the projection searches below, on the 8 closest
  * initially-free candidates per query (a query whose list is used up rescans its node on the device).  Rotation histogram
@@ -525,6 +527,11 @@ int orbm_scene_median_depth_device(orbm_t *h, int n_kf, const double *d_pose_R, 
  * MapPoint.cpp:184); here both entries are emitted and the row is counted in d_result[5].
  * Overflow: n_obs > cap_obs is found after the count and before anything is scattered; d_obs_kf / d_obs_kp are then untouched and
  * d_obs_off is ALL ZEROS -- every list is empty, so a refresh enqueued behind it changes nothing -- and d_result[1] = 1.
+ * What the calls of a mapper step's opening do behind such a build (tests/mapper_session.py runs a session through one): the refresh
+ * counts every selected valid row under "no observation" and leaves d_covis all zero, so orbm_update_connections_device has nothing to
+ * do; and orbm_cull_map_points_device sees getNumObs() == 0 for every row, so every listed row of age >= 2 goes bad, its slots left
+ * naming it (the next build skips them as invalid).  That destroys a map: a chain that does not read d_result[1] back sizes cap_obs to
+ * n_kf * stride, which cannot overflow.
  * d_result (int32 x 8, written, not accumulated): [0] n_obs (the full count, also on overflow), [1] overflow, [2] slots skipped: row
  * invalid, [3] slots skipped: key frame bad, [4] the longest list, [5] rows in which a key frame occurs more than once (0 on
  * overflow: it is found by the sort), [6] rows with more than 1024 observations (the refresh leaves those untouched), [7] 0.
@@ -548,7 +555,9 @@ int orbm_build_observations_device(orbm_t *h, int n_kf, const int32_t *d_n, cons
  * it is never rewritten and read with the refresh's distrust: offsets that do not describe a list inside [0, n_obs] give an empty
  * list; an entry whose key frame is outside [0, n_kf) or whose feature is outside [0, min(d_n[k], stride)) is dropped, never
  * dereferenced (d_result[6] counts such entries once each, over all of [0, n_obs)).  Liveness is evaluated against d_slots and d_bad
- * as they are NOW, so a stale CSR entry is harmless.
+ * as they are NOW, so a stale CSR entry is harmless.  Behind a build that overflowed every list is empty: numMP is still counted from
+ * the slots, numRedundant is 0 for every candidate, so every candidate is kept (d_code 0, or 1 / 2) and nothing is written but the
+ * outputs; orbm_erase_connections_device then finds no code 3 and leaves the graph.
  *
  * Candidates idx = 1 .. n_recent - 2 strictly in order, last = 0 (n_recent < 3: no candidate -- not the reference's size_t
  * underflow).  For c = recent[idx]:
@@ -705,6 +714,9 @@ int orbm_fuse_apply_device(orbm_t *h, const int32_t *d_best_idx, const int32_t *
  * 16 no edge; [6] entries of d_local dropped, [7] skipped for a bad key frame; [8] rows dropped for having no edge, [9] second edges
  * of a key frame in one row, [10] CSR entries dropped for an index out of range; the rest 0.  On a refusal the counts are still the
  * FULL counts, no array is written at or past its capacity, and what lies below is unspecified: do not run the LM on it.
+ * Behind a build that overflowed (every list empty; tests/mapper_session.py's session csr_overflow_late) the call keeps its local key
+ * frames ([0] = [3], no fixed one), drops every valid row they name for having no edge ([8] counts each once, [1] = [2] = 0) and refuses
+ * with 16: the caller, who reads [5] back, runs neither the LM nor orbm_local_ba_apply_device, and the step goes on to the culling.
  * Shape: ONE launch of ONE workgroup of 1024 threads with barriers between the phases, as the culling -- 20 key frames x 2000 slots x
  * short lists are latency: first occurrences by atomicMin (the least key wins whatever the order), then the slots in order, a tile of
  * 1024 at a time, with a block scan of (has an edge, edges) numbering points and edges.  A row's list is walked twice (count, write)
