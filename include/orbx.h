@@ -186,7 +186,13 @@ int orbx_tap_sincos(orbx_t *h, const float *angles_deg, int n, float *cos_sin);
                                  * descriptors in one pass over the raw level, no blurred level in memory) */
 #define ORBX_VAR_FAST_CELL_GROUP 10 /* calls with a few frames: FAST cells (one wave each) per workgroup -- the group reserves its
                                      * place in the candidate list with one atomic: 1, 4, 8 (default) or 16 */
-#define ORBX_N_VARIANTS 11
+#define ORBX_VAR_PYRAMID_SPLIT 11 /* batches with the strip form of FAST: 0 one pyramid chain ahead of one FAST launch,
+                                   * G = 2 .. 6: levels G.. are resized on the side stream, by the kernel that needs no LDS, beside
+                                   * FAST of levels 0 .. G-1; FAST of levels G.. follows as a second launch.  G >= n_levels is 0.
+                                   * -1 by call size (default): G = 3 where ORBX_VAR_RESIZE_LDS picks k_resize_lds, 0 elsewhere.
+                                   * + ORBX_PYRAMID_SPLIT_LDS: the side chain keeps the call's own resize kernel (measurement only) */
+#define ORBX_PYRAMID_SPLIT_LDS 8
+#define ORBX_N_VARIANTS 12
 int orbx_set_variant(orbx_t *h, int which, int value);
 int orbx_get_variant(const orbx_t *h, int which, int *value);
 
@@ -204,11 +210,14 @@ int orbx_get_variant(const orbx_t *h, int which, int *value);
  * runs beside the others.  Mode 2 times calls that run as ONE frame range (ORBX_VAR_STREAMS = 1, else ORBX_E_UNSUPPORTED from
  * the query below); a synchronous call with a few frames that takes the split order (ORBX_VAR_SPLIT_LEVEL0) brackets only its FAST,
  * blur, orientation and descriptor launches -- resize and quadtree read 0 there.  The orientation bracket includes k_desc_bins;
- * the descriptor bracket opens behind the wait for a side-stream blur. */
+ * the descriptor bracket opens behind the wait for a side-stream blur.  With ORBX_VAR_PYRAMID_SPLIT the resize stage has two launch
+ * groups, one per stream, and so has FAST. */
 int orbx_set_stage_timing(orbx_t *h, int enable);
 /* timing mode 2: per stage, the sum over the last extract call's launch groups of that stage (FAST: one or two, level 0 may
  * start early on the side stream) of the time between the events around each group.  Synchronises on those events. */
 int orbx_stage_times_in_step_ms(orbx_t *h, float *ms /* ORBX_N_STAGES */);
+/* timing mode 2: the number of launch groups of every stage in the last extract call (does not synchronise) */
+int orbx_stage_groups_in_step(orbx_t *h, int *n /* ORBX_N_STAGES */);
 /* timing mode 2, FAST only (kept for callers of the earlier interface): sum and number of its launch groups */
 int orbx_fast_times_in_step_ms(orbx_t *h, float *ms_sum, int *n_launches);
 /* timing mode 1: milliseconds each stage took in the last extract call (synchronises) */

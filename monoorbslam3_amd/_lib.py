@@ -80,6 +80,7 @@ _SIGS = {
     "orbx_fast_times_in_step_ms": (_i32, [_vp, C.POINTER(_f32), C.POINTER(_i32)]),
     "orbx_stage_times_ms": (_i32, [_vp, _vp]),
     "orbx_stage_times_in_step_ms": (_i32, [_vp, _vp]),
+    "orbx_stage_groups_in_step": (_i32, [_vp, _vp]),
     "orbx_last_error": (C.c_char_p, []),
     "orbx_version": (C.c_char_p, []),
 }

@@ -76,7 +76,8 @@ struct orbx_ctx {
     // timing mode 2: events around the (up to two) launch groups of every stage of a step, on the stream they are launched on
     hipEvent_t ev_in[ORBX_N_STAGES][4]; int ev_in_n[ORBX_N_STAGES];
     DevBuf d_fast_cells; int n_fast_cells;                      // uint16_t[4] per cell
-    DevBuf d_fast_strips; int n_fast_strips, n_fast_strips0;    // uint16_t[4] per strip; strips of all levels / of level 0
+    DevBuf d_fast_strips; int n_fast_strips;                    // uint16_t[4] per strip, level-major
+    int fast_strips_before[ORBX_MAX_LEVELS + 1];                // [l]: strips of levels [0, l)
     int fast_variant;                                           // ORBX_VAR_FAST: 0 = by call size (default), 1 = one wave per cell, 2 = strips
     int zero_copy;                                              // ORBX_VAR_ZERO_COPY
     int fast_cell_group;                                        // ORBX_VAR_FAST_CELL_GROUP: cells (one wave each) per workgroup of the few-frames FAST kernel: 1, 4, 8 (default) or 16
@@ -120,6 +121,8 @@ struct orbx_ctx {
     // chain; the remaining levels' cells follow on the main stream
     int early_fast;
     hipEvent_t ev_start[9], ev_fast0[9];
+    // ORBX_VAR_PYRAMID_SPLIT: resizes of the small levels on the side stream beside FAST of the large ones (see enqueue)
+    int pyramid_split;
     // stage timing
     int timing;
     hipEvent_t ev[ORBX_N_STAGES + 1];
@@ -214,6 +217,10 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 #endif
 #ifndef ORBX_FUSED_DESC_MIN_PIXELS
 #define ORBX_FUSED_DESC_MIN_PIXELS 55000000ull
+#endif
+// ORBX_VAR_PYRAMID_SPLIT = -1: first level of the side chain where the pyramid is k_resize_lds's (profiles/pyramid_split.md)
+#ifndef ORBX_PYRAMID_SPLIT_AUTO
+#define ORBX_PYRAMID_SPLIT_AUTO 3
 #endif
 
 struct Geometry {
@@ -402,7 +409,7 @@ static int ensure_geometry(orbx_ctx *c, int w0, int h0, int batch, int out_cap)
             orbx_build_fast_strips(c->levels, 0, c->levels.n_levels, st.data());
             ORB_TRY(upload(c->d_fast_strips, st));
             c->n_fast_strips = ns;
-            c->n_fast_strips0 = orbx_build_fast_strips(c->levels, 0, 1, nullptr);
+            for (int l = 0; l <= ORBX_MAX_LEVELS; ++l) c->fast_strips_before[l] = orbx_build_fast_strips(c->levels, 0, l, nullptr);
         }
         {
             const int nt = orbx_build_blur_tiles(c->levels, nullptr);
@@ -505,6 +512,7 @@ static int create_common(const orbx_cfg *cfg, const int *quotas_override, orbx_t
     c->side_blur = 1;      // the blur on a side stream next to FAST
     c->early_fast = -1;    // level 0's FAST beside the pyramid unless the pyramid is k_resize_lds's (see enqueue)
     c->split_level0 = 1;
+    c->pyramid_split = -1; // the small levels' resizes beside FAST of the large ones where the pyramid is k_resize_lds's (see enqueue)
     c->fast_variant = 0;   // strips for batches, one wave per cell for a few frames
     c->blur_mfma = 1;      // matrix pipe for batches and levels that are large enough
     c->resize2 = 1;        // two levels per launch for calls with a few frames
@@ -654,20 +662,22 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     // against 0.231, at 512: 0.35 against 0.46; 1920x1080 x 128: 0.37 against 0.52): from about 10^8 level-0 pixels per call
     const bool lds_resize = c->resize_lds == 2 || (c->resize_lds == 1 && (size_t)n_frames * (size_t)LV.lv[0].w * (size_t)LV.lv[0].h >= (size_t)100000000);
     // level l from level l - 1 -- and level l + 1 with it when the two fit one launch (k_resize2): returns the last level made
-    auto launch_resize = [&](hipStream_t st, int l, int *zero_counts) -> int {
+    // (no_lds: this level alone and by k_resize, whatever the call would take -- the side chain of ORBX_VAR_PYRAMID_SPLIT)
+    const bool two_levels = c->resize2 == 2 || (c->resize2 == 1 && n_frames < 24);
+    auto launch_resize = [&](hipStream_t st, int l, int *zero_counts, bool no_lds) -> int {
         const uint8_t *sp; size_t sfs; int spitch;
         raw(l - 1, &sp, &sfs, &spitch);
         // (small calls only: per 512 frames the pyramid takes 0.71 ms this way against 0.47 -- a workgroup's two phases run one
         // after the other -- while a single 1242x375 frame is back 20 us sooner, 157 -> 138 us; ORBX_VAR_RESIZE2 = 2 forces it)
         // (a source under 8 pixels wide is narrower than the 8-byte window of k_resize2's first phase: orbx_launch_resize has a kernel for it)
-        if ((c->resize2 == 2 || (c->resize2 == 1 && n_frames < 24)) && l + 1 < L && c->resize2_ok[l] && LV.lv[l - 1].w >= 8) {
+        if (!no_lds && two_levels && l + 1 < L && c->resize2_ok[l] && LV.lv[l - 1].w >= 8) {
             orbx_launch_resize2(st, sp, sfs, spitch, LV.lv[l - 1].w, LV.lv[l - 1].h, b.img_arena + LV.lv[l].raw_off, b.img_frame_stride,
                                 LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, xtap(l), ytap(l), b.img_arena + LV.lv[l + 1].raw_off,
                                 b.img_frame_stride, LV.lv[l + 1].pitch, LV.lv[l + 1].w, LV.lv[l + 1].h, xtap(l + 1),
                                 ytap(l + 1), n_frames, zero_counts);
             return l + 1;
         }
-        if (lds_resize && c->resize_lds_ok[l]) {
+        if (!no_lds && lds_resize && c->resize_lds_ok[l]) {
             orbx_launch_resize_lds(st, sp, sfs, spitch, LV.lv[l - 1].w, LV.lv[l - 1].h, l == 1 ? LV.lv[0].w : spitch,
                                    b.img_arena + LV.lv[l].raw_off, b.img_frame_stride, LV.lv[l].pitch, LV.lv[l].w, LV.lv[l].h, xtap(l),
                                    ytap(l), n_frames, zero_counts);
@@ -685,7 +695,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     const bool strips = c->fast_variant == 2 || (c->fast_variant == 0 && n_frames >= 24);
     const uint16_t *d_units = (strips ? c->d_fast_strips : c->d_fast_cells).as<uint16_t>();
     const int n_units = strips ? c->n_fast_strips : c->n_fast_cells;
-    const int n_cells0 = strips ? c->n_fast_strips0 : LV.lv[0].n_cols * LV.lv[0].n_rows;
+    const int n_cells0 = strips ? c->fast_strips_before[1] : LV.lv[0].n_cols * LV.lv[0].n_rows;
     auto launch_fast = [&](hipStream_t st, const uint16_t *units, int n) {
         // timing mode 2: the step keeps its streams, and HIP events on the launch's own stream bracket each launch group, so
         // that the kernels are timed as they run beside the others (orbx_stage_times_in_step_ms)
@@ -773,7 +783,7 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         bool started = false;
         for (int l = 1; l < L;) {
             // the first launch also clears the candidate counters
-            const int done = launch_resize(s, l, l == 1 ? b.cand_count : nullptr); // last level this launch produced
+            const int done = launch_resize(s, l, l == 1 ? b.cand_count : nullptr, false); // last level this launch produced
             if (!started && done >= std::max(G - 1, 1)) { // counters are zero, levels < G exist
                 ORB_TRY(hipEventRecord(c->ev_start[slot], s));
                 started = true;
@@ -801,12 +811,30 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
         if (early_fast > 1) // level 0 needs no pyramid for its blur either
             launch_blur(c->side[slot], 0, 1);
     }
-    // (Measured and dropped, round 5: the pyramid's last levels -- a chain of small launches, 0.11 ms for a fifth of level 1's
-    // pixels -- and their FAST on the side stream beside FAST of the large levels: resize 0.34 -> 0.18-0.30 ms in step, FAST
-    // 0.70 -> 0.76-0.77, step 2.21 against 2.18 ms for every split level 3..6; profiles/NEGATIVES.md.)
+    // ORBX_VAR_PYRAMID_SPLIT = G: the pyramid's last levels are a chain of small dependent launches (levels 4..7 of 1242x375 x 512:
+    // 105 us for 28 % of the resized pixels), and FAST, bound by its LDS, leaves registers and wave slots of every CU unused.  Levels
+    // G.. are resized on the side stream by k_resize (no LDS, 27 VGPRs) beside FAST of levels 0 .. G-1; FAST of levels G.. is a
+    // second launch behind both.  Level 1 stays on the main stream (G >= 2): its launch clears the candidate counters.
+    // Measured (512 frames 1242x375, profiles/pyramid_split.md): step 2.064 -> 2.016 ms at G = 3, 2.030 at 4, 2.048 at 5, 2.047 at 2;
+    // the first FAST launch starts at 178 us instead of 325, FAST takes 502 + 271 us instead of 711, and k_resize beside it is starved
+    // (levels 3..7: 506 us against 151 alone), so the side chain ends just behind the first launch.  With k_resize_lds on the side
+    // stream (+ ORBX_PYRAMID_SPLIT_LDS) nothing is gained: 2.072.  Round 5 had the small levels' FAST on the side stream too and lost.
+    const int G = c->pyramid_split < 0 ? (lds_resize ? ORBX_PYRAMID_SPLIT_AUTO : 0) : (c->pyramid_split & ~ORBX_PYRAMID_SPLIT_LDS);
+    const bool psplit = !t && slot == 8 && strips && !early && !split && !two_levels && L > 2 && G >= 2 && G < L;
     {
         InStep rt(c, ORBX_STAGE_RESIZE, s);
-        for (int l = 1; l < L;) l = launch_resize(s, l, l == 1 && zero_in_resize ? b.cand_count : nullptr) + 1;
+        for (int l = 1; l < (psplit ? G : L);) l = launch_resize(s, l, l == 1 && zero_in_resize ? b.cand_count : nullptr, false) + 1;
+    }
+    if (psplit) {
+        ORB_TRY(hipEventRecord(c->ev_start[slot], s)); // levels < G exist, candidate counters are zero
+        launch_fast(s, d_units, c->fast_strips_before[G]);
+        ORB_TRY(hipStreamWaitEvent(c->side[slot], c->ev_start[slot], 0));
+        {
+            InStep rt(c, ORBX_STAGE_RESIZE, c->side[slot]);
+            for (int l = G; l < L; ++l) launch_resize(c->side[slot], l, nullptr, c->pyramid_split < 0 || !(c->pyramid_split & ORBX_PYRAMID_SPLIT_LDS));
+        }
+        ORB_TRY(hipEventRecord(c->ev_pyr[slot], c->side[slot]));
+        ORB_TRY(hipStreamWaitEvent(s, c->ev_pyr[slot], 0)); // the whole pyramid from here on
     }
     if (t) ORB_TRY(hipEventRecord(c->ev[1], s));
     // (nothing to fork when k_blur_desc describes every level: no blur pass, and no event pair in the stream between the pyramid and FAST)
@@ -822,6 +850,8 @@ static int enqueue(orbx_ctx *c, hipStream_t s, const uint8_t *d_l0, size_t l0_fs
     if (early) {
         launch_fast(s, d_units + 4 * n_cells0, n_units - n_cells0);
         ORB_TRY(hipStreamWaitEvent(s, c->ev_fast0[slot], 0));
+    } else if (psplit) {
+        launch_fast(s, d_units + 4 * c->fast_strips_before[G], n_units - c->fast_strips_before[G]);
     } else {
         launch_fast(s, d_units, n_units);
     }
@@ -1137,6 +1167,15 @@ extern "C" int orbx_stage_times_in_step_ms(orbx_t *c, float *ms)
     return ORBX_OK;
 }
 
+extern "C" int orbx_stage_groups_in_step(orbx_t *c, int *n)
+{
+    if (!c || !n) return orbx_set_error(ORBX_E_ARG, "null argument");
+    if (c->timing != 2 || c->ev_in_n[ORBX_STAGE_FAST] < 1) return orbx_set_error(ORBX_E_ARG, "no extract call in timing mode 2 yet");
+    if (c->n_sub > 1) return orbx_set_error(ORBX_E_UNSUPPORTED, "in-step stage times need ORBX_VAR_STREAMS = 1");
+    for (int st = 0; st < ORBX_N_STAGES; ++st) n[st] = c->ev_in_n[st];
+    return ORBX_OK;
+}
+
 extern "C" int orbx_fast_times_in_step_ms(orbx_t *c, float *ms_sum, int *n_launches)
 {
     if (!c || !ms_sum) return orbx_set_error(ORBX_E_ARG, "null argument");
@@ -1172,6 +1211,7 @@ static int *variant_field(orbx_ctx *c, int which, int *lo, int *hi)
     case ORBX_VAR_ZERO_COPY: *lo = 0; *hi = 1; return &c->zero_copy;
     case ORBX_VAR_DESC: *lo = 0; *hi = 2; return &c->desc_variant;
     case ORBX_VAR_FAST_CELL_GROUP: *lo = 1; *hi = 16; return &c->fast_cell_group;
+    case ORBX_VAR_PYRAMID_SPLIT: *lo = -1; *hi = ORBX_PYRAMID_SPLIT_LDS + 6; return &c->pyramid_split;
     default: return nullptr;
     }
 }
@@ -1189,6 +1229,9 @@ extern "C" int orbx_set_variant(orbx_t *c, int which, int value)
     // the first level of the main chain lies inside the pyramid: 0 (one chain) .. n_levels - 1
     if (which == ORBX_VAR_SPLIT_LEVEL0 && value > c->cfg.n_levels - 1)
         return orbx_set_error(ORBX_E_ARG, "split level must be below the handle's n_levels");
+    // first level of the side chain: 2 .. 6 (level 1 clears the candidate counters on the main stream), with or without the control bit
+    if (which == ORBX_VAR_PYRAMID_SPLIT && value > 0 && ((value & ~ORBX_PYRAMID_SPLIT_LDS) < 2 || (value & ~ORBX_PYRAMID_SPLIT_LDS) > 6))
+        return orbx_set_error(ORBX_E_ARG, "pyramid split level must be -1, 0 or 2 .. 6");
     *f = value;
     return ORBX_OK;
 }

@@ -29,6 +29,7 @@ VARIANTS = {
     "zero_copy": (8, {}),
     "desc": (9, {"auto": 0, "separate": 1, "fused": 2}),
     "fast_cell_group": (10, {}),
+    "pyramid_split": (11, {"auto": -1, "off": 0}),
 }
 
 
@@ -237,6 +238,12 @@ class ORBExtractor:
         ms = np.zeros(len(STAGES), np.float32)
         _lib.check(self._L.orbx_stage_times_in_step_ms(self._h, _vp(ms)))
         return dict(zip(STAGES, ms.tolist()))
+
+    def stage_groups_in_step(self):
+        """Timing mode 2: how many launch groups every stage of the last call had (two where a stage ran on two streams)."""
+        n = np.zeros(len(STAGES), np.int32)
+        _lib.check(self._L.orbx_stage_groups_in_step(self._h, _vp(n)))
+        return dict(zip(STAGES, n.tolist()))
 
     def stage_times_ms(self):
         ms = np.zeros(len(STAGES), np.float32)
