@@ -1266,6 +1266,95 @@ int orbm_apply_scale_rotation_device(orbm_t *h, const struct orbi_calib *calib, 
                                      int n_priors, float *d_points, const uint8_t *d_valid, const int32_t *d_n_points, int cap_points,
                                      const float *d_summary, int be_first, float min_scale, int32_t *d_result, void *stream);
 
+/* ---- Two-view initialisation: the H / F RANSAC ---------------------------------------------------------------------------------------
+ * The front half of TwoViewReconstruction::Reconstruct (modules/Frontend/TwoViewReconstruction.cpp:14-84, reached from
+ * Tracking.cpp:620 through Pinhole.cpp:90 / Fisheye.cpp:138), the consumer of the d_matches12 that
+ * orbm_search_for_initialization_device leaves on the device: the match list (:26-30), the draw of the eight-point sets (:42-58),
+ * FindHomography and FindFundamental (:86-161) with ComputeH21 / ComputeF21 (:163-224), CheckHomography / CheckFundamental (:226-344)
+ * and Normalize (:558-596), and the RH decision (:73-79).  ReconstructH / ReconstructF / CheckRT / DecomposeE stay with the caller.
+ *
+ * Inputs.  d_kps1 [n1], d_kps2 [n2]: orbx_kp records, UNDISTORTED by the caller (Fisheye's cv::fisheye::undistortPoints is not part
+ * of this); only x and y are read.  d_matches12 [n1]: m in [0, n2) is a match, anything else none.  sigma: the reference's 1.f
+ * (Pinhole.cpp:86); invSigma2 = 1.f / (sigma * sigma).  iters: max_iterations (200 there), 1 .. ORBM_TWO_VIEW_MAX_ITERS.
+ * d_sets: NULL -- the sets are drawn on the device from rng_state as orbm_two_view_sets draws them (0: cv::RNG's default state,
+ * ORBM_TWO_VIEW_RNG_DEFAULT) -- or [iters][8] int32 indices into the match list, for a caller who wants the draw of their own
+ * OpenCV; an index outside the list is kept inside it.
+ *
+ * Arithmetic (float unless said otherwise, no fused multiply-add; `/` and sqrt correctly rounded; a product-sum of three reads
+ * (p0 + p1) + p2):
+ *   Normalize over ALL key points of a frame, matched or not: meanX = sum(x) / N, meanDevX = sum(fabsf(x - meanX)) / N, sX = 1.f / meanDevX,
+ *     T = [sX, 0, -meanX * sX; 0, sY, -meanY * sY; 0, 0, 1]; a point is ((x - meanX) * sX, (y - meanY) * sY).  The four sums are TREES
+ *     (a thread's stride of 1024, the wave's butterfly, the sixteen waves in order), so T1 and T2 differ from the reference's running
+ *     float sums in the last bits.
+ *   The matrix of :172-190 (16 x 9) / :207-215 (8 x 9) from the normalised sample, its entries multiplied in float.  From here to the
+ *     de-normalised 3 x 3 the arithmetic is DOUBLE on those floats and on the float entries of T1 and T2, rounded to float once at the
+ *     end: a float Jacobi of 360 rotations would leave several times the error of the float SVD the reference runs.
+ *   Hn, Fn = the right singular vector of the matrix's smallest singular value, row-major 3 x 3 (a one-sided Jacobi, a fixed number of
+ *     sweeps: not bit-reproducible by another SVD; csrc/orbm_two_view.hip); Fn then loses its smallest singular value (:220-223), by
+ *     the same method on the 3 x 3.
+ *   H21 = (T2^-1 * Hn) * T1 with T2^-1 = [1 / sX2, 0, meanX2; 0, 1 / sY2, meanY2; 0, 0, 1];  F21 = (T2^T * Fn) * T1; the zeros of
+ *     T are not multiplied: M = T2^-1 * Hn has M(0, c) = (1 / sX2) * Hn(0, c) + meanX2 * Hn(2, c), T2^T * Fn has M(2, c) =
+ *     (T2(0, 2) * Fn(0, c) + T2(1, 2) * Fn(1, c)) + Fn(2, c), and X = M * T1 has X(r, 0) = M(r, 0) * sX1, X(r, 1) = M(r, 1) * sY1,
+ *     X(r, 2) = (M(r, 0) * T1(0, 2) + M(r, 1) * T1(1, 2)) + M(r, 2).  From here on float again, on the rounded H21 and F21.
+ *   CheckHomography per match, H12 = the cofactors of the float H21 times 1 / det, det = (h11 * c11 - h12 * c12) + h13 * c13, in double
+ *     and rounded to float once (H21 mixes entries of 1e-3 and of 1e2: a float inverse is off by 1e-3 relative in places, LAPACK's less):
+ *     w = 1.f / ((h31inv * u2 + h32inv * v2) + h33inv), u2in1 = ((h11inv * u2 + h12inv * v2) + h13inv) * w, v2in1 alike,
+ *     chiSquare1 = ((u1 - u2in1) * (u1 - u2in1) + (v1 - v2in1) * (v1 - v2in1)) * invSigma2; the second side with H21 and (u1, v1);
+ *     th = 5.991f.  CheckFundamental: a2 = (f11 * u1 + f12 * v1) + f13, b2, c2 alike, num2 = (a2 * u2 + b2 * v2) + c2,
+ *     chiSquare1 = ((num2 * num2) / (a2 * a2 + b2 * b2)) * invSigma2; the second side with the columns of F21 and (u2, v2);
+ *     th = 3.841f, thScore = 5.991f.  Per side `if (chi > th) inlier = false; else score += thScore - chi` (a NaN adds itself, as there).
+ *   The score of a hypothesis: lane l of the wave adds the sides of the matches l, l + 64, ... in that order, then the 64 sums meet in a
+ *     butterfly (steps 32 .. 1): a fixed order, so the same input gives the same bytes, and not the reference's running sum.
+ *   The pick per family: the FIRST iteration whose score is the maximum (:116, :155 use a strict `>`); a score that is not above 0
+ *     picks nothing.  RH = SH / (SH + SF), one float add and one float divide; H is chosen when RH > 0.5f.
+ *
+ * Outputs, every one written by a call that succeeds with d_result[1] != 1, none otherwise:
+ *   d_pairs [n1][2] int32: match_pairs in ascending i, (i, m); the rows from n_matches on are (-1, -1).
+ *   d_H, d_F [9] float row-major: the winning H21 and F21.  d_inl_H, d_inl_F [n1] uint8 per MATCH index (row of d_pairs): the two
+ *   inlier masks, 0 from n_matches on.  d_score [2]: SH, SF.  d_rh [1]: RH (0 when SH + SF == 0).
+ *   d_hyp [2][iters][9] float (may be NULL): every hypothesis after de-normalisation, H then F.  d_hyp_score [2][iters] float (may be
+ *   NULL): every hypothesis's score.  Documented outputs: a caller may want to refine the runners-up.
+ * d_result (int32 x 8, written): [0] n_matches; [1] status: 0 ok, 1 fewer than 8 matches (the reference would index an empty vector;
+ *   ONLY d_result is written), 2 SH + SF == 0 (:73, the reference returns false); [2], [3] the winning iteration of H and of F, -1
+ *   when no hypothesis scored above 0 (the matrix is then zeros and the mask all 0; the reference leaves them unset); [4] 1 when
+ *   RH > 0.5f, i.e. H is chosen; [5], [6] the inlier counts of H and of F; [7] 0.
+ * The draw's parity with OpenCV is UNPINNED: OpenCV is not available where this library is built and tested, so orbm_two_view_sets
+ * restates cv::RNG from its published source (the multiply-with-carry state = (uint32) state * 4164903690 + (state >> 32), the draw
+ * (uint32) state % size) and is held to a model that restates the same text; pass d_sets to use the draw of your own OpenCV.
+ *
+ * Shape (latency, not throughput: 2 * iters waves on 256 CUs).  Three launches on `stream`, no host wait: k_tv_prepare, ONE workgroup of
+ * 1024 (the list by a block scan, walked twice so that fewer than 8 matches are found before a row is written; Normalize; the draw:
+ * the 8 * iters raw values do not depend on n_matches, and the generator is state' = state * 4164903690 modulo 4164903690 * 2^32 - 1,
+ * so one wave makes them, each lane 128 values from a state it jumps to by one modular product, and
+ * a lane per iteration resolves its eight "take index randi, move the last into its place" steps on an eight-entry override list);
+ * k_tv_hypotheses, ONE WAVE per hypothesis, four to a workgroup (the rows of the matrix on 16 lanes, the column dot products 16-wide
+ * __shfl_xor butterflies; then all 64 lanes stride over the matches, the inlier bits one __ballot word per 64 matches in handle
+ * scratch); k_tv_pick, ONE workgroup of 1024.  Handle scratch (grow-only, apart from the searches'): the sets, the hypotheses, their
+ * scores and 2 * iters mask rows of ceil(n1 / 64) words; one call in flight per handle.  As compiled for gfx950 -- VGPRs / scratch /
+ * static LDS: k_tv_prepare 81 / 0 / 33088 B, k_tv_hypotheses 222 / 0 / 0 B, k_tv_pick 40 / 0 / 264 B: no scratch memory; the two
+ * one-workgroup kernels within 128 VGPRs (all a thread of sixteen waves can have), k_tv_hypotheses within 256 (its 18 doubles a lane and
+ * three butterflies in flight; two waves per SIMD remain, which is what 2 * 1024 waves put on the 1024 SIMDs of the device).
+ * Measured device time of one call at iters = 200 (profiles/two_view_latency.txt): 196 us at 300 matches, 211 us at 2000; 8 us less with d_sets given.
+ * Refused with ORBX_E_ARG before any launch, every byte left as passed: iters outside 1 .. 1024, n1 or n2 < 1, sigma <= 0, a required
+ * pointer NULL.  Behind those, also before any launch: n1 or n2 above ORBM_TWO_VIEW_MAX_KEYPOINTS is ORBX_E_UNSUPPORTED.  Without a HIP
+ * device the call fails with ORBX_E_NO_DEVICE.  Enqueued on `stream` (NULL: orbx.h, "Streams"). */
+#define ORBM_TWO_VIEW_MAX_ITERS 1024
+#define ORBM_TWO_VIEW_MAX_KEYPOINTS 65536 /* n1, n2: the 2 * iters mask rows of n1 bits stay within 16 MB of handle scratch */
+#define ORBM_TWO_VIEW_RNG_DEFAULT 0xffffffffull
+int orbm_two_view_ransac_device(orbm_t *h, const void *d_kps1, int n1, const void *d_kps2, int n2, const int32_t *d_matches12, float sigma,
+                                int iters, uint64_t rng_state, const int32_t *d_sets, int32_t *d_pairs, float *d_H, float *d_F,
+                                uint8_t *d_inl_H, uint8_t *d_inl_F, float *d_score, float *d_rh, float *d_hyp, float *d_hyp_score,
+                                int32_t *d_result, void *stream);
+/* The same with host pointers throughout: synchronous on the handle's stream, one pinned copy each way, the same kernels and the
+ * same bytes as the device entry point. */
+int orbm_two_view_ransac(orbm_t *h, const void *kps1, int n1, const void *kps2, int n2, const int32_t *matches12, float sigma, int iters,
+                         uint64_t rng_state, const int32_t *sets, int32_t *pairs, float *H, float *F, uint8_t *inl_H, uint8_t *inl_F,
+                         float *score, float *rh, float *hyp, float *hyp_score, int32_t *result);
+/* The draw of :42-58 on the host, no device needed: sets [iters][8] int32, eight distinct indices below n_matches each, the
+ * generator running on from set to set (rng_state 0: ORBM_TWO_VIEW_RNG_DEFAULT).  ORBX_E_ARG: n_matches < 8, iters outside
+ * 1 .. 1024, sets NULL. */
+int orbm_two_view_sets(int n_matches, int iters, uint64_t rng_state, int32_t *sets);
+
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,
  * :115-120).  best_idx[g] = index inside the group of the descriptor with the least median Hamming distance to the

@@ -14,6 +14,10 @@ __attribute__((visibility("hidden"))) hipError_t orbm_device_call(orbm_t *c, hip
 // the handle's own stream, on which such a call uploads, computes, downloads and waits.
 __attribute__((visibility("hidden"))) hipError_t orbm_host_stage(orbm_t *c, size_t bytes, void **dev, void **pinned, hipStream_t *s);
 
+// The scratch of the two-view RANSAC (orbm_two_view.hip): `bytes` of device memory of the handle's own, grow-only, apart from the
+// blocks the searches use, so that a search and the RANSAC behind it on one stream share nothing.  One call in flight per handle.
+__attribute__((visibility("hidden"))) hipError_t orbm_two_view_scratch(orbm_t *c, size_t bytes, void **dev);
+
 // ---- what the map-side device entry points share (orbm_project / triangulate / refresh / observations) -------------------------
 constexpr int ORBM_MAX_POINTS = 1 << 19;   // map points per call: k_project's frustum form and k_cull keep one bit per point in 64 KB of LDS
 constexpr int ORBM_MAX_LIST = 1024;        // observations per list (MEDOID_MAX of k_medoid): the refresh leaves longer lists untouched

@@ -1403,6 +1403,7 @@ struct orbm_ctx {
     HandleStream hs;
     DevBuf a, b, out, q_idx, c_begin, c_len, out_begin, c_idx, row_ok, col_ok, bidx, bbest, bsecond;
     DevBuf w_in, w_out, w_grid; // window searches: staged inputs, lists, CSR grid + scratch
+    DevBuf two_view;            // orbm_two_view_ransac{,_device}: the sets, the hypotheses, their scores and mask rows (orbm_two_view.hip)
     PinBuf h_in, h_out;
     int window_on_device = 1;   // ORBM_VAR_WINDOW = 1 keeps the host grid (the parity twin of the device lists)
     int best2_variant = 0;      // ORBM_VAR_BEST2: 0 = fp4, 1 = i8, 2 = valu
@@ -1455,6 +1456,13 @@ hipError_t orbm_host_stage(orbm_t *c, size_t bytes, void **dev, void **pinned, h
     if (e == hipSuccess) e = need(c->w_in, bytes);
     if (e == hipSuccess) e = need(c->h_in, bytes);
     *dev = c->w_in.p, *pinned = c->h_in.p, *s = c->hs.stream;
+    return e;
+}
+
+hipError_t orbm_two_view_scratch(orbm_t *c, size_t bytes, void **dev) // orbm_internal.h
+{
+    const hipError_t e = need(c->two_view, bytes);
+    *dev = c->two_view.p;
     return e;
 }
 

@@ -169,6 +169,9 @@ def _mlib():
             "orbm_distinctive_descriptors": (i32, [vp, vp, vp, i32, vp]),
             "orbm_distinctive_descriptors_device": (i32, [vp, vp, vp, i32, vp, vp]),
             "orbm_three_maxima": (None, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+            "orbm_two_view_ransac_device": (i32, [vp, vp, i32, vp, i32, vp, f32, i32, C.c_uint64] + [vp] * 12),
+            "orbm_two_view_ransac": (i32, [vp, vp, i32, vp, i32, vp, f32, i32, C.c_uint64] + [vp] * 11),
+            "orbm_two_view_sets": (i32, [i32, i32, C.c_uint64, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -762,6 +765,39 @@ class ORBMatcher:
             p("cell_start"), p("cell_items"), grid_cols, grid_rows, n2, p("pre"), window, list_cap, p("matches12"), p("result"),
             _lib.stream_arg(stream)))
 
+    # -- the H / F RANSAC of TwoViewReconstruction::Reconstruct (TwoViewReconstruction.cpp:14-344) ----------------
+    def TwoViewRansacDevice(self, d, n1, n2, sigma=1.0, iters=200, rng_state=0, stream=None):
+        """orbm_two_view_ransac_device on torch device tensors: d = dict(kps1, kps2 (orbx_kp records, undistorted), matches12 i32 [n1] (as
+        SearchForInitializationDevice leaves it); sets i32 [iters, 8] (optional: the caller's draw); out: pairs i32 [n1, 2], H, F f32 [9],
+        inl_H, inl_F u8 [n1], score f32 [2], rh f32 [1], hyp f32 [2, iters, 9] and hyp_score f32 [2, iters] (both optional), result i32
+        [8]).  Enqueues on `stream`; nothing is copied or synchronised.  result[1] = 1 (fewer than 8 matches): only result was written."""
+        p = lambda k: d[k].data_ptr() if d.get(k) is not None else None  # noqa: E731
+        _lib.check(self._L.orbm_two_view_ransac_device(
+            self._hd._h, p("kps1"), n1, p("kps2"), n2, p("matches12"), sigma, iters, rng_state, p("sets"), p("pairs"), p("H"), p("F"),
+            p("inl_H"), p("inl_F"), p("score"), p("rh"), p("hyp"), p("hyp_score"), p("result"), _lib.stream_arg(stream)))
+
+    def TwoViewRansac(self, kps1, kps2, matches12, sigma=1.0, iters=200, rng_state=0, sets=None, out=None, all_hypotheses=True):
+        """orbm_two_view_ransac on numpy arrays.  Returns a dict of the outputs (names as for TwoViewRansacDevice; hyp and hyp_score with
+        all_hypotheses); `out`, a dict of C-contiguous arrays of those names and types, is written in place instead."""
+        k1 = np.ascontiguousarray(kps1, dtype=KP_DTYPE)
+        k2 = np.ascontiguousarray(kps2, dtype=KP_DTYPE)
+        m12 = np.ascontiguousarray(matches12, dtype=np.int32)
+        st = None if sets is None else np.ascontiguousarray(sets, dtype=np.int32)
+        n1, it = len(k1), max(int(iters), 0)
+        types = dict(pairs=(np.int32, (n1, 2)), H=(np.float32, (9,)), F=(np.float32, (9,)), inl_H=(np.uint8, (n1,)), inl_F=(np.uint8, (n1,)),
+                     score=(np.float32, (2,)), rh=(np.float32, (1,)), hyp=(np.float32, (2, it, 9)), hyp_score=(np.float32, (2, it)),
+                     result=(np.int32, (8,)))
+        if out is None:
+            out = {k: np.zeros(shape, dt) for k, (dt, shape) in types.items() if all_hypotheses or not k.startswith("hyp")}
+        for k, a in out.items():
+            assert a.dtype == types[k][0] and a.flags["C_CONTIGUOUS"], k
+        assert st is None or st.shape == (it, 8)
+        q = lambda k: _vp(out[k]) if out.get(k) is not None else None  # noqa: E731
+        _lib.check(self._L.orbm_two_view_ransac(
+            self._hd._h, _vp(k1), n1, _vp(k2), len(k2), _vp(m12), sigma, iters, rng_state, None if st is None else _vp(st), q("pairs"), q("H"),
+            q("F"), q("inl_H"), q("inl_F"), q("score"), q("rh"), q("hyp"), q("hyp_score"), q("result")))
+        return out
+
     # -- static SearchByProjection(keyFrame, mapPoints, Map*, th): the fuse (ORBMatcher.cpp:524-592) ------------
     def SearchFuseDevice(self, d, nq, grid_cols, grid_rows, list_cap=48, stream=None):
         """orbm_search_fuse_device on torch device tensors: d = dict(q_desc, q_xy, q_radius, q_level, q_ok, kps, desc, cell_start,
@@ -804,6 +840,16 @@ class ORBMatcher:
         _lib.check(self._L.orbm_search_fuse(self._hd._h, _vp(qd), _vp(qx), _vp(qr), _vp(ql), _vp(qk), len(qd), _vp(k),
                                             _vp(d), len(k), img_w, img_h, _vp(s2), len(s2), _vp(bi), _vp(bd), C.byref(n)))
         return bi, bd, n.value
+
+
+TWO_VIEW_RNG_DEFAULT = 0xFFFFFFFF   # ORBM_TWO_VIEW_RNG_DEFAULT: cv::RNG's default state
+
+
+def two_view_sets(n_matches, iters=200, rng_state=0):
+    """orbm_two_view_sets: the eight-point sets of TwoViewReconstruction.cpp:42-58, int32 [iters, 8]; a host function, no GPU needed"""
+    sets = np.zeros((max(int(iters), 0), 8), np.int32)
+    _lib.check(_mlib().orbm_two_view_sets(n_matches, iters, rng_state, _vp(sets)))
+    return sets
 
 
 def local_ba_problem_device(matcher, *args, **kwargs):
