@@ -1271,7 +1271,7 @@ int orbm_apply_scale_rotation_device(orbm_t *h, const struct orbi_calib *calib, 
  * Tracking.cpp:620 through Pinhole.cpp:90 / Fisheye.cpp:138), the consumer of the d_matches12 that
  * orbm_search_for_initialization_device leaves on the device: the match list (:26-30), the draw of the eight-point sets (:42-58),
  * FindHomography and FindFundamental (:86-161) with ComputeH21 / ComputeF21 (:163-224), CheckHomography / CheckFundamental (:226-344)
- * and Normalize (:558-596), and the RH decision (:73-79).  ReconstructH / ReconstructF / CheckRT / DecomposeE stay with the caller.
+ * and Normalize (:558-596), and the RH decision (:73-79).  ReconstructH / ReconstructF / CheckRT / DecomposeE: the next section, orbm_two_view_pose_device.
  *
  * Inputs.  d_kps1 [n1], d_kps2 [n2]: orbx_kp records, UNDISTORTED by the caller (Fisheye's cv::fisheye::undistortPoints is not part
  * of this); only x and y are read.  d_matches12 [n1]: m in [0, n2) is a match, anything else none.  sigma: the reference's 1.f
@@ -1354,6 +1354,109 @@ int orbm_two_view_ransac(orbm_t *h, const void *kps1, int n1, const void *kps2, 
  * generator running on from set to set (rng_state 0: ORBM_TWO_VIEW_RNG_DEFAULT).  ORBX_E_ARG: n_matches < 8, iters outside
  * 1 .. 1024, sets NULL. */
 int orbm_two_view_sets(int n_matches, int iters, uint64_t rng_state, int32_t *sets);
+
+/* ---- Two-view initialisation: the pose and the points ---------------------------------------------------------------------------------
+ * The back half of TwoViewReconstruction::Reconstruct (modules/Frontend/TwoViewReconstruction.cpp): the dispatch (:79-83), ReconstructH
+ * (:346-475), ReconstructF (:477-556), CheckRT (:598-687), Triangulate (:689-705), DecomposeE (:707-724), and the tail in which the
+ * tracker consumes the result (Tracking.cpp:622-627).  It reads exactly what orbm_two_view_ransac_device writes, from device memory,
+ * and goes directly behind it on the same stream.
+ *
+ * Inputs.  fx, fy, cx, cy: K.  d_kps1 [n1], d_kps2 [n2]: orbx_kp records, UNDISTORTED by the caller as for the RANSAC; only x and y are
+ * read.  d_matches12 [n1].  d_pairs, d_H, d_F, d_inl_H, d_inl_F and d_ransac_result (int32 x 8): the RANSAC's outputs of those names
+ * (its d_result).  family: -1 takes the RANSAC's choice from d_ransac_result[4] ON THE DEVICE (1: H), 0 forces F, 1 forces H -- for a
+ * caller who wants the runner-up.  d_ransac_result[1] != 0 (the RANSAC refused) is found on the device too: the call then writes
+ * d_result and nothing else.  d_ransac_result[0] is kept inside 0 .. n1, and a row of d_pairs outside [0, n1) x [0, n2) is skipped.
+ * sigma: the reference's 1.f; th2 = 4.f * sigma * sigma (:451, :505).  min_parallax: the reference's 1.f (degrees).
+ *
+ * Two places where the reference cannot be followed literally.
+ *   ReconstructH's hypothesis vectors.  It constructs vR(8), vt(8), vn(8) and then push_backs the eight computed hypotheses BEHIND them,
+ *     so its loop at :447 checks eight default-constructed, uninitialised matrices.  The library checks the eight computed hypotheses
+ *     in the order they are computed: d' = d2 for i = 0..3 (rows 0..3), then d' = -d2 for i = 0..3 (rows 4..7) -- the evident intent, and
+ *     upstream ORB-SLAM's.  vn is never read and is not built.
+ *   Triangulate returning false.  It returns false on Ph(3) == 0 and leaves Pc1 unset, which CheckRT then reads.  Here the division
+ *     produces a non-finite point and the isfinite gate of :636 drops the match.
+ *
+ * Arithmetic.
+ *   The decomposition runs in DOUBLE on the float H21 / F21 and the float K and is rounded to float once per hypothesis (R, and t over
+ *     its norm), as the RANSAC's solve does and for its reason (a fixed-sweep float Jacobi leaves several times the float SVD's error):
+ *     E = (K^T * F21) * K; A = (K^-1 * H21) * K with K^-1 = [1 / fx, 0, -cx / fx; 0, 1 / fy, -cy / fy; 0, 0, 1]; the 3 x 3 SVD by a
+ *     one-sided Jacobi (8 sweeps; the columns of B = A * V over their norms are U, sorted by descending norm).  DecomposeE needs the
+ *     column of U of the zero singular value, which B does not hold: U.col(2) = u0 x u1; R1 = U * W * V^T, R2 = U * W^T * V^T, each
+ *     negated when its determinant is negative (:720-723); t = U.col(2).  H: s = det(U) * det(V^T), the degeneracy test
+ *     d1 / d2 < 1.00001 || d2 / d3 < 1.00001 on the double singular values, and the formulas of :376-436 as written.
+ *   The ORDER of the hypotheses is the library's own.  An SVD is unique only up to joint sign flips of (u_i, v_i), and up to independent
+ *     signs on the null pair of E; these flips permute {R1, R2} x {t, -t} and the eight of H.  The order here is fixed by this Jacobi
+ *     and deterministic -- the same input gives the same bytes -- but another SVD lists the same SET in another order.  The set of
+ *     hypotheses and the decision are what the reference determines; compare hypotheses by nearest (R, t), never by index.  F's rows
+ *     are (R1, t), (R2, t), (R1, -t), (R2, -t) of this library's R1, R2, t.
+ *   CheckRT runs in float, no fused multiply-add, `/` and sqrt correctly rounded, in the reference's statement order; a row times a
+ *     column reads ((p0 + p1) + p2) + p3.  P1 = K [I | 0], P2 = K * [R | t] in pixel units, O2 = -R^T * t.  Triangulate's 4 x 4 right
+ *     singular vector is orbm_triangulate_matches_device's solve (a one-sided Jacobi, six sweeps, shared source).  n1.normalize() divides
+ *     by sqrt(n1 . n1) where that is above 0.  cosParallax is compared with 0.99998 in double; proj_u1 = (fx * Pc1(0)) * invZ1 + cx.
+ *   The parallax is (acosf(c) * 180.f) / M_PIf32 with c the element of rank min(50, nGood - 1) of the good cosines in ascending order:
+ *     an exact order statistic (a radix select over the order-preserving integer image of the floats), not a sort; acosf is the
+ *     device's.
+ *   The decision is orbm_two_view_decide's, below.
+ *
+ * Outputs.  Every one is written by a call that gets as far as the hypotheses (d_result[0] != 1):
+ *   d_R21 [9], d_t21 [3] float, row-major: the winning hypothesis; zeros when not accepted.
+ *   d_points3D [n1][3] float, per key point of frame 1: Pc1 of the winning hypothesis where CheckRT stored it (:672: every good match,
+ *     those with cosParallax >= 0.99998 too), zeros elsewhere and when not accepted.
+ *   d_triangulated [n1] uint8: the winner's vbGood; zeros when not accepted.
+ *   d_matches12_out [n1] int32 (Tracking.cpp:622-627): d_matches12 with every entry >= 0 that is not triangulated set to -1 when
+ *     accepted; d_matches12 unchanged when not.  The next stage reads its input from the device.
+ *   d_hyp_R [8][9], d_hyp_t [8][3] float, d_hyp_good [8] int32, d_hyp_parallax [8] float: every hypothesis, its nGood and its parallax
+ *     (degrees).  F fills the first four rows and zeros the rest; a degenerate H zeros all eight.
+ *   d_hyp_code [8][n1] uint8, may be NULL: where each key point of frame 1 left CheckRT under each hypothesis.  0 no match, 1 matched
+ *     but not an inlier of the family used (:628), 2 not finite (:636), 3 behind camera 1 (:649), 4 behind camera 2 (:653), 5 error in
+ *     image 1 (:661), 6 error in image 2 (:669), 7 good (nGood and vbGood), 8 good without parallax (nGood and the point, vbGood false).
+ *     The rows of hypotheses that do not exist are zeros.
+ *   d_result, int32 x 16: [0] status: 0 accepted, 1 the RANSAC refused (ONLY d_result is written; [1] the family, [3] -1, the rest 0),
+ *     2 H degenerate (:370), 3 no clear winner or too few good, 4 parallax too low (the other conditions hold); [1] the family used
+ *     (0 F, 1 H); [2] the number of hypotheses (4, 8, or 0 when degenerate); [3] the winner's row, -1 unless accepted; [4] nInlier;
+ *     [5] minGood; [6] the number triangulated (0 unless accepted); [7] matches left: the entries of d_matches12_out in [0, n2);
+ *     [8..15] a copy of d_hyp_good.
+ *
+ * Shape (latency: at most 8 hypotheses and a few thousand matches, 65536 at the cap).  Three launches on `stream`, no host wait, no
+ * allocation in steady state: k_tvp_decompose, one lane (the 3 x 3 Jacobi and the hypotheses in constant-indexed registers);
+ * k_tvp_check, ONE workgroup of 1024 per hypothesis, threads striding over the match list, nGood and nInlier by wave popcounts added in
+ * LDS, the select four 8-bit digits with a 256-bin histogram in LDS each, the keys in handle scratch; k_tvp_decide, ONE workgroup of
+ * 1024: the decision, then the winner walked AGAIN for d_points3D / d_triangulated (the same arithmetic on the same inputs, so the same
+ * gates bit for bit, as orbm_triangulate_matches_device's second walk), then d_matches12_out.  Handle scratch (grow-only, a block of its
+ * own): 32 bytes and 8 rows of n1 keys; one call in flight per handle.  As compiled for gfx950 -- VGPRs / scratch / static LDS:
+ * k_tvp_decompose 168 / 0 / 0 B, k_tvp_check 86 / 0 / 1104 B, k_tvp_decide 90 / 0 / 8 B: no scratch memory; the two workgroups of sixteen
+ * waves within the 128 VGPRs a thread of theirs can have, the single wave of k_tvp_decompose within 256.
+ * Measured device time of one call (profiles/two_view_latency.txt): 56 us at 250 matches (229 inliers), 133 us at 1647 (1553 inliers);
+ * the search, the RANSAC and this call on one stream 271 and 734 us.  The float32 numpy model of this half takes 2 and 12 ms on the host
+ * behind a wait and a read-back: an order of magnitude only, numpy is not the reference's C++.
+ * Refused with ORBX_E_ARG before any launch, every byte left as passed: a required pointer NULL (all but d_hyp_code), n1 or n2 < 1,
+ * sigma <= 0, fx or fy not finite or not positive, family outside -1 .. 1.  Behind those, also before any launch: n1 or n2 above
+ * ORBM_TWO_VIEW_MAX_KEYPOINTS is ORBX_E_UNSUPPORTED.  Without a HIP device the call fails with ORBX_E_NO_DEVICE.  Enqueued on `stream`
+ * (NULL: orbx.h, "Streams"). */
+int orbm_two_view_pose_device(orbm_t *h, float fx, float fy, float cx, float cy, const void *d_kps1, int n1, const void *d_kps2, int n2,
+                              const int32_t *d_matches12, const int32_t *d_pairs, const float *d_H, const float *d_F, const uint8_t *d_inl_H,
+                              const uint8_t *d_inl_F, const int32_t *d_ransac_result, int family, float sigma, float min_parallax,
+                              float *d_R21, float *d_t21, float *d_points3D, uint8_t *d_triangulated, int32_t *d_matches12_out,
+                              float *d_hyp_R, float *d_hyp_t, int32_t *d_hyp_good, float *d_hyp_parallax, uint8_t *d_hyp_code,
+                              int32_t *d_result, void *stream);
+/* The same with host pointers throughout: synchronous on the handle's stream, one pinned copy each way, the same kernels and the
+ * same bytes as the device entry point. */
+int orbm_two_view_pose(orbm_t *h, float fx, float fy, float cx, float cy, const void *kps1, int n1, const void *kps2, int n2,
+                       const int32_t *matches12, const int32_t *pairs, const float *H, const float *F, const uint8_t *inl_H,
+                       const uint8_t *inl_F, const int32_t *ransac_result, int family, float sigma, float min_parallax, float *R21,
+                       float *t21, float *points3D, uint8_t *triangulated, int32_t *matches12_out, float *hyp_R, float *hyp_t,
+                       int32_t *hyp_good, float *hyp_parallax, uint8_t *hyp_code, int32_t *result);
+/* The decision of ReconstructF (family 0: n_good and parallax hold four entries) or ReconstructH (family 1: eight) on the host, no
+ * device needed: the same code the device runs.  winner: the accepted hypothesis or -1; min_good; reason: 0 accepted, 3 no clear winner
+ * or too few good, 4 parallax too low (and the other conditions hold).  The reference's spellings are kept:
+ *   H: minGood = min(cvRound(0.6 * nInlier), 100), to nearest with ties to even, in double; bestGood / secondBestGood tracked as the
+ *     loop of :447-464 does, the FIRST maximum winning; accepted when secondBestGood < 0.75 * bestGood && bestParallax >= minParallax &&
+ *     bestGood > minGood.
+ *   F: minGood = min(cvFloor(0.6 * nInlier), 100); goodTh = cvFloor(0.7 * maxGood); maxGood < minGood || nSimilar > 1 rejects; the
+ *     cascade of :524-552, so the first hypothesis that reaches the maximum is the one asked; its parallax test is a strict `>`.
+ * ORBX_E_ARG: a pointer NULL, family not 0 or 1, n_inlier < 0. */
+int orbm_two_view_decide(int family, const int32_t *n_good, const float *parallax, int n_inlier, float min_parallax, int32_t *winner,
+                         int32_t *min_good, int32_t *reason);
 
 /* MapPoint::computeDescriptor (modules/BasicObject/MapPoint.cpp:103-152) for n_groups map points at once.
  * Group g = the descriptors desc[off[g] .. off[g+1]) of one point's observations (the caller skips bad key frames,

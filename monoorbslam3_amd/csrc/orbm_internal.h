@@ -17,6 +17,9 @@ __attribute__((visibility("hidden"))) hipError_t orbm_host_stage(orbm_t *c, size
 // The scratch of the two-view RANSAC (orbm_two_view.hip): `bytes` of device memory of the handle's own, grow-only, apart from the
 // blocks the searches use, so that a search and the RANSAC behind it on one stream share nothing.  One call in flight per handle.
 __attribute__((visibility("hidden"))) hipError_t orbm_two_view_scratch(orbm_t *c, size_t bytes, void **dev);
+// The same for the pose recovery behind it (orbm_two_view_pose.hip), a block of its own: growing it never frees what the RANSAC ahead of
+// it on the stream still reads.
+__attribute__((visibility("hidden"))) hipError_t orbm_two_view_pose_scratch(orbm_t *c, size_t bytes, void **dev);
 
 // ---- what the map-side device entry points share (orbm_project / triangulate / refresh / observations) -------------------------
 constexpr int ORBM_MAX_POINTS = 1 << 19;   // map points per call: k_project's frustum form and k_cull keep one bit per point in 64 KB of LDS

@@ -1404,6 +1404,7 @@ struct orbm_ctx {
     DevBuf a, b, out, q_idx, c_begin, c_len, out_begin, c_idx, row_ok, col_ok, bidx, bbest, bsecond;
     DevBuf w_in, w_out, w_grid; // window searches: staged inputs, lists, CSR grid + scratch
     DevBuf two_view;            // orbm_two_view_ransac{,_device}: the sets, the hypotheses, their scores and mask rows (orbm_two_view.hip)
+    DevBuf two_view_pose;       // orbm_two_view_pose{,_device}: the head and the eight rows of cosine keys (orbm_two_view_pose.hip)
     PinBuf h_in, h_out;
     int window_on_device = 1;   // ORBM_VAR_WINDOW = 1 keeps the host grid (the parity twin of the device lists)
     int best2_variant = 0;      // ORBM_VAR_BEST2: 0 = fp4, 1 = i8, 2 = valu
@@ -1463,6 +1464,13 @@ hipError_t orbm_two_view_scratch(orbm_t *c, size_t bytes, void **dev) // orbm_in
 {
     const hipError_t e = need(c->two_view, bytes);
     *dev = c->two_view.p;
+    return e;
+}
+
+hipError_t orbm_two_view_pose_scratch(orbm_t *c, size_t bytes, void **dev) // orbm_internal.h
+{
+    const hipError_t e = need(c->two_view_pose, bytes);
+    *dev = c->two_view_pose.p;
     return e;
 }
 

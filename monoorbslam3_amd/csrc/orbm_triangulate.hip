@@ -28,6 +28,7 @@
 #include "orb_host.h"
 #include "orbm_internal.h"
 #include "orbm_camera.h"
+#include "orbm_jacobi.h"
 
 #pragma clang fp contract(off)
 
@@ -35,7 +36,6 @@ namespace {
 
 constexpr int TR_T = 1024;     // threads of the one workgroup
 constexpr int TR_WAVES = TR_T / 64;
-constexpr int TR_SWEEPS = 6;
 
 struct TriArgs {               // by value in the launch's arguments
     orbm_proj_camera cam;
@@ -54,28 +54,7 @@ struct TriPoint {
 // gate codes = index of the counter in d_result (1 is the overflow flag, no gate)
 enum { T_ACCEPTED = 0, T_FAIL = 2, T_ILLEGAL = 3, T_PARALLAX = 4, T_NEGATIVE = 5, T_REPROJ = 6, T_SCALE = 7 };
 
-__device__ __forceinline__ float dot4(const float (&a)[4], const float (&b)[4]) { return ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]; }
-
-// one Hestenes rotation of the columns p, q of A (stored by column) and of V
-__device__ __forceinline__ void rotate(float (&ap)[4], float (&aq)[4], float (&vp)[4], float (&vq)[4])
-{
-    const float alpha = dot4(ap, ap), beta = dot4(aq, aq), gamma = dot4(ap, aq);
-    float t = 0.f;
-    if (gamma != 0.f) {   // (NaN takes this branch and spreads)
-        const float zeta = (beta - alpha) / (2.f * gamma);
-        t = copysignf(1.f, zeta) / (fabsf(zeta) + sqrtf(1.f + zeta * zeta));
-    }
-    const float c = 1.f / sqrtf(1.f + t * t), s = c * t;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float x = ap[r], y = aq[r];
-        ap[r] = c * x - s * y;
-        aq[r] = s * x + c * y;
-        const float vx = vp[r], vy = vq[r];
-        vp[r] = c * vx - s * vy;
-        vq[r] = s * vx + c * vy;
-    }
-}
+// dot4, rotate (one Hestenes rotation of two columns) and TR_SWEEPS: orbm_jacobi.h, shared with orbm_two_view_pose.hip
 
 // camera->backProject(kp.pt): Pinhole.cpp:40-42 / Fisheye.cpp:68-73
 __device__ __forceinline__ void back_project(const TriArgs &a, float inv_fx, float inv_fy, const float *__restrict__ scale, int per_kp_index,

@@ -42,6 +42,7 @@
 #include "orb_device.h"
 #include "orb_host.h"
 #include "orbm_internal.h"
+#include "orbm_jacobi.h"
 
 #pragma clang fp contract(off)
 
@@ -224,34 +225,7 @@ __device__ __forceinline__ double sum16(double v)
     return v;
 }
 
-// the rotation angle of one Hestenes step from the three dot products
-__device__ __forceinline__ void jacobi_cs(double alpha, double beta, double gamma, double &c, double &s)
-{
-    double t = 0.0;
-    if (gamma != 0.0) {
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    }
-    c = 1.0 / sqrt(1.0 + t * t);
-    s = c * t;
-}
-
-__device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
-__device__ __forceinline__ void rotate3(double (&ap)[3], double (&aq)[3], double (&vp)[3], double (&vq)[3])
-{
-    double c, s;
-    jacobi_cs(dot3(ap, ap), dot3(aq, aq), dot3(ap, aq), c, s);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double x = ap[r], y = aq[r];
-        ap[r] = c * x - s * y;
-        aq[r] = s * x + c * y;
-        const double vx = vp[r], vy = vq[r];
-        vp[r] = c * vx - s * vy;
-        vq[r] = s * vx + c * vy;
-    }
-}
+// jacobi_cs (the rotation angle of one Hestenes step), dot3 and rotate3: orbm_jacobi.h, shared with orbm_two_view_pose.hip
 
 // ComputeF21 :220-223: U diag(w0, w1, 0) V^T of the row-major 3 x 3 `m`, in place
 __device__ __forceinline__ void rank2(double (&m)[9])

@@ -172,6 +172,9 @@ def _mlib():
             "orbm_two_view_ransac_device": (i32, [vp, vp, i32, vp, i32, vp, f32, i32, C.c_uint64] + [vp] * 12),
             "orbm_two_view_ransac": (i32, [vp, vp, i32, vp, i32, vp, f32, i32, C.c_uint64] + [vp] * 11),
             "orbm_two_view_sets": (i32, [i32, i32, C.c_uint64, vp]),
+            "orbm_two_view_pose_device": (i32, [vp, f32, f32, f32, f32, vp, i32, vp, i32] + [vp] * 7 + [i32, f32, f32] + [vp] * 12),
+            "orbm_two_view_pose": (i32, [vp, f32, f32, f32, f32, vp, i32, vp, i32] + [vp] * 7 + [i32, f32, f32] + [vp] * 11),
+            "orbm_two_view_decide": (i32, [i32, vp, vp, i32, f32, vp, vp, vp]),
         }
         for name, (res, args) in sigs.items():
             fn = getattr(L, name)
@@ -798,6 +801,48 @@ class ORBMatcher:
             q("F"), q("inl_H"), q("inl_F"), q("score"), q("rh"), q("hyp"), q("hyp_score"), q("result")))
         return out
 
+    # -- ReconstructH / ReconstructF behind the RANSAC (TwoViewReconstruction.cpp:79-83, :346-556, :598-724) ------
+    def TwoViewPoseDevice(self, d, n1, n2, K, family=-1, sigma=1.0, min_parallax=1.0, stream=None):
+        """orbm_two_view_pose_device on torch device tensors: d = dict(kps1, kps2, matches12 and, as TwoViewRansacDevice left them, pairs, H,
+        F, inl_H, inl_F, ransac_result i32 [8]; out: R21 f32 [9], t21 f32 [3], points3D f32 [n1, 3], triangulated u8 [n1], matches12_out
+        i32 [n1], hyp_R f32 [8, 9], hyp_t f32 [8, 3], hyp_good i32 [8], hyp_parallax f32 [8], hyp_code u8 [8, n1] (optional), result i32
+        [16]).  K = (fx, fy, cx, cy).  family -1: the RANSAC's choice, read on the device; 0 F, 1 H.  Enqueues on `stream`; nothing is
+        copied or synchronised.  result[0] = 1 (the RANSAC refused): only result was written."""
+        p = lambda k: d[k].data_ptr() if d.get(k) is not None else None  # noqa: E731
+        fx, fy, cx, cy = K
+        _lib.check(self._L.orbm_two_view_pose_device(
+            self._hd._h, fx, fy, cx, cy, p("kps1"), n1, p("kps2"), n2, p("matches12"), p("pairs"), p("H"), p("F"), p("inl_H"), p("inl_F"),
+            p("ransac_result"), family, sigma, min_parallax, p("R21"), p("t21"), p("points3D"), p("triangulated"), p("matches12_out"),
+            p("hyp_R"), p("hyp_t"), p("hyp_good"), p("hyp_parallax"), p("hyp_code"), p("result"), _lib.stream_arg(stream)))
+
+    def TwoViewPose(self, kps1, kps2, matches12, ransac, K, family=-1, sigma=1.0, min_parallax=1.0, out=None, codes=True):
+        """orbm_two_view_pose on numpy arrays; `ransac` is what TwoViewRansac returned (pairs, H, F, inl_H, inl_F, result).  Returns a dict
+        of the outputs (names as for TwoViewPoseDevice; hyp_code with `codes`); `out`, a dict of C-contiguous arrays of those names and
+        types, is written in place instead."""
+        k1 = np.ascontiguousarray(kps1, dtype=KP_DTYPE)
+        k2 = np.ascontiguousarray(kps2, dtype=KP_DTYPE)
+        m12 = np.ascontiguousarray(matches12, dtype=np.int32)
+        n1 = len(k1)
+        ins = dict(pairs=(np.int32, (n1, 2)), H=(np.float32, (9,)), F=(np.float32, (9,)), inl_H=(np.uint8, (n1,)), inl_F=(np.uint8, (n1,)),
+                   result=(np.int32, (8,)))
+        r = {k: np.ascontiguousarray(ransac[k], dtype=dt) for k, (dt, _) in ins.items()}
+        for k, (_, shape) in ins.items():
+            assert r[k].shape == shape, k
+        types = dict(R21=(np.float32, (9,)), t21=(np.float32, (3,)), points3D=(np.float32, (n1, 3)), triangulated=(np.uint8, (n1,)),
+                     matches12_out=(np.int32, (n1,)), hyp_R=(np.float32, (8, 9)), hyp_t=(np.float32, (8, 3)), hyp_good=(np.int32, (8,)),
+                     hyp_parallax=(np.float32, (8,)), hyp_code=(np.uint8, (8, n1)), result=(np.int32, (16,)))
+        if out is None:
+            out = {k: np.zeros(shape, dt) for k, (dt, shape) in types.items() if codes or k != "hyp_code"}
+        for k, a in out.items():
+            assert a.dtype == types[k][0] and a.flags["C_CONTIGUOUS"], k
+        q = lambda k: _vp(out[k]) if out.get(k) is not None else None  # noqa: E731
+        fx, fy, cx, cy = K
+        _lib.check(self._L.orbm_two_view_pose(
+            self._hd._h, fx, fy, cx, cy, _vp(k1), n1, _vp(k2), len(k2), _vp(m12), _vp(r["pairs"]), _vp(r["H"]), _vp(r["F"]), _vp(r["inl_H"]),
+            _vp(r["inl_F"]), _vp(r["result"]), family, sigma, min_parallax, q("R21"), q("t21"), q("points3D"), q("triangulated"),
+            q("matches12_out"), q("hyp_R"), q("hyp_t"), q("hyp_good"), q("hyp_parallax"), q("hyp_code"), q("result")))
+        return out
+
     # -- static SearchByProjection(keyFrame, mapPoints, Map*, th): the fuse (ORBMatcher.cpp:524-592) ------------
     def SearchFuseDevice(self, d, nq, grid_cols, grid_rows, list_cap=48, stream=None):
         """orbm_search_fuse_device on torch device tensors: d = dict(q_desc, q_xy, q_radius, q_level, q_ok, kps, desc, cell_start,
@@ -850,6 +895,18 @@ def two_view_sets(n_matches, iters=200, rng_state=0):
     sets = np.zeros((max(int(iters), 0), 8), np.int32)
     _lib.check(_mlib().orbm_two_view_sets(n_matches, iters, rng_state, _vp(sets)))
     return sets
+
+
+def two_view_decide(family, n_good, parallax, n_inlier, min_parallax=1.0):
+    """orbm_two_view_decide: the decision of ReconstructF (family 0, four hypotheses) or ReconstructH (family 1, eight) from the
+    per-hypothesis nGood and parallax; returns (winner or -1, minGood, reason: 0 accepted, 3 no clear winner or too few good, 4 parallax
+    too low); a host function, the code the device runs, no GPU needed"""
+    g = np.ascontiguousarray(n_good, dtype=np.int32)
+    p = np.ascontiguousarray(parallax, dtype=np.float32)
+    assert family not in (0, 1) or (len(g) >= (8 if family else 4) and len(p) >= (8 if family else 4))
+    w, mg, why = C.c_int32(-1), C.c_int32(0), C.c_int32(0)
+    _lib.check(_mlib().orbm_two_view_decide(family, _vp(g), _vp(p), n_inlier, min_parallax, C.byref(w), C.byref(mg), C.byref(why)))
+    return w.value, mg.value, why.value
 
 
 def local_ba_problem_device(matcher, *args, **kwargs):
